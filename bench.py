@@ -11,11 +11,15 @@ border rule, frames per launch -- rank 0 decides, every rank runs what it receiv
 `python bench.py --gpus N` spawns the N ranks itself when no launcher did (torch.distributed.run) and refuses to run on
 fewer than N GPUs.
 
-`roofline.traffic` is measured IN this run: after the timed region rank 0 re-runs one sub-batch of the same launch geometry under
-`rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE` (separate passes, nothing else traced), together with a 16 B / lane copy of known
-size that calibrates both counters on this box (MI355X_MICROARCH.md, HBM section).
+A plain run does only what the headline needs: set up, warm up, time `--steps` steps, write the outputs (`--dump-outputs DIR`) and
+print the line.  `roofline.achieved` / `frac` come from the events of the timed launches themselves.
 
-Prints ONE JSON line on rank 0 (contract in the task statement) including `roofline` and `cpu_baseline`.
+`--full` adds everything else: the bit-exact parity gate before the timed region and, after it, the measured copy rate, the cfg4 / cfg5
+legs on N > 1 GPUs, and on one GPU `roofline.traffic` (rank 0 re-runs one sub-batch of the same launch geometry under
+`rocprofv3 --pmc FETCH_SIZE` and `--pmc WRITE_SIZE`, separate passes, nothing else traced, together with a 16 B / lane copy of known
+size that calibrates both counters on the GPU at hand), `cpu_baseline`, BASELINE configs 2-5 and the host-inclusive rows.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); under --full it includes `cpu_baseline` and the per-config summary.
 """
 import argparse
 import json
@@ -356,7 +360,8 @@ def emit(res):
         line["cpu_baseline"] = {k: cb[k] for k in ("value", "unit", "cores", "kind", "one_thread_Mpix_s", "cpu_model", "sample") if k in cb}
         line["cpu_baseline"]["sample"] = str(cb.get("sample_short", cb.get("sample", "")))[:200]
     p = res.get("parity")
-    line["parity"] = p if len(json.dumps(p)) < 300 else str(p)[:300]
+    if p is not None:
+        line["parity"] = p if len(json.dumps(p)) < 300 else str(p)[:300]
     if "test_mode" in res:
         line["test_mode"] = res["test_mode"][:120]
     if "summary_us_per_frame_and_frac" in res:
@@ -400,6 +405,21 @@ def parity_gate(cv, frames, out, B):
     for f in rng.integers(0, B, 16).tolist():
         assert torch.equal(out[f], cv.GaussianBlur(frames[f], 5)), f"batch != single-frame path on frame {f}"
     return {"frames_vs_oracle": checked, "frames_vs_single_frame_hook": 16, "result": "bit-exact"}
+
+
+DUMP_SAMPLE = 1 << 22          # pixels of the seeded sample over the whole batch (16 MB as float32)
+
+
+def dump_outputs(d, out):
+    """--dump-outputs DIR: what the timed path handed its caller in the last step -- the blurred batch `out` (B x 2160 x 3840 CV_8UC1, B x 8.3 MB:
+    too large to write whole) -- as float32: the last frame whole (33 MB, every border) and a fixed sample of DUMP_SAMPLE pixels drawn over the
+    whole batch with a seeded generator (the same pixels for the same arguments, so that two builds compare output for output)."""
+    os.makedirs(d, exist_ok=True)
+    torch.cuda.synchronize()
+    np.save(os.path.join(d, "gauss5x5_last_frame.npy"), out[-1].cpu().numpy().astype(np.float32))
+    idx = np.sort(np.random.default_rng(809564).integers(0, out.numel(), DUMP_SAMPLE))
+    sample = out.reshape(-1)[torch.from_numpy(idx).to(out.device)]
+    np.save(os.path.join(d, "gauss5x5_batch_sample.npy"), sample.cpu().numpy().astype(np.float32))
 
 
 def copy_probe(views, reps=2):
@@ -549,11 +569,18 @@ def main():
                     help="4K frames per GPU per step; 0 = sized for the GPU's HBM (see pick_batch)")
     ap.add_argument("--frames-per-launch", type=int, default=int(os.environ.get("MI355CV_BENCH_FPL", "512")),
                     help="a step (one pass over the resident batch) is issued as consecutive launches over sub-batches of this many frames")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-pmc", action="store_true", help="skip the in-run rocprofv3 --pmc passes that measure roofline.traffic")
+    ap.add_argument("--full", action="store_true",
+                    help="also the parity gate, the measured copy rate, roofline.traffic, cpu_baseline, BASELINE configs 2-5, the host-inclusive rows "
+                         "and (N > 1) the cfg4 / cfg5 legs; a plain run times the headline only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step computed as DIR/<name>.npy (float32; see dump_outputs)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip cpu_baseline and the CPU times beside other_configs")
+    ap.add_argument("--no-pmc", action="store_true", help="with --full: skip the in-run rocprofv3 --pmc passes that measure roofline.traffic")
     ap.add_argument("--pmc-child", action="store_true", help=argparse.SUPPRESS)
-    ap.add_argument("--no-other-configs", action="store_true", help="skip BASELINE configs 2-5 (reported under other_configs)")
+    ap.add_argument("--no-other-configs", action="store_true", help="with --full: skip BASELINE configs 2-5 (reported under other_configs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     # test hook, never a reportable number: MI355CV_BENCH_SHARED_GPU=1 lets the N ranks share GPU 0 over gloo, so that the N > 1 code path
     # (spawn, sharding, broadcasts, max-over-ranks timing, the cfg4 / cfg5 legs) can be exercised on a one-GPU box; the line says so
@@ -616,7 +643,7 @@ def main():
     cv.GaussianBlurBatch(frames, KS, BORDER, dst=out)
     torch.cuda.synchronize()
     kernel = _lib.lib.mi355cv_lastKernel().decode()
-    parity = parity_gate(cv, frames, out, B) if rank == 0 else None
+    parity = parity_gate(cv, frames, out, B) if rank == 0 and args.full else None
 
     views = [(frames[lo:lo + FPL], out[lo:lo + FPL]) for lo in range(0, B, FPL)]
     nl = len(views)
@@ -651,10 +678,12 @@ def main():
         t = torch.tensor([elapsed, kern_ms], dtype=torch.float64, device=dev)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed, kern_ms = float(t[0]), float(t[1])
-    copy_gbs = copy_probe(views) if rank == 0 else None
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, out)            # before copy_probe, which overwrites `out`
+    copy_gbs = copy_probe(views) if rank == 0 and args.full else None
 
     legs = None
-    if world > 1 and not args.no_other_configs:
+    if world > 1 and args.full and not args.no_other_configs:
         del frames, out, views
         torch.cuda.empty_cache()
         try:
@@ -670,7 +699,7 @@ def main():
         q = max(1, args.steps // 4)
         # HBM bytes per launch from the PMC counters, measured in THIS run on THIS box (measure_traffic below)
         traffic_info = None
-        if world == 1 and not args.no_pmc:
+        if world == 1 and args.full and not args.no_pmc:
             del frames, out, views
             frames = out = views = None
             torch.cuda.empty_cache()
@@ -697,17 +726,19 @@ def main():
                                        "max": round(float(per_launch.max()), 4)},
                          "step_ms": {"median": round(float(np.median(per_step)), 4), "min": round(float(per_step.min()), 4), "max": round(float(per_step.max()), 4),
                                      "first_quarter_mean": round(float(per_step[:q].mean()), 4),
-                                     "rest_mean": round(float(per_step[q:].mean()), 4) if args.steps > q else None},
-                         "measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 4)},
-            "parity": parity,
+                                     "rest_mean": round(float(per_step[q:].mean()), 4) if args.steps > q else None}},
         }
+        if copy_gbs is not None:
+            res["roofline"].update({"measured_copy_GBs": round(copy_gbs, 1), "frac_of_measured_copy": round(achieved / copy_gbs, 4)})
+        if parity is not None:
+            res["parity"] = parity
         if shared:
             res["test_mode"] = f"{world} ranks SHARE ONE GPU over gloo (MI355CV_BENCH_SHARED_GPU=1): a code-path test, not a measurement"
         if legs is not None:
             res["other_configs"] = legs
-        if world == 1 and not args.no_cpu_baseline:
+        if world == 1 and args.full and not args.no_cpu_baseline:
             res["cpu_baseline"] = cpu_baseline()
-        if world == 1 and not args.no_other_configs:
+        if world == 1 and args.full and not args.no_other_configs:
             frames = out = views = None
             torch.cuda.empty_cache()
             try:

@@ -58,3 +58,12 @@ def test_oversize_summary_is_shed_not_fatal(capsys, tmp_path, monkeypatch):
     assert len(out) == 1 and len(out[0]) < 4096
     d = json.loads(out[0])
     assert "summary" not in d and d["roofline"]["frac"] == 0.73 and d["value"] == 2.9e6
+
+
+def test_full_and_dump_outputs_are_options():
+    """everything beyond the headline sits behind --full; --dump-outputs DIR writes what the timed path computed (--help needs no GPU)"""
+    import subprocess
+    import sys
+    p = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--help"], capture_output=True, text=True, timeout=300, cwd=ROOT)
+    assert p.returncode == 0, p.stderr[-2000:]
+    assert "--full" in p.stdout and "--dump-outputs" in p.stdout

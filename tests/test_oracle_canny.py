@@ -18,7 +18,9 @@ def scene(h, w, cn, seed):
     if cn > 1:
         img = np.stack([np.roll(img, 3 * c, axis=1) if c else img for c in range(cn)], axis=2)
         img = np.ascontiguousarray(img)
-    return O.ref_GaussianBlur(img, 3, 0, 0, 4)
+    # cv::GaussianBlur 3x3, sigma 0, BORDER_REFLECT_101 through the oracle's restatement (bit-exact to the reference: tests/golden/gaussian_u8.npz),
+    # so that the scene needs no reference build
+    return O.orc_gaussianBlurBinomialU8(img, 3, 4)
 
 
 @pytest.mark.ref

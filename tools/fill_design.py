@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""DESIGN.md = docs/DESIGN.md.in with the @PLACEHOLDERS@ of its ledger filled from ONE bench line (the driver's command run on a gpurun box):
+"""DESIGN.md = docs/DESIGN.md.in with the @PLACEHOLDERS@ of its ledger filled from ONE bench line of `python bench.py --full` on an MI355X:
     python tools/fill_design.py profiles/r06_bench_n1.json [suite-tail.txt]
 so that the numbers in the ledger are exactly those of a committed record and never typed by hand."""
 import json, re, sys

@@ -4,7 +4,7 @@
 # Every recipe writes under gpurun_out/ (merged back by gpurun) with the tag $TAG (default: the recipe name); copy what is to be kept into profiles/.
 #   suite            the whole -m gpu suite
 #   tests <files..>  the named test files (-m gpu); must be the last recipe on the line
-#   bench            the driver's bench command, whole JSON line kept
+#   bench            the bench command with --full, whole JSON line kept
 #   trace            the same command under rocprofv3 --kernel-trace --stats + tools/trace_headline.py (the committed rocprof summary of the headline kernel)
 #   why-slow [rows]  tools/why_slow.sh: wave cycles parked / issue-stalled / issuing per kernel of the weak rows
 #   tm               matchTemplate: timing (tools/tm_ab.py), PMC counters (tools/pmc_tm.sh), the MFMA issue-rate micro-benchmark
@@ -30,7 +30,7 @@ while [ $# -gt 0 ]; do
   case $rec in
     suite)     timeout 1500 python -m pytest tests -m gpu -q --timeout 400 > $O/${T}_suite.log 2>&1; echo "suite rc $?"; tail -8 $O/${T}_suite.log | cut -c1-300 ;;
     tests)     timeout 1500 python -m pytest "$@" -m gpu -q --timeout 400 > $O/${T}_tests.log 2>&1; echo "tests rc $?"; tail -12 $O/${T}_tests.log | cut -c1-300; break ;;
-    bench)     timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 > $O/${T}_bench.json 2> $O/${T}_bench.err; echo "bench rc $?"; tail -c 1600 $O/${T}_bench.json; tail -3 $O/${T}_bench.err | cut -c1-200 ;;
+    bench)     timeout 900 python bench.py --gpus 1 --steps 20 --warmup 5 --full > $O/${T}_bench.json 2> $O/${T}_bench.err; echo "bench rc $?"; tail -c 1600 $O/${T}_bench.json; tail -3 $O/${T}_bench.err | cut -c1-200 ;;
     trace)     (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/${T}_trace && timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/${T}_trace -- python $R/bench.py --gpus 1 --steps 20 --warmup 5 --no-pmc --no-other-configs --no-cpu-baseline > $O/${T}_trace_bench.json 2> $O/${T}_trace.err)
                kt=$(find /tmp/${T}_trace -name "*kernel_trace.csv" | head -1); ks=$(find /tmp/${T}_trace -name "*kernel_stats.csv" | head -1)
                python tools/trace_headline.py "$kt" $O/${T}_trace_bench.json > $O/${T}_trace_summary.txt 2>&1; head -40 "$ks" >> $O/${T}_trace_summary.txt; head -14 $O/${T}_trace_summary.txt | cut -c1-220 ;;
