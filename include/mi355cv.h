@@ -437,6 +437,17 @@ MI355CV_API int mi355cv_equalize_hist(const mi355cv_uchar* src_data, size_t src_
 MI355CV_API int mi355cv_threshold_otsu(const mi355cv_uchar* src_data, size_t src_step, mi355cv_uchar* dst_data, size_t dst_step, int width, int height,
         int depth, double maxValue, int thresholdType, double* thresh);
 
+/* --------------------------------------------------- CLAHE (csrc/clahe.hip) */
+
+/* cv::createCLAHE(clipLimit, Size(tilesX, tilesY))->apply(src, dst) (imgproc/src/clahe.cpp; no HAL hook) on CV_8UC1 (depth MI355CV_8U) or CV_16UC1
+ * (MI355CV_16U), bit-identical to the reference.  margin_right / margin_bottom: real pixels of the parent image right of and below the ROI (locateROI), which
+ * the reference's copyMakeBorder takes in before it reflects when a side is not divisible by the tile count; 0 for a whole image.  src == dst is allowed. */
+MI355CV_API int mi355cv_clahe(const mi355cv_uchar* src_data, size_t src_step, mi355cv_uchar* dst_data, size_t dst_step, int width, int height, int depth,
+        int margin_right, int margin_bottom, double clipLimit, int tilesX, int tilesY);
+/* `nframes` whole frames of one geometry, `*_frame_stride` bytes apart (as mi355cv_thresholdBatch): one set of launches per group of frames */
+MI355CV_API int mi355cv_claheBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, mi355cv_uchar* dst_data, size_t dst_step,
+        size_t dst_frame_stride, int nframes, int width, int height, int depth, double clipLimit, int tilesX, int tilesY);
+
 /* --------------------------------------------------- f3: sparse pyramidal Lucas-Kanade (modules/video) */
 
 /* replaces hal_ni_ScharrDeriv (modules/video/src/hal_replacement.hpp:84; caller calcScharrDeriv lkpyramid.cpp:67): CV_8U cn 1..4 ->

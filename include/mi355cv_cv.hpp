@@ -249,6 +249,49 @@ inline void warpPolar(cv::InputArray _src, cv::OutputArray _dst, cv::Size dsize,
     cv::warpPolar(_src, _dst, dsize, center, maxRadius, flags);
 }
 
+// cv::CLAHE (imgproc.hpp; CLAHE_Impl, clahe.cpp).  The reference has no HAL hook for it.  mi355cv::createCLAHE returns a cv::CLAHE whose apply sends a 2-D
+// CV_8UC1 / CV_16UC1 cv::Mat through mi355cv_clahe -- tile histograms, clipping, LUTs and the blend on the device, bit-identical to cv::CLAHE, a submatrix's
+// parent margins passed on for the padding rule -- and hands everything else (UMat, other types, calls the library declines, no device) to the stock object it
+// wraps.  Parameters live in the stock object.
+class CLAHE CV_FINAL : public cv::CLAHE
+{
+public:
+    explicit CLAHE(const cv::Ptr<cv::CLAHE>& stock) : stock_(stock) {}
+    void setClipLimit(double v) CV_OVERRIDE { stock_->setClipLimit(v); }                 double getClipLimit() const CV_OVERRIDE { return stock_->getClipLimit(); }
+    void setTilesGridSize(cv::Size v) CV_OVERRIDE { stock_->setTilesGridSize(v); }       cv::Size getTilesGridSize() const CV_OVERRIDE { return stock_->getTilesGridSize(); }
+    void collectGarbage() CV_OVERRIDE { stock_->collectGarbage(); }
+    void clear() CV_OVERRIDE { stock_->clear(); }
+    bool empty() const CV_OVERRIDE { return stock_->empty(); }
+    void write(cv::FileStorage& fs) const CV_OVERRIDE { stock_->write(fs); }
+    void read(const cv::FileNode& fn) CV_OVERRIDE { stock_->read(fn); }
+    cv::String getDefaultName() const CV_OVERRIDE { return stock_->getDefaultName(); }
+
+    void apply(cv::InputArray _src, cv::OutputArray _dst) CV_OVERRIDE
+    {
+        if (_src.kind() == cv::_InputArray::MAT && !_dst.isUMat()) {
+            cv::Mat src = _src.getMat();
+            const cv::Size grid = stock_->getTilesGridSize();
+            if (src.dims <= 2 && (src.type() == CV_8UC1 || src.type() == CV_16UC1) && !src.empty() && grid.width > 0 && grid.height > 0) {
+                cv::Size whole; cv::Point ofs;
+                src.locateROI(whole, ofs);
+                _dst.create(src.size(), src.type());
+                cv::Mat dst = _dst.getMat();
+                if (mi355cv_clahe(src.data, src.step, dst.data, dst.step, src.cols, src.rows, src.depth(), whole.width - ofs.x - src.cols,
+                                  whole.height - ofs.y - src.rows, stock_->getClipLimit(), grid.width, grid.height) == MI355CV_OK)
+                    return;
+            }
+        }
+        stock_->apply(_src, _dst);
+    }
+private:
+    cv::Ptr<cv::CLAHE> stock_;
+};
+
+inline cv::Ptr<cv::CLAHE> createCLAHE(double clipLimit = 40.0, cv::Size tileGridSize = cv::Size(8, 8))
+{
+    return cv::makePtr<mi355cv::CLAHE>(cv::createCLAHE(clipLimit, tileGridSize));
+}
+
 #ifdef OPENCV_FEATURES_2D_HPP   // cv::FAST lives in opencv2/features2d.hpp; include it before this header to get the wrapper
 // cv::FAST (features2d.hpp; fast.cpp:496).  TYPE_9_16 runs as one call on the GPU at any threshold (cv::FAST's own HAL route, hal_FAST, only covers
 // thresholds <= 20 and moves the score image over PCIe twice); everything else goes to the stock function.

@@ -128,6 +128,8 @@ def _load():
         "mi355cv_cvtMultipliedRGBAtoRGBA": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int]),
         "mi355cv_equalize_hist": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int]),
         "mi355cv_threshold_otsu": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_dbl, c_int, ctypes.POINTER(ctypes.c_double)]),
+        "mi355cv_clahe": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int, c_int]),
+        "mi355cv_claheBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_dbl, c_int, c_int]),
         "mi355cv_ScharrDeriv": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int]),
         "mi355cv_LKOpticalFlowLevel": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_u8p, c_u8p, c_sz, c_u8p, c_u8p,
                                                c_int, c_int, c_int, c_dbl, ctypes.c_bool, ctypes.c_float]),

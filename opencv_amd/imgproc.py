@@ -9,7 +9,7 @@ import numpy as np
 
 from . import _lib
 from .core import (Img, empty_like_kind, bind_stream, torch, CV_8U, CV_16U, CV_16S, CV_32F, CV_64F, _DEPTH_T,  # noqa: F401
-                   BORDER_CONSTANT, BORDER_ISOLATED, BORDER_DEFAULT)
+                   BORDER_CONSTANT, BORDER_ISOLATED, BORDER_DEFAULT, BORDER_REFLECT_101)
 
 L = _lib.lib
 _vp = ctypes.c_void_p
@@ -28,7 +28,7 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "TM_CCOEFF", "TM_CCOEFF_NORMED",
            "pyrDown", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
-           "Canny", "equalizeHist", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
+           "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
            "GaussianBlur", "GaussianBlurBatch", "sepSmoothFixedU8", "getGaussianKernelQ8_binomial",
            "getGaussianKernel", "getGaussianKernelQ"]
@@ -545,6 +545,73 @@ def equalizeHist(src, dst=None):
     bind_stream(s, d)
     _lib.check(L.mi355cv_equalize_hist(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h), "equalize_hist")
     return out
+
+
+# ----------------------------------------------------------------------------- CLAHE (no HAL hook: mi355cv_clahe / mi355cv_claheBatch)
+class CLAHE:
+    """cv::CLAHE (imgproc.hpp; CLAHE_Impl, clahe.cpp) on CV_8UC1 and CV_16UC1 images: tile histograms, clipping, per-tile LUTs and the bilinear blend all
+    run in libmi355cv.so, bit-identical to the reference.  Create with createCLAHE."""
+
+    def __init__(self, clipLimit=40.0, tileGridSize=(8, 8)):
+        self.setClipLimit(clipLimit)
+        self.setTilesGridSize(tileGridSize)
+
+    def setClipLimit(self, clipLimit):
+        self._clip = float(clipLimit)
+
+    def getClipLimit(self):
+        return self._clip
+
+    def setTilesGridSize(self, tileGridSize):
+        tx, ty = (int(v) for v in tileGridSize)
+        if tx <= 0 or ty <= 0:
+            raise ValueError("CLAHE: the tile grid needs a positive number of tiles on each side")
+        self._tiles = (tx, ty)
+
+    def getTilesGridSize(self):
+        return self._tiles
+
+    def collectGarbage(self):
+        """the reference frees its padded copy and LUT buffers here; the library's scratch is pooled per thread"""
+
+    @staticmethod
+    def _check(s):
+        if s.cn != 1 or s.depth not in (CV_8U, CV_16U):
+            raise ValueError("CLAHE: CV_8UC1 or CV_16UC1 only")                            # CV_Assert in CLAHE_Impl::apply
+
+    def apply(self, src, dst=None, roi=None):
+        """CLAHE of `src` (a torch device tensor, a CPU tensor or a numpy array).  roi=(x, y, w, h): process that submatrix of `src`, whose pixels right of
+        and below it are the parent margins the reference's copyMakeBorder takes in (locateROI).  dst may be the source itself (in place)."""
+        view, s, fw, fh, ox, oy = _parent_geometry(src, roi, BORDER_REFLECT_101)
+        self._check(s)
+        out = dst if dst is not None else empty_like_kind(view, s.h, s.w, 1, s.depth)
+        d = Img(out)
+        if (d.w, d.h, d.cn, d.depth) != (s.w, s.h, 1, s.depth):
+            raise ValueError("CLAHE.apply: dst must have the source's size and type")
+        bind_stream(s, d)
+        tx, ty = self._tiles
+        _lib.check(L.mi355cv_clahe(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, s.depth, fw - ox - s.w, fh - oy - s.h, self._clip, tx, ty), "clahe")
+        return out
+
+    def applyBatch(self, frames, dst=None):
+        """CLAHE of each frame of a [N, H, W] tensor (resident in HBM, or a CPU tensor for the pipelined host path), one set of launches per group of frames"""
+        n, s0 = _batch_geom(frames)
+        if frames.dim() != 3:
+            raise ValueError("CLAHE.applyBatch: frames [N, H, W] of one channel")
+        self._check(s0)
+        out = _batch_out(frames, dst, frames.shape, frames.dtype)
+        d0 = Img(out[0])
+        bind_stream(s0, d0)
+        tx, ty = self._tiles
+        rc = L.mi355cv_claheBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, n, s0.w, s0.h, s0.depth,
+                                  self._clip, tx, ty)
+        _lib.check(rc, "claheBatch")
+        return out
+
+
+def createCLAHE(clipLimit=40.0, tileGridSize=(8, 8)):
+    """cv::createCLAHE (clahe.cpp)"""
+    return CLAHE(clipLimit, tileGridSize)
 
 
 ADAPTIVE_THRESH_MEAN_C, ADAPTIVE_THRESH_GAUSSIAN_C = 0, 1
