@@ -49,7 +49,7 @@ __global__ __launch_bounds__(512, ((DMA ? (KSX + KSY <= 6 || (KSX + KSY == 7 && 
                                                   Geom g, const int* __restrict__ bsel /* [strips][8] */, const int* __restrict__ seeds /* [classes][32] */,
                                                   const v4i* __restrict__ rowB /* [classes][2][KSX][64] */, const v4i* __restrict__ colA /* [KSY][64] */)
 {
-    constexpr int NW = sepmx::NWAVE, DEPTH = 2, TW = sepmx::TW, NT = 64 * NW, NCHUNK = (TW - 32 + 32 * KSX) / 16, PC = NCHUNK | 1, P = 16 * PC, NSLOT = DMA ? DEPTH + 1 : 2, NI = (TR * PC + NT - 1) / NT;
+    constexpr int NW = sepmx::NWAVE, DEPTH = 2, TW = sepmx::TW, NT = 64 * NW, NCHUNK = sepmx::pieceChunks(KSX), PC = NCHUNK | 1, P = 16 * PC, NSLOT = DMA ? DEPTH + 1 : 2, NI = (TR * PC + NT - 1) / NT;
     static_assert(NI <= 3, "at most three chunks per lane and step");
     extern __shared__ uint4 lds16[];                     // NSLOT staged blocks of TR x P bytes, two transposition blocks of TR x TW, the column pass' A operand (KSY KB)
     uchar (*stage)[TR * P] = reinterpret_cast<uchar (*)[TR * P]>(lds16);
@@ -65,7 +65,7 @@ __global__ __launch_bounds__(512, ((DMA ? (KSX + KSY <= 6 || (KSX + KSY == 7 && 
     }
     src += (size_t)bz * sframe;
     dst += (size_t)bz * dframe;
-    const int X0 = (int)bx * TW - g.shift, y0 = by * g.seg;
+    const int X0 = sepmx::stripX0(g, (int)bx), y0 = by * g.seg;
     const int rows = min(g.seg, g.H - y0);
     const int nU = (rows + TR - 1) / TR, nT = nU + KSY - 1;
 
@@ -95,8 +95,7 @@ __global__ __launch_bounds__(512, ((DMA ? (KSX + KSY <= 6 || (KSX + KSY == 7 && 
     };
     auto request = [&](int t, int sl) -> int {                                      // (sl = t mod NSLOT, carried by the caller: no division in the walk)
         int issued = 0;
-        const int syA = y0 - g.ay + TR * t + g.offY;                                 // the step's first source row in the parent
-        const bool inner = g.fast && syA >= 1 && syA + TR - 1 <= g.fullH - 2;        // (uniform)
+        const bool inner = sepmx::innerStep(g, y0, t);                               // (uniform)
 #pragma unroll
         for (int i = 0; i < NI; i++) {
             if (64 * (wave + NW * i) >= TR * PC) continue;                            // (wave-uniform)
@@ -104,9 +103,9 @@ __global__ __launch_bounds__(512, ((DMA ? (KSX + KSY <= 6 || (KSX + KSY == 7 && 
             int ln = lane;
             asm volatile("" : "+v"(ln));                                              // (opaque: the chunk's row / column / base pointer are recomputed per step -- hoisted out
             const int q = 64 * (wave + NW * i) + ln, cr = q / PC, cc = q - cr * PC;    //  of the walk they are six more registers per lane, and a spilled register comes back
-            const int e0 = X0 - g.ax * g.cn - g.delta + 16 * cc;                       //  through vector memory, behind every row piece in flight)
+            const int e0 = sepmx::chunkE0(g, X0, cc);                                  //  through vector memory, behind every row piece in flight)
             const bool valid = q < TR * PC && cc < NCHUNK;
-            const int sy = y0 - g.ay + TR * t + cr;
+            const int sy = sepmx::stepRow0(g, y0, t) + cr;
             uchar* slot = &stage[sl][16 * 64 * (wave + NW * i)];
             if (DMA && inner) {
                 // every row of the step is a real row away from the parent's rim: no border, no rim test; a wave-instruction's 64 chunks span three rows, so some lane always
@@ -313,7 +312,7 @@ bool sepmxRun(Stager& stg, const uchar* src, size_t sstep, size_t sframe, uchar*
     static const int xcdEnv = std::getenv("MI355CV_SEPMX_XCD") ? atoi(std::getenv("MI355CV_SEPMX_XCD")) : 1;
     if (!sepmx::plan(g, kx, ky, (uintptr_t)src, sstep, nframes > 1 ? sframe : 0, nframes, segEnv, dmaEnv)) return false;
     constexpr int TW = sepmx::TW;
-    const int nstrips = (g.WE + g.shift + TW - 1) / TW, nseg = (H + g.seg - 1) / g.seg;
+    const int nstrips = sepmx::numStrips(g), nseg = (H + g.seg - 1) / g.seg;
     if (nseg > 65535) return false;
     // The operand block (bsel | seeds | rowB | colA, each part 16-byte aligned) depends on the taps and the row geometry only: callers filter frame after frame with the same
     // parameters, so the last few blocks stay resident on the device (building one costs ~0.1 ms of host time, a per-frame call is ~20 us)

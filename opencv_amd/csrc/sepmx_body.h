@@ -34,7 +34,7 @@ struct Geom {
     int seg;                                   // output rows per segment (a multiple of TR)
     int box, divScale, divDelta, tailStart;    // box filter finish (0: the Gaussian's byte 2; 1: ((s + dd) * ds) >> 23; 2: cvRound(float(s) * scaleF), the row's last (WE % 8) elements in double; 3: saturate(s))
     float scaleF; double scaleD;
-    int fast;                                  // the row pitch is >= 512 bytes: a chunk of a row that is neither the parent's first nor its last lies inside the parent's memory
+    int fast;                                  // every chunk of a row that is neither the parent's first nor its last lies inside the parent's memory (innerFits)
     int sumKy;                                 // the column taps' sum (the seeds of the column pass depend on it)
     int xcd;                                   // 1: workgroup ids are dealt so that the strips of one XCD (linear id mod 8) are neighbours and share their halo columns in its L2
     int ncls;                                  // row-pass operand classes (0 = interior; one per wave whose columns see a left / right border)
@@ -121,6 +121,30 @@ inline void buildColA(const Geom& g, const uint16_t* ky, int8_t* tab)
             }
 }
 
+// The walk's staging geometry, shared by the kernel, plan() and the host emulation (tests/hostemu/sepmx_emu.cpp): strip s owns ROI elements [stripX0, stripX0 + TW); a
+// staged row piece is pieceChunks 16-byte chunks, chunk cc from ROI element chunkE0; step t of the segment at output row y0 stages the TR source rows from stepRow0.
+MX_HD int numStrips(const Geom& g) { return (g.WE + g.shift + TW - 1) / TW; }
+MX_HD int stripX0(const Geom& g, int strip) { return strip * TW - g.shift; }
+MX_HD constexpr int pieceChunks(int ksx) { return (TW - 32 + 32 * ksx) / 16; }
+MX_HD int chunkE0(const Geom& g, int X0, int cc) { return X0 - g.ax * g.cn - g.delta + 16 * cc; }
+MX_HD int stepRow0(const Geom& g, int y0, int t) { return y0 - g.ay + TR * t; }                    // (a ROI row; + offY = the parent's)
+// the UNCHECKED loader: every row of the step is a real row of the parent that is neither its first nor its last, and g.fast (plan()) says that on such rows every chunk
+// of every strip lies inside the parent's memory -- the chunks are loaded without chunkKind's test
+MX_HD bool innerStep(const Geom& g, int y0, int t)
+{
+    const int syA = stepRow0(g, y0, t) + g.offY;
+    return g.fast && syA >= 1 && syA + TR - 1 <= g.fullH - 2;
+}
+// what g.fast promises, from the same expressions: the first chunk of the first strip on the parent's row 1 does not start before the parent's first byte, the last chunk
+// of the last strip on row fullH - 2 ends at or before its last.  (The piece starts shift + ax cn + delta bytes before the ROI's row and ends up to 223 + 32 KSX - ax cn
+// - delta bytes after it: a centred window keeps both under 512, cv::boxFilter with an anchor near the window's left end and 13 K steps reaches 639 bytes.)
+MX_HD bool innerFits(const Geom& g, size_t sstep)
+{
+    const long long lo = (long long)sstep + chunkE0(g, stripX0(g, 0), 0) + g.offX * g.cn;
+    const long long hi = (long long)(g.fullH - 2) * (long long)sstep + chunkE0(g, stripX0(g, numStrips(g) - 1), pieceChunks(g.ksx) - 1) + 16 + g.offX * g.cn;
+    return lo >= 0 && hi <= g.span;
+}
+
 // false: outside what the kernel covers (a tap beyond int8, more K steps than MAXKS)
 inline bool plan(Geom& g, const uint16_t* kx, const uint16_t* ky, uintptr_t srcAddr, size_t sstep, size_t sframe, int nframes, int segOverride = 0, int dmaOverride = -1)
 {
@@ -148,7 +172,6 @@ inline bool plan(Geom& g, const uint16_t* kx, const uint16_t* ky, uintptr_t srcA
     g.ksy = ksyClass(g.ksy);
     if (g.ksx == 13 && g.ksy == 9) return false;                     // (the one pair the kernel is not built for: it would spill registers)
     g.sumKy = sy;
-    g.fast = sstep >= 512;
     // A staged row piece is 224 + 32 KSX bytes from element X0 - ax cn - delta.  With strips at multiples of 256 it starts 16 .. 64 bytes before a 128-byte line and touches
     // one line more than it has to (19 taps: four lines, 512 bytes, for 256 bytes of output: profiles/r06_sepmx.txt); strips moved left by whole 32-column blocks put it
     // where it touches the fewest (the first strip's leading blocks then have no outputs).
@@ -161,8 +184,9 @@ inline bool plan(Geom& g, const uint16_t* kx, const uint16_t* ky, uintptr_t srcA
         }
         g.shift = best;
     }
+    g.fast = sstep >= 512 && innerFits(g, sstep);
     // segments: enough workgroups to fill the chip (256 CUs x 2 x 2), each segment repeats (KSY - 1) tiles of row sums at its top
-    const int nstrips = (g.WE + g.shift + TW - 1) / TW;
+    const int nstrips = numStrips(g);
     int nseg = (1024 + nstrips * nframes - 1) / (nstrips * nframes);
     const int maxseg = (g.H + 4 * TR - 1) / (4 * TR);
     if (nseg > maxseg) nseg = maxseg;

@@ -2242,6 +2242,17 @@ __global__ __launch_bounds__(64 * WS_WAVES) void k_warp32_strip(const uchar* __r
             t = t + c.y;
             out[o] = t;
         }
+        // a footprint wholly outside the source is the border value ITSELF in the reference (remapBilinear's first border branch), not its blend over the ring's
+        // border-filled slots (cval w0 + cval w1 + ... is one or two ulp off cval for most weight pairs): decided per PIXEL, a lane may straddle the rim.  Only lanes on
+        // the rim come here (sx and sy are monotone along the lane: if a pixel is outside, one of the lane's extremes is) -- tested for every pixel of every lane it cost
+        // 2.7 us of 56.9 per 8K frame, this way 2.1 (BASELINE config 3c: the kernel is bound by instruction issue)
+        if (sxHi >= s.sw || sxLo + 1 < 0 || syHi >= s.sh || r0 + 1 < 0) {
+#pragma unroll
+            for (int o = 0; o < 4; o++) {
+                const int sx = X[o] >> 5, sy = Y[o] >> 5;
+                if ((unsigned)(sx + 1) > (unsigned)s.sw || (unsigned)(sy + 1) > (unsigned)s.sh) out[o] = cvf;      // sx >= sw || sx + 1 < 0 || sy >= sh || sy + 1 < 0
+            }
+        }
         // ---- (d) all taps of this step are in registers everywhere, the next step's pieces have landed.  (sched_barrier: the blend stays ABOVE the wait -- left to itself
         // the scheduler sinks it below the barrier, where nothing is in flight any more)
         asm volatile("" : "+v"(out[0]), "+v"(out[1]), "+v"(out[2]), "+v"(out[3]));       // (... and the optimiser does not sink it either: the four results exist here)
@@ -2267,7 +2278,6 @@ __global__ __launch_bounds__(64 * WS_WAVES) void k_warp32_strip(const uchar* __r
         if (live && lane == 0) flags[((size_t)blockIdx.z * w.dh + y) * gridDim.x + blockIdx.x] = anyDefer ? 1 : 0;
         if (live && xl <= xe && !laneDefer && !(a.dbg & 2)) {
             uchar* drow = dst + (size_t)y * dstep;
-            if (laneOut) { out[0] = out[1] = out[2] = out[3] = s.cval[0]; }
             if (xl + 3 <= xe) {
                 typedef float f4 __attribute__((ext_vector_type(4)));
                 __builtin_nontemporal_store(f4{out[0], out[1], out[2], out[3]}, reinterpret_cast<f4*>(drow + (size_t)xl * 4));

@@ -82,3 +82,47 @@ extern "C" int emu_sepmx(const unsigned char* src, size_t sstep, unsigned char* 
     info[0] = g.ksx; info[1] = g.ksy; info[2] = g.delta; info[3] = g.shift; info[4] = g.dma; info[5] = ncls;
     return 0;
 }
+
+// The reach of the kernel's UNCHECKED loader.  request() of k_sepmx takes a shortcut on steps for which sepmx::innerStep holds: every chunk of the step is loaded (or
+// requested asynchronously) without chunkKind's test against the parent's memory.  Zero weights hide whatever such a load returns, so no comparison of outputs can see a
+// chunk that leaves the allocation: this walks every (strip, segment, step, wave-instruction, lane) the kernel walks -- with the kernel's own helpers for the predicate, the
+// strip and chunk origins -- and reports the smallest and largest byte offset, from the parent's first byte, at which a 16-byte chunk would be loaded unchecked.
+// fastRule 0: g.fast as plan() sets it; 1: the pitch rule alone (sstep >= 512), which is what the kernel ran under before plan() looked at the reach -- the test uses it
+// to show that this walk does see the chunks that rule let out.
+// out: min, max, span, chunks walked, g.fast, ksx, shift, delta, dma.  Returns 1 where plan() declines.
+extern "C" int emu_sepmx_inner_reach(size_t sstep, int W, int H, int cn, int fullW, int fullH, int offX, int offY, int border, const uint16_t* kx, int nx, int ax,
+                                     const uint16_t* ky, int ny, int ay, unsigned long long fakeAddr, int fastRule, long long* out)
+{
+    Geom g; memset(&g, 0, sizeof g);
+    g.W = W; g.H = H; g.cn = cn; g.fullW = fullW; g.fullH = fullH; g.offX = offX; g.offY = offY; g.border = border; g.nx = nx; g.ny = ny; g.ax = ax; g.ay = ay;
+    g.box = 3; g.tailStart = (W * cn) & ~7;
+    if (!plan(g, kx, ky, (uintptr_t)fakeAddr, sstep, 0, 1)) return 1;
+    if (fastRule == 1) g.fast = sstep >= 512;
+    const int nstrips = numStrips(g), nseg = (H + g.seg - 1) / g.seg;
+    const int NCHUNK = pieceChunks(g.ksx), PC = NCHUNK | 1, NT = 64 * NWAVE, NI = (TR * PC + NT - 1) / NT;
+    long long lo = 0, hi = 0, count = 0;
+    for (int bx = 0; bx < nstrips; bx++)
+        for (int by = 0; by < nseg; by++) {
+            const int X0 = stripX0(g, bx), y0 = by * g.seg;
+            const int rows = g.seg < g.H - y0 ? g.seg : g.H - y0;
+            const int nU = (rows + TR - 1) / TR, nT = nU + g.ksy - 1;
+            for (int t = 0; t < nT; t++) {
+                if (!innerStep(g, y0, t)) continue;
+                for (int i = 0; i < NI; i++)
+                    for (int wave = 0; wave < NWAVE; wave++) {
+                        if (64 * (wave + NWAVE * i) >= TR * PC) continue;
+                        for (int lane = 0; lane < 64; lane++) {
+                            const int q = 64 * (wave + NWAVE * i) + lane, cr = q / PC, cc = q - cr * PC;
+                            if (!(q < TR * PC && cc < NCHUNK)) continue;
+                            const int e0 = chunkE0(g, X0, cc), sy = stepRow0(g, y0, t) + cr;
+                            const long long a = (long long)(sy + g.offY) * (long long)sstep + e0 + (long long)g.offX * g.cn;
+                            if (!count || a < lo) lo = a;
+                            if (!count || a > hi) hi = a;
+                            count++;
+                        }
+                    }
+            }
+        }
+    out[0] = lo; out[1] = hi; out[2] = g.span; out[3] = count; out[4] = g.fast; out[5] = g.ksx; out[6] = g.shift; out[7] = g.delta; out[8] = g.dma;
+    return 0;
+}

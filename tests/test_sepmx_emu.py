@@ -99,3 +99,93 @@ def test_sepmx_host_half_windows_and_box(emu):
             rc, got, info = run(emu, src, src.shape[:2], (0, 0), border, [1] * kw, ax, [1] * kh, ay, box=box)
             assert rc == 0
             assert np.array_equal(got, o.orc_boxFilter(src, -1, (kw, kh), anchor, norm, border)), (kw, kh, anchor, norm, border, info)
+
+
+# ----------------------------------------------------------------------------- the unchecked loader's reach
+def reach(emu, sstep, w, h, cn, full, off, kx, ax, ky, ay, addr, fast_rule=0, border=1):
+    """(rc, dict) of emu_sepmx_inner_reach: the byte range, from the parent's first byte, of the chunks k_sepmx loads without a bounds test"""
+    kx = np.ascontiguousarray(kx, np.uint16); ky = np.ascontiguousarray(ky, np.uint16)
+    out = (ctypes.c_longlong * 9)()
+    emu.emu_sepmx_inner_reach.restype = ctypes.c_int
+    rc = emu.emu_sepmx_inner_reach(ctypes.c_size_t(sstep), w, h, cn, full[0], full[1], off[0], off[1], border, o.P(kx), len(kx), ax, o.P(ky), len(ky), ay,
+                                   ctypes.c_ulonglong(addr), fast_rule, out)
+    return rc, dict(zip(("min", "max", "span", "count", "fast", "ksx", "shift", "delta", "dma"), list(out)))
+
+
+def inside(r):
+    return r["count"] == 0 or (r["min"] >= 0 and r["max"] + 16 <= r["span"])
+
+
+BASE = 0x7f0000000000
+PITCHES = [512] + list(range(513, 640, 16)) + [527, 639, 640, 1024] + [528, 576, 624]      # (the last three: 16-byte aligned pitches inside the range, i.e. asynchronous staging)
+
+
+def box_geometries(cn, kw):
+    """(pitch, W, fullW, fullH, offX, offY, address, anchor.x, residue): cv::boxFilter rows with the window's anchor from its left end to its right end, widths that put the
+    last strip's start 1 / 128 / 255 elements before the row's end (four channels: elements come in fours -- 4 / 128 / 252), row starts at 16 n and 16 n + 5, whole images
+    and windows with columns of the parent to their left"""
+    for ax in sorted({0, 1, kw // 2, kw - 2, kw - 1}):
+        for pitch in PITCHES:
+            for align in (0, 5):
+                for off_x in (0, 7):
+                    for res in ((1, 128, 255) if cn != 4 else (4, 128, 252)):
+                        yield pitch, ax, align, off_x, res
+
+
+@pytest.mark.parametrize("cn", [1, 3, 4])
+def test_sepmx_unchecked_loads_stay_inside_the_parent(emu, cn):
+    """k_sepmx's `inner` loader (sepmx.hip request(): steps whose rows are all real rows of the parent other than its first and last) loads every chunk without a test.
+    A chunk that leaves the parent's memory there is invisible in the output (its weights are zero), so the walk is replayed on the CPU with the kernel's own helpers
+    (sepmx_body.h: innerStep, stripX0, chunkE0, pieceChunks) and every unchecked chunk must lie in [0, span).  Before plan() looked at the reach (g.fast = pitch >= 512
+    alone), boxFilter with anchor.x near 0 and a window of thirteen K steps staged up to 639 bytes past a row's start: with a pitch of 512 .. 639 bytes the piece of row
+    fullH - 2 ran past the end of the image.  The last loop shows that this replay sees exactly that under the old rule."""
+    ky = [1] * 5                                                                  # anchor.y = 2: steps stage parent rows 32 t - 2 + offY .. + 31
+    seen_fast, seen_slow, old_rule_out, walked = 0, 0, 0, 0
+    for kw in (61, 62, 129, 243, 255):
+        kx = [1] * kw
+        for pitch, ax, align, off_x, res in box_geometries(cn, kw):
+            addr = BASE + off_x * cn + align                                      # the ROI's first byte (the parent starts at BASE + align)
+            rc, r0 = reach(emu, pitch, 8, 95, cn, (off_x + 8, 95), (off_x, 0), kx, ax, ky, 2, addr)
+            if rc == 1:
+                continue                                                          # (more K steps than the row pass has: plan() declines, another kernel's)
+            # the widest ROI the pitch holds with (WE + shift) % 256 == res
+            w = (pitch // cn) - off_x
+            while w > 0 and (w * cn + r0["shift"]) % 256 != res:
+                w -= 1
+            if w <= 0:
+                continue
+            for off_y in (0, 3):
+                full_h = 95 + off_y                                               # the third step's last row is the parent's row fullH - 2: the last row the shortcut may touch
+                geo = (pitch, w, 95, cn, (off_x + w, full_h), (off_x, off_y), kx, ax, ky, 2, addr)
+                rc, r = reach(emu, *geo)
+                assert rc == 0
+                assert r["shift"] == r0["shift"] and (w * cn + r["shift"]) % 256 == res
+                walked += r["count"]
+                seen_fast += r["fast"] != 0; seen_slow += r["fast"] == 0
+                assert inside(r), (cn, kw, ax, pitch, align, off_x, off_y, w, r)
+                rc, old = reach(emu, *geo, fast_rule=1)
+                assert old["count"] > 0                                           # (every pitch here is >= 512 and the image is tall enough: the old rule always took the shortcut)
+                old_rule_out += not inside(old)
+    assert walked > 0 and seen_fast > 0, (walked, seen_fast, seen_slow)          # the shortcut is still taken where it fits ...
+    print("cn", cn, "shortcut kept", seen_fast, "given up", seen_slow, "geometries the pitch rule let out of the parent", old_rule_out)
+    assert seen_slow > 0 and old_rule_out > 0, (seen_slow, old_rule_out)          # ... is given up where it does not, and the replay sees the pitch rule's escapes
+
+
+@pytest.mark.parametrize("cn", [1, 2, 3, 4])
+def test_sepmx_unchecked_loads_gaussian_control(emu, cn):
+    """the centred windows of cv::GaussianBlur (the geometries of test_sepmx_host_half_gaussian, and taller / wider ones so that inner steps exist): the shortcut stays on
+    wherever the pitch is 512 bytes or more, and stays inside"""
+    walked = 0
+    for (w, h) in [(300, 40), (256 // cn, 33), (37, 5), (19, 70), (600 // cn, 9), (600, 200), (512 // cn, 130), (1031, 97)]:
+        for (kw, kh, sigma) in [(19, 19, 3.0), (7, 33, 2.5), (33, 9, 5.0), (65, 11, 11.0), (129, 15, 21.0)]:
+            if (kw - 1) * cn > 384:
+                continue
+            kx, ky = gauss(kw, sigma), gauss(kh, sigma)
+            for addr in (BASE, BASE + 5):
+                for pitch in sorted({w * cn, (w * cn + 15) // 16 * 16, w * cn + 64}):
+                    rc, r = reach(emu, pitch, w, h, cn, (w, h), (0, 0), kx, kw // 2, ky, kh // 2, addr, border=4)
+                    assert rc == 0, (w, h, cn, kw, kh)
+                    assert r["fast"] == (pitch >= 512), (w, h, cn, kw, pitch, r)
+                    assert inside(r), (w, h, cn, kw, kh, pitch, r)
+                    walked += r["count"]
+    assert walked > 0

@@ -163,6 +163,17 @@ def test_sepmx_box_filter(cv, orc, cn):
             if cn == 1:
                 assert "k_sepmx<" in last_kernel(), (last_kernel(), ks)
             assert np.array_equal(got, orc.orc_boxFilter(big, -1, ks, (-1, -1), True, border)), (cn, ks, border, last_kernel())
+    if cn == 1:
+        # a long window anchored at its left end on rows of 528 bytes: the staged row piece reaches 600 bytes past the row's start (thirteen K steps), further than the
+        # pitch, so plan() gives up the unchecked loader (tests/test_sepmx_emu.py has the reach) and every chunk goes through chunkKind; the last inner step of the 96-row
+        # image ends on its last row but one
+        wide = rng.integers(0, 256, (96, 528), dtype=np.uint8)
+        for w in (513, 528, 400):
+            for border in (0, 1, 4):
+                got = cv.boxFilter(_dev(wide)[:, :w], -1, (251, 5), (1, 1), True, border).cpu().numpy()
+                if border != 4:                                             # (249 reflected taps land outside the wave's window: the two-pass box filter's)
+                    assert "k_sepmx<13," in last_kernel() and ",box>" in last_kernel(), last_kernel()
+                assert np.array_equal(got, orc.orc_boxFilter(np.ascontiguousarray(wide[:, :w]), -1, (251, 5), (1, 1), True, border)), (w, border, last_kernel())
     # a window into a larger image, and batches
     parent = rng.integers(0, 256, (90, 400, cn) if cn > 1 else (90, 400), dtype=np.uint8)
     for roi in [(5, 4, 300, 60), (0, 0, 128, 90), (390, 10, 10, 70)]:

@@ -1,6 +1,6 @@
 """GPU parity for rows a7-a9: resize, warpAffine, warpPerspective, remap -- through the C ABI against the oracle.
-8U/16U/16S bit-exact (test_imgwarp_strict.cpp:1089-1092 demands 0 for 8U warpAffine), 32F within 1e-4 relative
-(in practice identical: same operation order, no FMA)."""
+8U/16U/16S bit-exact (test_imgwarp_strict.cpp:1089-1092 demands 0 for 8U warpAffine); 32F bit for bit in warpAffine (check_bits: same operation order, no FMA;
+tests/test_warp32_strip_gpu.py has the strip kernel's edges), within 1e-6 relative elsewhere."""
 import os
 
 import numpy as np
@@ -38,6 +38,15 @@ def check(got, want, tol=1e-6):
         assert orc.rel_err(got, want) <= tol
     else:
         assert np.array_equal(got, want)
+
+
+def check_bits(got, want):
+    """warpAffine with INTER_NEAREST / INTER_LINEAR: CV_32F bit for bit too -- the kernels that serve it (k_warp_lin, k_warp32_tile, k_warp32_strip and the generic sampler
+    behind them) keep remapBilinear's products and order of sums, none contracted into an FMA, and so does the restatement (built with -ffp-contract=off)"""
+    if want.dtype == np.float32:
+        _bits(got, want)
+    else:
+        check(got, want)
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -141,11 +150,11 @@ def test_warp_affine(cv, orc, dtype, cn):
             for interp in (0, 1):
                 for border, bval in [(0, 0.0), (0, (10, 200, 30, 77)), (1, 0), (2, 0), (3, 0), (4, 0)]:
                     want = orc.orc_warpAffine(src, M, dsize, interp, border, bval)
-                    check(cv.warpAffine(dev(src), M, dsize, interp | cv.WARP_INVERSE_MAP, border, bval), want)
+                    check_bits(cv.warpAffine(dev(src), M, dsize, interp | cv.WARP_INVERSE_MAP, border, bval), want)
     M = mats(cv, 61, 45)[0]
-    check(cv.warpAffine(src, M, (61, 45), 1 | cv.WARP_INVERSE_MAP), orc.orc_warpAffine(src, M, (61, 45)))   # host arrays
+    check_bits(cv.warpAffine(src, M, (61, 45), 1 | cv.WARP_INVERSE_MAP), orc.orc_warpAffine(src, M, (61, 45)))   # host arrays
     # forward matrix: the wrapper inverts it as cv::warpAffine does (imgwarp.cpp:2824-2834)
-    check(cv.warpAffine(dev(src), M, (61, 45)), orc.orc_warpAffine(src, cv.invertAffineTransform(M), (61, 45)))
+    check_bits(cv.warpAffine(dev(src), M, (61, 45)), orc.orc_warpAffine(src, cv.invertAffineTransform(M), (61, 45)))
 
 
 @pytest.mark.parametrize("dtype", [np.uint8, np.float32])
@@ -156,7 +165,7 @@ def test_warp_tile_orders(cv, orc, dtype):
     M = cv.getRotationMatrix2D((115.0, 90.0), 11.0, 0.9)
     P = np.array([[1.05, 0.04, -6.0], [0.03, 0.95, 5.0], [1e-4, -1e-4, 1.0]])
     for dsize in [(700, 300), (65, 33), (129, 97), (641, 479), (1000, 40)]:
-        check(cv.warpAffine(dev(src), M, dsize, 1 | cv.WARP_INVERSE_MAP, 1), orc.orc_warpAffine(src, M, dsize, 1, 1))
+        check_bits(cv.warpAffine(dev(src), M, dsize, 1 | cv.WARP_INVERSE_MAP, 1), orc.orc_warpAffine(src, M, dsize, 1, 1))
         check(cv.warpPerspective(dev(src), P, dsize, 1 | cv.WARP_INVERSE_MAP, 0, 3.0), orc.orc_warpPerspective(src, P, dsize, 1, 0, 3.0))
 
 
@@ -173,7 +182,7 @@ def test_warp_32f_wide_sources(cv, orc):
         for border, bval in [(0, 0.0), (0, 2.5), (1, 0), (4, 0)]:
             for M in Ms:
                 got = cv.warpAffine(d, M, dsize, 1 | cv.WARP_INVERSE_MAP, border, bval)
-                check(got, orc.orc_warpAffine(src, M, dsize, 1, border, bval))
+                check_bits(got, orc.orc_warpAffine(src, M, dsize, 1, border, bval))
             for M in P:
                 got = cv.warpPerspective(d, M, dsize, 1 | cv.WARP_INVERSE_MAP, border, bval)
                 check(got, orc.orc_warpPerspective(src, M, dsize, 1, border, bval))
@@ -181,10 +190,10 @@ def test_warp_32f_wide_sources(cv, orc):
     big = rnd((3, 220, 272), np.float32, 99)
     dbig = dev(big)
     view = dbig[1, 8:208, 8:264]
-    check(cv.warpAffine(view, Ms[0], (256, 200), 1 | cv.WARP_INVERSE_MAP, 0, 0.0), orc.orc_warpAffine(np.ascontiguousarray(big[1, 8:208, 8:264]), Ms[0], (256, 200), 1, 0, 0.0))
+    check_bits(cv.warpAffine(view, Ms[0], (256, 200), 1 | cv.WARP_INVERSE_MAP, 0, 0.0), orc.orc_warpAffine(np.ascontiguousarray(big[1, 8:208, 8:264]), Ms[0], (256, 200), 1, 0, 0.0))
     outs = cv.warpAffineBatch(dbig, Ms[1], (272, 220), 1 | cv.WARP_INVERSE_MAP, 1)
     for f in range(3):
-        check(outs[f], orc.orc_warpAffine(big[f], Ms[1], (272, 220), 1, 1))
+        check_bits(outs[f], orc.orc_warpAffine(big[f], Ms[1], (272, 220), 1, 1))
 
 
 @pytest.mark.parametrize("dtype", DT)
@@ -244,7 +253,7 @@ def test_config3_8k_float(cv, orc):
     Minv = cv.invertAffineTransform(M)
     out = cv.warpAffine(d, M, (7680, 4320))
     want3 = orc_band(orc, src, Minv)        # the oracle handles one band of rows fast enough
-    check(out[2000:2200], want3)
+    check_bits(out[2000:2200], want3)
 
 
 def orc_band(orc, src, Minv, y0=2000, y1=2200):
