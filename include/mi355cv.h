@@ -310,6 +310,17 @@ MI355CV_API int mi355cv_pyrdown_offset(const mi355cv_uchar* src_data, size_t src
 MI355CV_API int mi355cv_pyrdownBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int src_width, int src_height,
         mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int dst_width, int dst_height, int nframes,
         int depth, int cn, int border_type);
+/* cv::pyrUp (pyramids.cpp, pyrUp_<CastOp>) has no HAL hook (csrc/pyrup.hip): depth 8U/16U/16S/32F, cn 1..4, dst = (2 * src_width) x (2 * src_height),
+ * border_type BORDER_DEFAULT (the only one the reference accepts; the ISOLATED bit is ignored).  Integer depths bit-identical to the reference.  Everything
+ * else -- CV_64F, the 2w +- 1 / 2h +- 1 sizes the reference also admits, source and destination that overlap in HBM, a source wider than 2^27 pixels or
+ * taller than 2^29 rows (the kernels index a destination row and count destination rows in int) -- is answered MI355CV_NOT_IMPLEMENTED.
+ * Both images in HBM, or both in host memory (staged under the host policy, cost class HOST_CHEAP). */
+MI355CV_API int mi355cv_pyrup(const mi355cv_uchar* src_data, size_t src_step, int src_width, int src_height,
+        mi355cv_uchar* dst_data, size_t dst_step, int dst_width, int dst_height, int depth, int cn, int border_type);
+/* `nframes` frames of one geometry, `*_frame_stride` bytes apart, one launch; all in HBM, or all in host memory (the pipelined path) */
+MI355CV_API int mi355cv_pyrupBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int src_width, int src_height,
+        mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int dst_width, int dst_height, int nframes,
+        int depth, int cn, int border_type);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

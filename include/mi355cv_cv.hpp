@@ -1,5 +1,5 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
-// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, matchTemplate -- and for the map
+// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -160,6 +160,22 @@ inline void buildPyramid(cv::InputArray _src, cv::OutputArrayOfArrays _dst, int 
             return;
     }
     cv::buildPyramid(_src, _dst, maxlevel, borderType);
+}
+
+// cv::pyrUp (imgproc.hpp; pyramids.cpp): the default destination size 2w x 2h on the device; the 2w +- 1 / 2h +- 1 sizes the reference also admits, CV_64F
+// and everything else the library declines go to the stock function.  When the destination is the source's own array, create() gives it a new buffer
+// (the sizes differ) and `src` keeps the old one: both paths below therefore read `src`, not `_src`.
+inline void pyrUp(cv::InputArray _src, cv::OutputArray _dst, const cv::Size& dstsize = cv::Size(), int borderType = cv::BORDER_DEFAULT)
+{
+    cv::Mat src = _src.getMat();
+    const cv::Size dsz = dstsize.empty() ? cv::Size(src.cols * 2, src.rows * 2) : dstsize;
+    if (src.dims <= 2 && !src.empty() && borderType == cv::BORDER_DEFAULT && dsz == cv::Size(src.cols * 2, src.rows * 2) && !_dst.isUMat()) {
+        _dst.create(dsz, src.type());
+        cv::Mat dst = _dst.getMat();
+        if (mi355cv_pyrup(src.data, src.step, src.cols, src.rows, dst.data, dst.step, dst.cols, dst.rows, src.depth(), src.channels(), borderType) == MI355CV_OK)
+            return;
+    }
+    cv::pyrUp(src, _dst, dstsize, borderType);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

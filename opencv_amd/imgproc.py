@@ -26,7 +26,7 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "COLOR_GRAY2RGBA", "COLOR_BGRA2GRAY", "COLOR_RGBA2GRAY",
            "matchTemplate", "matchTemplateBatch", "integral", "integralBatch", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED",
-           "pyrDown", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "pyrDown", "pyrUp", "pyrUpBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1274,6 +1274,34 @@ def pyrDownBatch(frames, borderType=BORDER_DEFAULT, dst=None):
     rc = L.mi355cv_pyrdownBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, d0.w, d0.h, n,
                                 s0.depth, s0.cn, borderType & ~BORDER_ISOLATED)
     _lib.check(rc, "pyrdownBatch")
+    return out
+
+
+def pyrUp(src, dstsize=None, borderType=BORDER_DEFAULT, dst=None):
+    """cv::pyrUp (pyramids.cpp, pyrUp_<CastOp>; no HAL hook) -> mi355cv_pyrup: [H,W(,C)] -> [2H,2W(,C)], 8U / 16U / 16S / 32F, 1..4 channels.
+    dstsize: None, (0, 0) or (2W, 2H); the odd sizes the reference also admits are declined by the library."""
+    if borderType != BORDER_DEFAULT:
+        raise ValueError("pyrUp: only BORDER_DEFAULT is allowed")                 # CV_Assert(borderType == BORDER_DEFAULT)
+    s = Img(src)
+    dw, dh = (2 * s.w, 2 * s.h) if dstsize is None or tuple(dstsize) == (0, 0) else dstsize
+    out = dst if dst is not None else empty_like_kind(src, dh, dw, s.cn, s.depth)
+    d = Img(out)
+    bind_stream(s, d)
+    rc = L.mi355cv_pyrup(_vp(s.ptr), s.step, s.w, s.h, _vp(d.ptr), d.step, d.w, d.h, s.depth, s.cn, borderType)
+    _lib.check(rc, "pyrup")
+    return out
+
+
+def pyrUpBatch(frames, dst=None):
+    """cv::pyrUp over [N,H,W(,C)] frames -> [N,2H,2W(,C)], one launch (host-resident batches: the pipelined path)"""
+    n, s0 = _batch_geom(frames)
+    shape = (n, 2 * s0.h, 2 * s0.w) + tuple(frames.shape[3:])
+    out = _batch_out(frames, dst, shape, frames.dtype)
+    d0 = Img(out[0])
+    bind_stream(s0, d0)
+    rc = L.mi355cv_pyrupBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, d0.w, d0.h, n,
+                              s0.depth, s0.cn, BORDER_DEFAULT)
+    _lib.check(rc, "pyrupBatch")
     return out
 
 
