@@ -321,6 +321,23 @@ MI355CV_API int mi355cv_pyrup(const mi355cv_uchar* src_data, size_t src_step, in
 MI355CV_API int mi355cv_pyrupBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int src_width, int src_height,
         mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int dst_width, int dst_height, int nframes,
         int depth, int cn, int border_type);
+/* cv::distanceTransform (distransform.cpp) has no HAL hook (csrc/disttransform.hip).  src CV_8UC1, a pixel is a site iff it is 0; dst has the source's size.
+ * Served: distance_type DIST_L2 (2) with mask_size DIST_MASK_PRECISE (0) -- the exact integer squared distance to the nearest site, square-rooted and correctly
+ * rounded to float, dst_depth MI355CV_32F; DIST_L1 (1) and DIST_C (3) with mask_size 0, 3 or 5 (one result: the exact city-block / chessboard distance, which is what
+ * the reference's 3 x 3 chamfer pass computes), dst_depth MI355CV_32F, or MI355CV_8U saturated at 255 for DIST_L1.  L2-precise equals the reference wherever its
+ * float32 parabola envelope is exact; where that misrounds (frames a few thousand pixels wide) this returns the mathematically exact value.
+ * A frame WITHOUT ANY SITE has no defined distance: every pixel of it is 31622776.0f (CV_32F) or 255 (CV_8U) and the call returns OK; parity with the reference,
+ * which returns an implementation-specific large number there, is not claimed on such frames.
+ * Answered MI355CV_NOT_IMPLEMENTED with the destination untouched: DIST_L2 with mask_size 3 or 5 (the chamfer approximations, raster-sequential), any other
+ * distance type or mask size, the labelled variant (no entry point), CV_8U output without DIST_L1, other destination depths, source and destination that overlap in
+ * HBM, width or height above mi355cv_limit("disttransform_max_dim") = 16384 (16-bit column distances and 32-bit squared distances in the kernels).
+ * Both images in HBM, or both in host memory (staged under the host policy, cost class HOST_HEAVY). */
+MI355CV_API int mi355cv_distanceTransform(const mi355cv_uchar* src_data, size_t src_step, int width, int height, mi355cv_uchar* dst_data, size_t dst_step,
+        int distance_type, int mask_size, int dst_depth);
+/* `nframes` frames of one geometry, `*_frame_stride` bytes apart; all in HBM, or all in host memory (the pipelined path).  A frame without a site gets the
+ * value above; the other frames of the batch are unaffected. */
+MI355CV_API int mi355cv_distanceTransformBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height,
+        mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int nframes, int distance_type, int mask_size, int dst_depth);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

@@ -1,5 +1,5 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
-// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, matchTemplate -- and for the map
+// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -176,6 +176,23 @@ inline void pyrUp(cv::InputArray _src, cv::OutputArray _dst, const cv::Size& dst
             return;
     }
     cv::pyrUp(src, _dst, dstsize, borderType);
+}
+
+// cv::distanceTransform (imgproc.hpp; distransform.cpp), the unlabelled overload: DIST_L2 with DIST_MASK_PRECISE, DIST_L1 and DIST_C on the device as the exact
+// distance to the nearest zero pixel (mi355cv.h states where that is the reference's own result); DIST_L2 with a 3 x 3 / 5 x 5 mask, the other metrics and
+// everything else the library declines go to the stock function.  A frame without any zero pixel gets the library's own value (31622776.0f / 255), not the
+// reference's.  The source is cloned when the destination is its own array: the device passes cannot run in place.
+inline void distanceTransform(cv::InputArray _src, cv::OutputArray _dst, int distanceType, int maskSize, int dstType = CV_32F)
+{
+    cv::Mat src = _src.getMat();
+    if (src.dims <= 2 && !src.empty() && src.type() == CV_8UC1 && (dstType == CV_32F || (dstType == CV_8U && distanceType == cv::DIST_L1)) && !_dst.isUMat()) {
+        if (_dst.kind() == cv::_InputArray::MAT && _dst.getMat().data == src.data) src = src.clone();
+        _dst.create(src.size(), dstType);
+        cv::Mat dst = _dst.getMat();
+        if (mi355cv_distanceTransform(src.data, src.step, src.cols, src.rows, dst.data, dst.step, distanceType, maskSize, dst.depth()) == MI355CV_OK)
+            return;
+    }
+    cv::distanceTransform(src, _dst, distanceType, maskSize, dstType);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

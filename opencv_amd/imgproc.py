@@ -26,7 +26,8 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "COLOR_GRAY2RGBA", "COLOR_BGRA2GRAY", "COLOR_RGBA2GRAY",
            "matchTemplate", "matchTemplateBatch", "integral", "integralBatch", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED",
-           "pyrDown", "pyrUp", "pyrUpBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "pyrDown", "pyrUp", "pyrUpBatch", "distanceTransform", "distanceTransformBatch", "DIST_L1", "DIST_L2", "DIST_C", "DIST_MASK_3", "DIST_MASK_5",
+           "DIST_MASK_PRECISE", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1302,6 +1303,53 @@ def pyrUpBatch(frames, dst=None):
     rc = L.mi355cv_pyrupBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, d0.w, d0.h, n,
                               s0.depth, s0.cn, BORDER_DEFAULT)
     _lib.check(rc, "pyrupBatch")
+    return out
+
+
+# ----------------------------------------------------------------------------- distance transform (no HAL hook: mi355cv_distanceTransform / ...Batch)
+DIST_L1, DIST_L2, DIST_C = 1, 2, 3                    # cv::DistanceTypes (imgproc.hpp)
+DIST_MASK_3, DIST_MASK_5, DIST_MASK_PRECISE = 3, 5, 0  # cv::DistanceTransformMasks
+
+
+def _dist_args(name, s, distanceType, dstType):
+    if s.depth != CV_8U or s.cn != 1:
+        raise ValueError(name + ": the source must be CV_8UC1")                    # CV_Assert(src.type() == CV_8UC1)
+    if dstType == CV_8U and distanceType != DIST_L1:
+        raise ValueError(name + ": CV_8U output needs DIST_L1")                   # CV_Assert(distType == DIST_L1) on the 8-bit path
+    if dstType not in (CV_8U, CV_32F):
+        raise ValueError(name + ": dstType must be CV_8U or CV_32F")
+
+
+def distanceTransform(src, distanceType, maskSize, dstType=CV_32F, dst=None):
+    """cv::distanceTransform (distransform.cpp; no HAL hook) -> mi355cv_distanceTransform: CV_8UC1 [H,W] -> the distance of every pixel to the nearest zero
+    pixel.  Served: DIST_L2 with DIST_MASK_PRECISE (exact squared distance, correctly rounded root), DIST_L1 and DIST_C with any mask (exact), CV_32F, or CV_8U
+    saturated for DIST_L1.  DIST_L2 with a 3 x 3 / 5 x 5 mask and the other metrics are declined by the library (NotImplementedError).  A frame without any
+    zero pixel gets 31622776.0 (CV_32F) / 255 (CV_8U) in every pixel: the library's own value, not the reference's."""
+    s = Img(src)
+    _dist_args("distanceTransform", s, distanceType, dstType)
+    out = dst if dst is not None else empty_like_kind(src, s.h, s.w, 1, dstType)
+    d = Img(out)
+    if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, 1, dstType):
+        raise ValueError("distanceTransform: dst must have the source's size and the type dstType")
+    bind_stream(s, d)
+    rc = L.mi355cv_distanceTransform(_vp(s.ptr), s.step, s.w, s.h, _vp(d.ptr), d.step, int(distanceType), int(maskSize), dstType)
+    _lib.check(rc, "distanceTransform")
+    return out
+
+
+def distanceTransformBatch(frames, distanceType, maskSize, dstType=CV_32F, dst=None):
+    """cv::distanceTransform over [N,H,W] frames of CV_8UC1 -> [N,H,W] (host-resident batches: the pipelined path); every frame on its own, a frame
+    without a zero pixel gets the value named above and leaves the others as they are"""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("distanceTransformBatch: frames [N, H, W] of one channel")
+    _dist_args("distanceTransformBatch", s0, distanceType, dstType)
+    out = _batch_out(frames, dst, tuple(frames.shape), _DEPTH_T[dstType])
+    d0 = Img(out[0])
+    bind_stream(s0, d0)
+    rc = L.mi355cv_distanceTransformBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, n,
+                                          int(distanceType), int(maskSize), dstType)
+    _lib.check(rc, "distanceTransformBatch")
     return out
 
 
