@@ -338,6 +338,40 @@ MI355CV_API int mi355cv_distanceTransform(const mi355cv_uchar* src_data, size_t 
  * value above; the other frames of the batch are unaffected. */
 MI355CV_API int mi355cv_distanceTransformBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height,
         mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int nframes, int distance_type, int mask_size, int dst_depth);
+/* cv::connectedComponents / cv::connectedComponentsWithStats (connectedcomponents.cpp) have no HAL hook (csrc/ccl.hip).  src CV_8UC1, a pixel is foreground iff
+ * it is non-zero; connectivity 4 or 8; ltype MI355CV_32S or MI355CV_16U; labels has the source's size.  Labels run 0 .. N - 1 with 0 for the background, and
+ * *nlabels = N is written to HOST memory (the call's one host synchronisation); N counts the background even when no pixel is background.  Every result is a pure
+ * function of the input: the union-find keeps the smallest pixel index as the root, so nothing depends on the order in which merges land.
+ * Numbering follows one of two orders.  PIXEL ORDER: components are numbered 1, 2, ... by the raster position of their first pixel (the smallest y * w + x) --
+ * every ccltype with connectivity 4, and CCL_WU (0) / CCL_SAUF (3) with connectivity 8.  BLOCK ORDER: by the raster position of their first 2 x 2 block (the
+ * smallest (y >> 1) * ceil(w / 2) + (x >> 1); two foreground pixels of one block are 8-connected, so the key is unique) -- connectivity 8 with CCL_DEFAULT (-1),
+ * CCL_GRANA (1) / CCL_BBDT (4) and CCL_BOLELLI (2) / CCL_SPAGHETTI (5).  Both orders follow from where the reference's labellers create provisional labels: SAUF at
+ * a component's first raster pixel, with set_union keeping the smaller root and flattenL renumbering roots in increasing order; the block-based ones per 2 x 2
+ * block in raster order of blocks.  The reference was not available to pin either order; the tests hold them against a restatement and scipy.ndimage.label.
+ * Answered MI355CV_NOT_IMPLEMENTED with every destination untouched: another ltype, connectivity other than 4 or 8, ccltype outside -1 .. 5, null pointers,
+ * width or height <= 0 or above mi355cv_limit("ccl_max_dim") = 16384 (32-bit pixel indices and areas, coordinate sums below 2^53), source and labels that overlap
+ * in HBM, and MI355CV_16U labels when N - 1 > 65535 (the reference's label type would wrap; labelling runs in 32-bit scratch and the decision is taken before the
+ * destination is written).  Both images in HBM, or both in host memory (staged under the host policy, cost class HOST_HEAVY). */
+MI355CV_API int mi355cv_connectedComponents(const mi355cv_uchar* src_data, size_t src_step, int width, int height, mi355cv_uchar* labels_data, size_t labels_step,
+        int connectivity, int ltype, int ccltype, int* nlabels);
+/* `nframes` frames of one geometry, `*_frame_stride` bytes apart; all in HBM, or all in host memory (the pipelined path).  nlabels: `nframes` ints in HOST memory,
+ * one copy for all frames.  With MI355CV_16U one frame with more than 65535 components declines the whole call (at most 65535 frames then); in the pipelined host
+ * path the chunks of frames already copied back stay written. */
+MI355CV_API int mi355cv_connectedComponentsBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height,
+        mi355cv_uchar* labels_data, size_t labels_step, size_t labels_frame_stride, int nframes, int connectivity, int ltype, int ccltype, int* nlabels);
+/* The statistics of a finished label image (ltype MI355CV_32S or MI355CV_16U): stats is nlabels rows of five CV_32S, CC_STAT_LEFT, TOP, WIDTH, HEIGHT, AREA = 0 .. 4,
+ * row 0 the background's; centroids (may be null) is nlabels rows of two CV_64F, double(sum of x) / double(area) and double(sum of y) / double(area), the sums exact
+ * 64-bit integers and the division the correctly rounded IEEE one.  A label without a pixel (label 0 of a frame without background) gets the library's own value:
+ * the five stats 0 and the centroid (NaN, NaN); the call returns OK and parity with the reference is not claimed for that row.  A value >= nlabels in the label
+ * image is skipped and never indexed.  The outputs live where the label image lives: all three on the device, or all on the host (staged).  Declined: null labels or
+ * stats, another ltype, nlabels < 1, the size bounds above, outputs and labels that overlap in HBM. */
+MI355CV_API int mi355cv_connectedComponentsStats(const mi355cv_uchar* labels_data, size_t labels_step, int width, int height, int ltype, int nlabels,
+        int* stats, size_t stats_step, double* centroids, size_t centroids_step);
+/* Device-resident frames only (host-resident ones are declined).  nlabels: `nframes` ints in HOST memory; frame f's rows from nlabels[f] up to max_labels are
+ * zero-filled; any nlabels[f] > max_labels, or nframes > 65535, is declined. */
+MI355CV_API int mi355cv_connectedComponentsStatsBatch(const mi355cv_uchar* labels_data, size_t labels_step, size_t labels_frame_stride, int width, int height, int ltype,
+        int nframes, const int* nlabels, int max_labels, int* stats, size_t stats_step, size_t stats_frame_stride,
+        double* centroids, size_t centroids_step, size_t centroids_frame_stride);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

@@ -1,5 +1,6 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
-// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, matchTemplate -- and for the map
+// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, connectedComponents,
+// connectedComponentsWithStats, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -193,6 +194,56 @@ inline void distanceTransform(cv::InputArray _src, cv::OutputArray _dst, int dis
             return;
     }
     cv::distanceTransform(src, _dst, distanceType, maskSize, dstType);
+}
+
+// cv::connectedComponents / cv::connectedComponentsWithStats (imgproc.hpp; connectedcomponents.cpp), both overloads of each: the one without ccltype means
+// CCL_DEFAULT.  CV_8UC1, connectivity 4 or 8, ltype CV_32S or CV_16U on the device (mi355cv.h states the numbering: by first pixel for connectivity 4 and for
+// CCL_WU / CCL_SAUF, by first 2 x 2 block otherwise); everything the library declines -- CV_16U labels with more than 65535 components among it -- goes to the
+// stock function.  A frame without background gets the library's own statistics row 0 (zeros, NaN centroid).  The source is cloned when the labels are its own
+// array.  Like mi355cv::pyrUp, these wrappers have not yet been compiled against the reference's headers.
+inline int connectedComponents(cv::InputArray _image, cv::OutputArray _labels, int connectivity, int ltype, int ccltype)
+{
+    cv::Mat image = _image.getMat();
+    if (image.dims <= 2 && !image.empty() && image.type() == CV_8UC1 && (ltype == CV_32S || ltype == CV_16U) && !_labels.isUMat()) {
+        if (_labels.kind() == cv::_InputArray::MAT && _labels.getMat().data == image.data) image = image.clone();
+        _labels.create(image.size(), ltype);
+        cv::Mat labels = _labels.getMat();
+        int n = 0;
+        if (mi355cv_connectedComponents(image.data, image.step, image.cols, image.rows, labels.data, labels.step, connectivity, ltype, ccltype, &n) == MI355CV_OK)
+            return n;
+    }
+    return cv::connectedComponents(image, _labels, connectivity, ltype, ccltype);
+}
+inline int connectedComponents(cv::InputArray image, cv::OutputArray labels, int connectivity = 8, int ltype = CV_32S)
+{
+    return mi355cv::connectedComponents(image, labels, connectivity, ltype, cv::CCL_DEFAULT);
+}
+
+inline int connectedComponentsWithStats(cv::InputArray _image, cv::OutputArray _labels, cv::OutputArray _stats, cv::OutputArray _centroids, int connectivity, int ltype,
+                                        int ccltype)
+{
+    cv::Mat image = _image.getMat();
+    if (image.dims <= 2 && !image.empty() && image.type() == CV_8UC1 && (ltype == CV_32S || ltype == CV_16U) && !_labels.isUMat() && !_stats.isUMat() &&
+        !_centroids.isUMat()) {
+        if (_labels.kind() == cv::_InputArray::MAT && _labels.getMat().data == image.data) image = image.clone();
+        _labels.create(image.size(), ltype);
+        cv::Mat labels = _labels.getMat();
+        int n = 0;
+        if (mi355cv_connectedComponents(image.data, image.step, image.cols, image.rows, labels.data, labels.step, connectivity, ltype, ccltype, &n) == MI355CV_OK) {
+            _stats.create(n, cv::CC_STAT_MAX, CV_32S);
+            _centroids.create(n, 2, CV_64F);
+            cv::Mat stats = _stats.getMat(), centroids = _centroids.getMat();
+            if (mi355cv_connectedComponentsStats(labels.data, labels.step, labels.cols, labels.rows, ltype, n, stats.ptr<int>(), stats.step, centroids.ptr<double>(),
+                                                 centroids.step) == MI355CV_OK)
+                return n;
+        }
+    }
+    return cv::connectedComponentsWithStats(image, _labels, _stats, _centroids, connectivity, ltype, ccltype);
+}
+inline int connectedComponentsWithStats(cv::InputArray image, cv::OutputArray labels, cv::OutputArray stats, cv::OutputArray centroids, int connectivity = 8,
+                                        int ltype = CV_32S)
+{
+    return mi355cv::connectedComponentsWithStats(image, labels, stats, centroids, connectivity, ltype, cv::CCL_DEFAULT);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

@@ -168,6 +168,11 @@ def _load():
         "mi355cv_pyrupBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_distanceTransform": (c_int, [c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, c_int]),
         "mi355cv_distanceTransformBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int]),
+        "mi355cv_connectedComponents": (c_int, [c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+        "mi355cv_connectedComponentsBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int)]),
+        "mi355cv_connectedComponentsStats": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_sz, ctypes.c_void_p, c_sz]),
+        "mi355cv_connectedComponentsStatsBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, ctypes.c_void_p, c_sz, c_sz,
+                                                          ctypes.c_void_p, c_sz, c_sz]),
         "mi355cv_buildPyramid": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_sz), c_int, c_int]),
         "mi355cv_cornerHarris": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int]),
         "mi355cv_cornerMinEigenVal": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),

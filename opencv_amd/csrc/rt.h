@@ -33,6 +33,7 @@ constexpr int BILATERAL_MAX_RADIUS = 16;
 constexpr int ORB_MAX_LEVELS = 32;
 constexpr int FILTER2D_DFT_TAPS = 130;     // whole-image filter2D from this many taps on is the reference's DFT case: declined unless MI355CV_FILTER_LARGE=1
 constexpr int DISTTRANSFORM_MAX_DIM = 16384; // mi355cv_distanceTransform: width and height (16-bit column distances, 32-bit squared distances; disttransform_math.h)
+constexpr int CCL_MAX_DIM = 16384;         // mi355cv_connectedComponents*: width and height (32-bit pixel indices and areas, coordinate sums below 2^53; ccl_math.h)
 }
 
 struct ThreadCtx;

@@ -8,7 +8,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .core import (Img, empty_like_kind, bind_stream, torch, CV_8U, CV_16U, CV_16S, CV_32F, CV_64F, _DEPTH_T,  # noqa: F401
+from .core import (Img, empty_like_kind, bind_stream, torch, CV_8U, CV_16U, CV_16S, CV_32S, CV_32F, CV_64F, _DEPTH_T,  # noqa: F401
                    BORDER_CONSTANT, BORDER_ISOLATED, BORDER_DEFAULT, BORDER_REFLECT_101)
 
 L = _lib.lib
@@ -27,7 +27,9 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "matchTemplate", "matchTemplateBatch", "integral", "integralBatch", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED",
            "pyrDown", "pyrUp", "pyrUpBatch", "distanceTransform", "distanceTransformBatch", "DIST_L1", "DIST_L2", "DIST_C", "DIST_MASK_3", "DIST_MASK_5",
-           "DIST_MASK_PRECISE", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
+           "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
+           "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1351,6 +1353,92 @@ def distanceTransformBatch(frames, distanceType, maskSize, dstType=CV_32F, dst=N
                                           int(distanceType), int(maskSize), dstType)
     _lib.check(rc, "distanceTransformBatch")
     return out
+
+
+# ----------------------------------------------------------------------------- connected components (no HAL hook: mi355cv_connectedComponents* / ...Stats*)
+CC_STAT_LEFT, CC_STAT_TOP, CC_STAT_WIDTH, CC_STAT_HEIGHT, CC_STAT_AREA, CC_STAT_MAX = range(6)           # cv::ConnectedComponentsTypes
+CCL_DEFAULT, CCL_WU, CCL_GRANA, CCL_BOLELLI, CCL_SAUF, CCL_BBDT, CCL_SPAGHETTI = -1, 0, 1, 2, 3, 4, 5    # cv::ConnectedComponentsAlgorithmsTypes
+
+
+def _ccl_args(name, s, connectivity, ltype):
+    if s.depth != CV_8U or s.cn != 1 or getattr(s.obj, "ndim", 2) != 2:
+        raise ValueError(name + ": the source must be a 2-D CV_8UC1 image")         # CV_Assert(img.type() == CV_8UC1)
+    if connectivity not in (4, 8):
+        raise ValueError(name + ": connectivity must be 4 or 8")
+    if ltype not in (CV_32S, CV_16U):
+        raise ValueError(name + ": ltype must be CV_32S or CV_16U")
+
+
+def connectedComponents(image, labels=None, connectivity=8, ltype=CV_32S, ccltype=CCL_DEFAULT):
+    """cv::connectedComponents (connectedcomponents.cpp; no HAL hook) -> mi355cv_connectedComponents: CV_8UC1 [H,W] -> (N, labels).  Labels 0 .. N - 1, 0 the
+    background; components numbered by their first raster pixel (connectivity 4, CCL_WU, CCL_SAUF) or by their first 2 x 2 block (connectivity 8 with the
+    other ccltypes), see mi355cv.h.  CV_16U labels with more than 65535 components are declined (NotImplementedError)."""
+    s = Img(image)
+    _ccl_args("connectedComponents", s, connectivity, ltype)
+    out = labels if labels is not None else empty_like_kind(image, s.h, s.w, 1, ltype)
+    d = Img(out)
+    if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, 1, ltype) or d.device != s.device:
+        raise ValueError("connectedComponents: labels must have the source's size, the type ltype and live where the source lives")
+    bind_stream(s, d)
+    n = ctypes.c_int(0)
+    rc = L.mi355cv_connectedComponents(_vp(s.ptr), s.step, s.w, s.h, _vp(d.ptr), d.step, int(connectivity), int(ltype), int(ccltype), ctypes.byref(n))
+    _lib.check(rc, "connectedComponents")
+    return n.value, out
+
+
+def _ccl_stats_out(ref, shape, dtype_t, dtype_np):
+    if torch is not None and isinstance(ref, torch.Tensor):
+        return torch.empty(shape, dtype=dtype_t, device=ref.device)
+    return np.empty(shape, dtype=dtype_np)
+
+
+def connectedComponentsWithStats(image, labels=None, stats=None, centroids=None, connectivity=8, ltype=CV_32S, ccltype=CCL_DEFAULT):
+    """cv::connectedComponentsWithStats -> (N, labels, stats int32 [N,5], centroids float64 [N,2]): the labelling call, then mi355cv_connectedComponentsStats over
+    the finished labels.  A frame without background has stats row 0 all zero and centroid (nan, nan)."""
+    n, out = connectedComponents(image, labels, connectivity, ltype, ccltype)
+    if stats is None:
+        stats = _ccl_stats_out(out, (n, 5), torch.int32 if torch is not None else None, np.int32)
+    if centroids is None:
+        centroids = _ccl_stats_out(out, (n, 2), torch.float64 if torch is not None else None, np.float64)
+    l, st, ce = Img(out), Img(stats), Img(centroids)
+    if (st.h, st.w, st.cn, st.depth) != (n, 5, 1, CV_32S) or (ce.h, ce.w, ce.cn, ce.depth) != (n, 2, 1, CV_64F) or st.device != l.device or ce.device != l.device:
+        raise ValueError("connectedComponentsWithStats: stats must be int32 [N,5] and centroids float64 [N,2], where the labels live")
+    bind_stream(l, st)
+    rc = L.mi355cv_connectedComponentsStats(_vp(l.ptr), l.step, l.w, l.h, int(ltype), n, _vp(st.ptr), st.step, _vp(ce.ptr), ce.step)
+    _lib.check(rc, "connectedComponentsStats")
+    return n, out, stats, centroids
+
+
+def connectedComponentsBatch(frames, labels=None, connectivity=8, ltype=CV_32S, ccltype=CCL_DEFAULT):
+    """cv::connectedComponents over [N,H,W] frames of CV_8UC1 -> (nlabels: list of N ints, labels [N,H,W]); host-resident batches take the pipelined path"""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("connectedComponentsBatch: frames [N, H, W] of one channel")
+    _ccl_args("connectedComponentsBatch", s0, connectivity, ltype)
+    out = _batch_out(frames, labels, tuple(frames.shape), _DEPTH_T[ltype])
+    d0 = Img(out[0])
+    bind_stream(s0, d0)
+    counts = (ctypes.c_int * n)()
+    rc = L.mi355cv_connectedComponentsBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, n,
+                                            int(connectivity), int(ltype), int(ccltype), counts)
+    _lib.check(rc, "connectedComponentsBatch")
+    return list(counts), out
+
+
+def connectedComponentsWithStatsBatch(frames, labels=None, connectivity=8, ltype=CV_32S, ccltype=CCL_DEFAULT):
+    """-> (nlabels, labels [N,H,W], stats int32 [N,maxN,5], centroids float64 [N,maxN,2]) with maxN = max(nlabels); frame f's rows from nlabels[f] on are zero.
+    Device-resident frames only: the library declines the statistics of a host-resident batch."""
+    counts, out = connectedComponentsBatch(frames, labels, connectivity, ltype, ccltype)
+    n, mx = len(counts), max(counts)
+    stats = torch.empty((n, mx, 5), dtype=torch.int32, device=out.device)
+    cent = torch.empty((n, mx, 2), dtype=torch.float64, device=out.device)
+    l0 = Img(out[0])
+    bind_stream(l0)
+    arr = (ctypes.c_int * n)(*counts)
+    rc = L.mi355cv_connectedComponentsStatsBatch(_vp(l0.ptr), l0.step, int(out.stride(0)) * l0.esz, l0.w, l0.h, int(ltype), n, arr, mx,
+                                                 _vp(stats.data_ptr()), 20, mx * 20, _vp(cent.data_ptr()), 16, mx * 16)
+    _lib.check(rc, "connectedComponentsStatsBatch")
+    return counts, out, stats, cent
 
 
 def buildPyramid(src, maxlevel, borderType=BORDER_DEFAULT):
