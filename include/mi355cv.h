@@ -372,6 +372,40 @@ MI355CV_API int mi355cv_connectedComponentsStats(const mi355cv_uchar* labels_dat
 MI355CV_API int mi355cv_connectedComponentsStatsBatch(const mi355cv_uchar* labels_data, size_t labels_step, size_t labels_frame_stride, int width, int height, int ltype,
         int nframes, const int* nlabels, int max_labels, int* stats, size_t stats_step, size_t stats_frame_stride,
         double* centroids, size_t centroids_step, size_t centroids_frame_stride);
+/* cv::HoughLines / cv::HoughLinesWithAccumulator, the standard transform (HoughLinesStandard, hough.cpp), have no HAL hook (csrc/hough.hip).  src CV_8UC1, a
+ * pixel votes iff it is non-zero.  rho and theta arrive as doubles and are used as float; "float" below is IEEE binary32 with every operation rounded on its own
+ * (no fused multiply-add), cvRound is round-half-to-even.
+ *   geometry  numangle = floor((max_theta - min_theta) / theta) + 1 in double, one fewer when numangle > 1 and |CV_PI - (numangle - 1) theta| < theta / 2;
+ *             numrho = cvRound(float(2 (width + height) + 1) / rho_f); irho = 1.f / rho_f.
+ *   table     ang = (float)min_theta; tabSin[n] = (float)(sin((double)ang) * irho), tabCos[n] likewise (libm on the host, the product in double); ang += theta_f.
+ *   votes     every non-zero pixel (x, y) and every n: r = cvRound(x * tabCos[n] + y * tabSin[n]) + (numrho - 1) / 2, cell (n + 1)(numrho + 2) + r + 1 of the
+ *             (numangle + 2) x (numrho + 2) CV_32S accumulator gains 1.
+ *   maxima    inner cell b is one iff a[b] > threshold, a[b] > a[b - 1], a[b] >= a[b + 1], a[b] > a[b - numrho - 2], a[b] >= a[b + numrho + 2].
+ *   order     votes descending, equal votes by b ascending.
+ *   lines     rho = (r - (numrho - 1) * 0.5f) * rho_f, theta = (float)min_theta + n * theta_f; lines_cn = 2 floats per line, or 3 with (float)votes.
+ * The accumulator is integer and the order is total, so every result is a pure function of the input.  The reference was not available to pin these steps; the
+ * tests hold the kernels bit for bit against two independent Python restatements of them (tests/hough_restate.py).
+ * lines: max_lines rows of lines_cn floats, dense.  *nlines (HOST memory; reading it back is the call's one host synchronisation) receives the TOTAL number of
+ * maxima; only the first min(*nlines, max_lines) rows are written, rows past the count never are.
+ * Answered MI355CV_NOT_IMPLEMENTED with every destination untouched: srn != 0 or stn != 0 (the multi-scale variant), rho <= 0 or theta <= 0, angles outside
+ * 0 <= min_theta < max_theta <= CV_PI, null pointers, lines_cn other than 2 or 3, max_lines < 1, width or height <= 0 or above mi355cv_limit("hough_max_dim") =
+ * 16384 (a packed point (y << 16 | x) needs both <= 65535; 16384 is the bound of the neighbouring entries and keeps a frame's point list within 1 GiB and every
+ * count below 2^28), an accumulator above mi355cv_limit("hough_max_accum") = 2^26 cells (256 MiB per frame; a cell index is the low word of the sort key), more than 65535 angles, and
+ * lines that overlap the source in HBM.  Image and lines both in HBM, or both in host memory (staged under the host policy, cost class HOST_HEAVY; the lines then
+ * come back in a second copy after the counts).  cv::HoughLinesP, cv::HoughCircles and cv::HoughLinesPointSet have no entry. */
+MI355CV_API int mi355cv_houghLines(const mi355cv_uchar* src_data, size_t src_step, int width, int height, float* lines, int lines_cn, int max_lines,
+        double rho, double theta, int threshold, double srn, double stn, double min_theta, double max_theta, int* nlines);
+/* `nframes` frames of one geometry, `src_frame_stride` / `lines_frame_stride` bytes apart (the latter a multiple of 4 and at least max_lines rows); all in HBM,
+ * or all in host memory.  One enqueue for all frames; nlines: `nframes` ints in HOST memory.  A frame without an edge pixel yields 0 lines and does not affect the
+ * others.  At most 65535 frames. */
+MI355CV_API int mi355cv_houghLinesBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, float* lines, int lines_cn,
+        int max_lines, size_t lines_frame_stride, int nframes, double rho, double theta, int threshold, double srn, double stn, double min_theta, double max_theta,
+        int* nlines);
+/* The geometry, and the accumulator itself: *numangle and *numrho (HOST memory) always; with accum != NULL the full (numangle + 2) x (numrho + 2) CV_32S
+ * accumulator of the frame, rows accum_step bytes apart (a multiple of 4, at least numrho + 2 ints), where the image lives.  With accum == NULL no device is
+ * touched and src is only tested for NULL.  The same refusals as mi355cv_houghLines. */
+MI355CV_API int mi355cv_houghLinesAccum(const mi355cv_uchar* src_data, size_t src_step, int width, int height, double rho, double theta, double min_theta,
+        double max_theta, int* accum, size_t accum_step, int* numangle, int* numrho);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

@@ -1,6 +1,6 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
 // (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, connectedComponents,
-// connectedComponentsWithStats, matchTemplate -- and for the map
+// connectedComponentsWithStats, HoughLines, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -244,6 +244,33 @@ inline int connectedComponentsWithStats(cv::InputArray image, cv::OutputArray la
                                         int ltype = CV_32S)
 {
     return mi355cv::connectedComponentsWithStats(image, labels, stats, centroids, connectivity, ltype, cv::CCL_DEFAULT);
+}
+
+// cv::HoughLines (imgproc.hpp; hough.cpp HoughLinesStandard): the standard transform of a CV_8UC1 edge image on the device, Vec2f (rho, theta) or -- when `lines`
+// is a Vec3f array, cv::HoughLinesWithAccumulator's form -- Vec3f (rho, theta, votes), ordered by votes.  A first call with room for 4096 lines; when the library
+// reports more maxima, one more call with that capacity.  Everything the library declines (srn or stn != 0, the multi-scale variant, among it) goes to the stock
+// function.  Like mi355cv::pyrUp, this wrapper has not yet been compiled against the reference's headers.
+inline void HoughLines(cv::InputArray _image, cv::OutputArray _lines, double rho, double theta, int threshold, double srn = 0, double stn = 0, double min_theta = 0,
+                       double max_theta = CV_PI)
+{
+    cv::Mat image = _image.getMat();
+    const int type = _lines.fixedType() && _lines.type() == CV_32FC3 ? CV_32FC3 : CV_32FC2, cn = CV_MAT_CN(type);
+    if (image.dims <= 2 && !image.empty() && image.type() == CV_8UC1 && !_lines.isUMat()) {
+        int cap = 4096, n = 0;
+        for (int pass = 0; pass < 2; pass++) {
+            std::vector<float> buf((size_t)cap * cn);
+            if (mi355cv_houghLines(image.data, image.step, image.cols, image.rows, buf.data(), cn, cap, rho, theta, threshold, srn, stn, min_theta, max_theta, &n) != MI355CV_OK)
+                break;
+            if (n <= cap) {
+                if (n == 0) { _lines.release(); return; }
+                cv::Mat(n, 1, type, buf.data()).copyTo(_lines);
+                return;
+            }
+            cap = n;
+        }
+    }
+    if (type == CV_32FC3) cv::HoughLinesWithAccumulator(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
+    else cv::HoughLines(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

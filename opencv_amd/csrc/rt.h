@@ -34,6 +34,8 @@ constexpr int ORB_MAX_LEVELS = 32;
 constexpr int FILTER2D_DFT_TAPS = 130;     // whole-image filter2D from this many taps on is the reference's DFT case: declined unless MI355CV_FILTER_LARGE=1
 constexpr int DISTTRANSFORM_MAX_DIM = 16384; // mi355cv_distanceTransform: width and height (16-bit column distances, 32-bit squared distances; disttransform_math.h)
 constexpr int CCL_MAX_DIM = 16384;         // mi355cv_connectedComponents*: width and height (32-bit pixel indices and areas, coordinate sums below 2^53; ccl_math.h)
+constexpr int HOUGH_MAX_DIM = 16384;       // mi355cv_houghLines*: width and height (packed 16-bit point coordinates, counts below 2^28; hough_math.h)
+constexpr int HOUGH_MAX_ACCUM = 1 << 26;   // ... and the cells of the accumulator, (numangle + 2) x (numrho + 2): a cell index is the low word of the sort key
 }
 
 struct ThreadCtx;

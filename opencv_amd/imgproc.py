@@ -5,6 +5,7 @@ after (file:line cited) and then calls the matching cv_hal_* replacement in
 libmi355cv.so.  No pixels are computed here.
 """
 import ctypes
+import math
 import numpy as np
 
 from . import _lib
@@ -29,7 +30,8 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "pyrDown", "pyrUp", "pyrUpBatch", "distanceTransform", "distanceTransformBatch", "DIST_L1", "DIST_L2", "DIST_C", "DIST_MASK_3", "DIST_MASK_5",
            "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
            "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
-           "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI",
+           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1439,6 +1441,96 @@ def connectedComponentsWithStatsBatch(frames, labels=None, connectivity=8, ltype
                                                  _vp(stats.data_ptr()), 20, mx * 20, _vp(cent.data_ptr()), 16, mx * 16)
     _lib.check(rc, "connectedComponentsStatsBatch")
     return counts, out, stats, cent
+
+
+# ----------------------------------------------------------------------------- standard Hough transform (no HAL hook: mi355cv_houghLines* )
+_HOUGH_MAX_LINES = 4096                      # the capacity of the first call; a frame with more maxima gets a second call with the reported count
+
+
+def _hough_args(name, s, rho, theta, srn, stn, min_theta, max_theta, maxLines):
+    if s.depth != CV_8U or s.cn != 1 or getattr(s.obj, "ndim", 2) != 2:
+        raise ValueError(name + ": the image must be a 2-D CV_8UC1 image")            # CV_Assert(img.type() == CV_8UC1)
+    if not rho > 0 or not theta > 0:
+        raise ValueError(name + ": rho and theta must be positive")
+    if srn < 0 or stn < 0:
+        raise ValueError(name + ": srn and stn must not be negative")
+    if not 0 <= min_theta < max_theta <= math.pi:
+        raise ValueError(name + ": 0 <= min_theta < max_theta <= pi is required")
+    if maxLines is not None and int(maxLines) < 1:
+        raise ValueError(name + ": maxLines must be at least 1")
+
+
+def _hough_alloc(ref, shape):
+    if torch is not None and isinstance(ref, torch.Tensor):
+        return torch.empty(shape, dtype=torch.float32, device=ref.device, pin_memory=(not ref.is_cuda) and ref.is_pinned())
+    return np.empty(shape, dtype=np.float32)
+
+
+def _hough(name, image, cn, rho, theta, threshold, srn, stn, min_theta, max_theta, maxLines):
+    s = Img(image)
+    _hough_args(name, s, rho, theta, srn, stn, min_theta, max_theta, maxLines)
+    cap = int(maxLines) if maxLines is not None else _HOUGH_MAX_LINES
+    n = ctypes.c_int(0)
+    for _ in range(2):
+        out = _hough_alloc(image, (cap, cn))
+        ptr = out.data_ptr() if torch is not None and isinstance(out, torch.Tensor) else out.ctypes.data
+        bind_stream(s)
+        rc = L.mi355cv_houghLines(_vp(s.ptr), s.step, s.w, s.h, _vp(ptr), cn, cap, float(rho), float(theta), int(threshold), float(srn), float(stn),
+                                  float(min_theta), float(max_theta), ctypes.byref(n))
+        _lib.check(rc, "houghLines")
+        if n.value <= cap or maxLines is not None:
+            break
+        cap = n.value                                                                 # more maxima than the first capacity: once more with that capacity
+    return out[:min(n.value, cap)]
+
+
+def HoughLines(image, rho, theta, threshold, srn=0, stn=0, min_theta=0, max_theta=math.pi, maxLines=None):
+    """cv::HoughLines, the standard transform (hough.cpp HoughLinesStandard; no HAL hook) -> mi355cv_houghLines: CV_8UC1 [H,W] -> float32 [N,2] of (rho, theta),
+    ordered by votes (ties by accumulator index), where the image lives.  maxLines caps N (the strongest lines are kept); without it every maximum is returned.
+    srn / stn != 0 (the multi-scale variant) is declined (NotImplementedError)."""
+    return _hough("HoughLines", image, 2, rho, theta, threshold, srn, stn, min_theta, max_theta, maxLines)
+
+
+def HoughLinesWithAccumulator(image, rho, theta, threshold, srn=0, stn=0, min_theta=0, max_theta=math.pi, maxLines=None):
+    """cv::HoughLinesWithAccumulator -> float32 [N,3] of (rho, theta, votes)"""
+    return _hough("HoughLinesWithAccumulator", image, 3, rho, theta, threshold, srn, stn, min_theta, max_theta, maxLines)
+
+
+def HoughLinesBatch(frames, rho, theta, threshold, srn=0, stn=0, min_theta=0, max_theta=math.pi, maxLines=_HOUGH_MAX_LINES, withAccumulator=False):
+    """cv::HoughLines over [N,H,W] frames of CV_8UC1, one enqueue -> (counts: list of N ints, lines float32 [N,maxLines,cn]); counts[f] is the number of maxima of
+    frame f, of which the first min(counts[f], maxLines) rows of lines[f] are written (the rest is left as allocated)."""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("HoughLinesBatch: frames [N, H, W] of one channel")
+    _hough_args("HoughLinesBatch", s0, rho, theta, srn, stn, min_theta, max_theta, maxLines)
+    cn, cap = (3 if withAccumulator else 2), int(maxLines)
+    out = _batch_alloc(frames, (n, cap, cn), torch.float32)
+    bind_stream(s0)
+    counts = (ctypes.c_int * n)()
+    rc = L.mi355cv_houghLinesBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(out.data_ptr()), cn, cap, cap * cn * 4, n, float(rho), float(theta),
+                                   int(threshold), float(srn), float(stn), float(min_theta), float(max_theta), counts)
+    _lib.check(rc, "houghLinesBatch")
+    return list(counts), out
+
+
+def HoughLinesAccumulator(image, rho, theta, min_theta=0, max_theta=math.pi):
+    """the vote accumulator HoughLines takes its maxima from -> int32 [numangle + 2, numrho + 2] where the image lives (mi355cv_houghLinesAccum); row n + 1,
+    column r + 1 holds the votes of angle n and distance bin r"""
+    s = Img(image)
+    _hough_args("HoughLinesAccumulator", s, rho, theta, 0, 0, min_theta, max_theta, None)
+    na, nr = ctypes.c_int(0), ctypes.c_int(0)
+    args = (_vp(s.ptr), s.step, s.w, s.h, float(rho), float(theta), float(min_theta), float(max_theta))
+    _lib.check(L.mi355cv_houghLinesAccum(*args, None, 0, ctypes.byref(na), ctypes.byref(nr)), "houghLinesAccum")
+    shape = (na.value + 2, nr.value + 2)
+    if torch is not None and isinstance(image, torch.Tensor):
+        out = torch.empty(shape, dtype=torch.int32, device=image.device)
+        ptr = out.data_ptr()
+    else:
+        out = np.empty(shape, dtype=np.int32)
+        ptr = out.ctypes.data
+    bind_stream(s)
+    _lib.check(L.mi355cv_houghLinesAccum(*args, _vp(ptr), shape[1] * 4, ctypes.byref(na), ctypes.byref(nr)), "houghLinesAccum")
+    return out
 
 
 def buildPyramid(src, maxlevel, borderType=BORDER_DEFAULT):
