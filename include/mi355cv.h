@@ -406,6 +406,27 @@ MI355CV_API int mi355cv_houghLinesBatch(const mi355cv_uchar* src_data, size_t sr
  * touched and src is only tested for NULL.  The same refusals as mi355cv_houghLines. */
 MI355CV_API int mi355cv_houghLinesAccum(const mi355cv_uchar* src_data, size_t src_step, int width, int height, double rho, double theta, double min_theta,
         double max_theta, int* accum, size_t accum_step, int* numangle, int* numrho);
+/* cv::minMaxLoc (csrc/minmax.hip).  src: one channel of CV_8U, CV_8S, CV_16U, CV_16S, CV_32S, CV_32F or CV_64F (depth 0 .. 6), its base aligned to the element
+ * only (a ROI that starts at an odd column is served).  mask: NULL, or CV_8UC1 of the same size with its own pitch; non-zero selects a pixel.
+ *   candidates   the selected pixels whose value is not NaN.
+ *   vals[0]      the least candidate value, vals[1] the greatest, as (double)element; -0.0 and +0.0 compare equal and the sign of a returned zero is unspecified;
+ *                +-inf are ordinary values.
+ *   locs         {minX, minY, maxX, maxY}: for both, the FIRST pixel in raster order (y, then x) that holds the value.
+ *   empty set    (mask all zero, every pixel NaN, or both) vals = {0, 0}, locs = {-1, -1, -1, -1}.
+ * The reference was not available to pin the treatment of NaN, of infinities and of the empty set: it is this restatement's (tests/minmax_restate.py), and the
+ * kernels are held against it bit for bit.  No core-HAL binding (cv_hal_minMaxIdx) is made: its parameter list could not be checked.
+ * src and mask both in HBM, or both in host memory (staged under the host policy, cost class HOST_CHEAP).  vals (2 doubles) and locs (4 ints) both in HBM -- the
+ * last kernel writes them and the call adds no host synchronisation of its own -- or both in host memory, which costs the call's one read-back.
+ * Answered MI355CV_NOT_IMPLEMENTED with vals and locs untouched: null src, vals or locs; a depth outside the seven; width or height <= 0 or above
+ * mi355cv_limit("minmax_max_dim") = 16384 (the bound of the neighbouring entries; a pixel index stays below 2^28); a pitch smaller than the row; a source pointer,
+ * pitch or frame stride that is no multiple of the element size; results that overlap the source or the mask in HBM; vals and locs in different kinds of memory. */
+MI355CV_API int mi355cv_minMaxLoc(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, const mi355cv_uchar* mask_data, size_t mask_step,
+        double* vals, int* locs);
+/* `nframes` frames of one geometry, `src_frame_stride` bytes apart; mask_frame_stride 0: one mask for all frames.  vals: 2 doubles per frame, locs: 4 ints per
+ * frame, dense.  One enqueue of two launches whatever nframes is (frames in host memory are staged in groups of at most 1 GiB).  A frame with an empty candidate
+ * set does not affect the others.  1 <= nframes <= 65535. */
+MI355CV_API int mi355cv_minMaxLocBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, int depth,
+        const mi355cv_uchar* mask_data, size_t mask_step, size_t mask_frame_stride, int nframes, double* vals, int* locs);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

@@ -1,6 +1,6 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
 // (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, connectedComponents,
-// connectedComponentsWithStats, HoughLines, matchTemplate -- and for the map
+// connectedComponentsWithStats, HoughLines, minMaxLoc, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -271,6 +271,26 @@ inline void HoughLines(cv::InputArray _image, cv::OutputArray _lines, double rho
     }
     if (type == CV_32FC3) cv::HoughLinesWithAccumulator(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
     else cv::HoughLines(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
+}
+
+// cv::minMaxLoc (core.hpp): one channel of CV_8U .. CV_64F with an optional CV_8UC1 mask; any output may be null.  NaN is never a candidate and an empty
+// candidate set gives 0, 0, (-1, -1), (-1, -1) -- this project's restatement (mi355cv.h), the reference was not available to pin either.  Everything the library
+// declines goes to the stock function.  Like mi355cv::pyrUp, this wrapper has not yet been compiled against the reference's headers.
+inline void minMaxLoc(cv::InputArray _src, double* minVal, double* maxVal = 0, cv::Point* minLoc = 0, cv::Point* maxLoc = 0, cv::InputArray _mask = cv::noArray())
+{
+    cv::Mat src = _src.getMat(), mask = _mask.getMat();
+    if (src.dims <= 2 && !src.empty() && src.channels() == 1 && !_src.isUMat() && (mask.empty() || (mask.type() == CV_8UC1 && mask.size() == src.size()))) {
+        double vals[2];
+        int locs[4];
+        if (mi355cv_minMaxLoc(src.data, src.step, src.cols, src.rows, src.depth(), mask.empty() ? 0 : mask.data, mask.empty() ? 0 : (size_t)mask.step, vals, locs) == MI355CV_OK) {
+            if (minVal) *minVal = vals[0];
+            if (maxVal) *maxVal = vals[1];
+            if (minLoc) *minLoc = cv::Point(locs[0], locs[1]);
+            if (maxLoc) *maxLoc = cv::Point(locs[2], locs[3]);
+            return;
+        }
+    }
+    cv::minMaxLoc(_src, minVal, maxVal, minLoc, maxLoc, _mask);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

@@ -177,6 +177,8 @@ def _load():
         "mi355cv_houghLinesBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_sz, c_int, c_dbl, c_dbl, c_int, c_dbl, c_dbl, c_dbl, c_dbl,
                                             ctypes.POINTER(c_int)]),
         "mi355cv_houghLinesAccum": (c_int, [c_u8p, c_sz, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, ctypes.c_void_p, c_sz, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+        "mi355cv_minMaxLoc": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_u8p, c_sz, ctypes.c_void_p, ctypes.c_void_p]),
+        "mi355cv_minMaxLocBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_u8p, c_sz, c_sz, c_int, ctypes.c_void_p, ctypes.c_void_p]),
         "mi355cv_buildPyramid": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_sz), c_int, c_int]),
         "mi355cv_cornerHarris": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int]),
         "mi355cv_cornerMinEigenVal": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -31,7 +31,7 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
            "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
            "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI",
-           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "minMaxLoc", "minMaxLocBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1531,6 +1531,58 @@ def HoughLinesAccumulator(image, rho, theta, min_theta=0, max_theta=math.pi):
     bind_stream(s)
     _lib.check(L.mi355cv_houghLinesAccum(*args, _vp(ptr), shape[1] * 4, ctypes.byref(na), ctypes.byref(nr)), "houghLinesAccum")
     return out
+
+
+# ----------------------------------------------------------------------------- cv::minMaxLoc (no HAL binding made: mi355cv_minMaxLoc* )
+def _minmax_mask(name, mask, like, shapes):
+    """the mask of minMaxLoc*: CV_8UC1 of one of `shapes`, of the same kind and on the same device as the source"""
+    if mask is None:
+        return None
+    is_t = torch is not None and isinstance(like, torch.Tensor)
+    if is_t != (torch is not None and isinstance(mask, torch.Tensor)) or (is_t and mask.device != like.device):
+        raise ValueError(name + ": the mask must live where the source lives")
+    if not is_t:
+        mask = np.asarray(mask)
+    if tuple(mask.shape) not in shapes or mask.dtype != (torch.uint8 if is_t else np.uint8):
+        raise ValueError(name + ": the mask must be CV_8UC1 of the source's size")
+    return mask
+
+
+def minMaxLoc(src, mask=None):
+    """cv::minMaxLoc -> mi355cv_minMaxLoc: one channel of CV_8U .. CV_64F [H,W], optional CV_8UC1 mask (non-zero selects) -> (minVal, maxVal, minLoc, maxLoc), the
+    locations as (x, y) of the FIRST pixel in raster order that holds the value.  NaN is never a candidate; an empty candidate set gives (0.0, 0.0, (-1, -1), (-1, -1))."""
+    s = Img(src)
+    if s.cn != 1 or getattr(s.obj, "ndim", 2) != 2:
+        raise ValueError("minMaxLoc: the source must be a 2-D single-channel image")
+    mask = _minmax_mask("minMaxLoc", mask, s.obj, ((s.h, s.w),))
+    m = Img(mask) if mask is not None else None
+    vals, locs = (ctypes.c_double * 2)(), (ctypes.c_int * 4)()
+    bind_stream(s)
+    rc = L.mi355cv_minMaxLoc(_vp(s.ptr), s.step, s.w, s.h, s.depth, _vp(m.ptr) if m is not None else None, m.step if m is not None else 0, vals, locs)
+    _lib.check(rc, "minMaxLoc")
+    return vals[0], vals[1], (locs[0], locs[1]), (locs[2], locs[3])
+
+
+def minMaxLocBatch(frames, mask=None, device=False):
+    """cv::minMaxLoc over [B,H,W] frames (strided views such as frames[:, 3:, 5:] are taken as they are), one enqueue -> (vals float64 [B,2] of (min, max), locs
+    int32 [B,4] of (minX, minY, maxX, maxY)).  mask: [H,W], shared by all frames, or [B,H,W].  device=True: both tensors stay on the frames' device and nothing is
+    read back; otherwise they are CPU tensors."""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("minMaxLocBatch: frames [B, H, W] of one channel")
+    mask = _minmax_mask("minMaxLocBatch", mask, frames, ((s0.h, s0.w), (n, s0.h, s0.w)))
+    mptr, mstep, mframe = None, 0, 0
+    if mask is not None:
+        m0 = Img(mask if mask.dim() == 2 else mask[0])
+        mptr, mstep, mframe = _vp(m0.ptr), m0.step, (int(mask.stride(0)) if mask.dim() == 3 else 0)
+    if device and not frames.is_cuda:
+        raise ValueError("minMaxLocBatch: device=True needs frames in device memory")
+    dev = frames.device if device else "cpu"
+    vals, locs = torch.empty((n, 2), dtype=torch.float64, device=dev), torch.empty((n, 4), dtype=torch.int32, device=dev)
+    bind_stream(s0)
+    rc = L.mi355cv_minMaxLocBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, s0.depth, mptr, mstep, mframe, n, _vp(vals.data_ptr()), _vp(locs.data_ptr()))
+    _lib.check(rc, "minMaxLocBatch")
+    return vals, locs
 
 
 def buildPyramid(src, maxlevel, borderType=BORDER_DEFAULT):
