@@ -321,6 +321,19 @@ MI355CV_API int mi355cv_pyrup(const mi355cv_uchar* src_data, size_t src_step, in
 MI355CV_API int mi355cv_pyrupBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int src_width, int src_height,
         mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride, int dst_width, int dst_height, int nframes,
         int depth, int cn, int border_type);
+/* cv::demosaicing / the Bayer codes of cv::cvtColor (demosaicing.cpp, Bayer2RGB_ / Bayer2Gray_) have no HAL hook (csrc/demosaic.hip): bilinear interpolation only.
+ * src: one channel of CV_8U or CV_16U (depth 0 or 2), width x height; dst: dcn = 3 (B G R), 4 (B G R alpha, alpha = 255 / 65535) or 1 (gray, the reference's own
+ * weights on the unrounded sums) channels of the same depth and size.  pattern 0..3 = BG, GB, RG, GR (COLOR_BayerBG2BGR .. COLOR_BayerGR2BGR), taken relative to
+ * the pointer handed in, like a cv::Mat submatrix; for R G B order pass the pattern with red and blue exchanged (BG <-> RG, GB <-> GR).  Bit-identical to the
+ * reference's definition restated in csrc/demosaic_math.h.  Declined (MI355CV_NOT_IMPLEMENTED, before any device is touched): null pointers, other depths, dcn or
+ * patterns, width or height below 3 or above mi355cv_limit("demosaic_max_dim") = 16384, a pitch below the row, a pointer / pitch / frame stride that is no multiple
+ * of the element size, nframes < 1; source and destination that overlap in HBM.  Both images in HBM, or both in host memory (staged under the host policy, cost
+ * class HOST_CHEAP). */
+MI355CV_API int mi355cv_demosaic(const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* dst, size_t dst_step,
+        int width, int height, int depth, int dcn, int pattern);
+/* `nframes` frames of one geometry, `*_frame_stride` bytes apart, one launch; all in HBM, or all in host memory (the pipelined path) */
+MI355CV_API int mi355cv_demosaicBatch(const mi355cv_uchar* src, size_t src_step, size_t src_frame_stride,
+        mi355cv_uchar* dst, size_t dst_step, size_t dst_frame_stride, int width, int height, int nframes, int depth, int dcn, int pattern);
 /* cv::distanceTransform (distransform.cpp) has no HAL hook (csrc/disttransform.hip).  src CV_8UC1, a pixel is a site iff it is 0; dst has the source's size.
  * Served: distance_type DIST_L2 (2) with mask_size DIST_MASK_PRECISE (0) -- the exact integer squared distance to the nearest site, square-rooted and correctly
  * rounded to float, dst_depth MI355CV_32F; DIST_L1 (1) and DIST_C (3) with mask_size 0, 3 or 5 (one result: the exact city-block / chessboard distance, which is what

@@ -1,5 +1,5 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
-// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, distanceTransform, connectedComponents,
+// (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, demosaicing, distanceTransform, connectedComponents,
 // connectedComponentsWithStats, HoughLines, minMaxLoc, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
@@ -177,6 +177,29 @@ inline void pyrUp(cv::InputArray _src, cv::OutputArray _dst, const cv::Size& dst
             return;
     }
     cv::pyrUp(src, _dst, dstsize, borderType);
+}
+
+// cv::demosaicing (imgproc.hpp; demosaicing.cpp): the bilinear Bayer codes -- COLOR_BayerBG2BGR .. GR2BGR (46 .. 49, the ...2RGB names are the same codes with the
+// B and R patterns exchanged), COLOR_Bayer..2GRAY (86 .. 89), COLOR_Bayer..2BGRA (139 .. 142) -- on CV_8UC1 / CV_16UC1 on the device; dstCn = 4 on a ...2BGR code
+// gives the four-channel result.  The VNG (62 .. 65) and edge-aware (135 .. 138) codes, other types, images below 3 x 3 and everything else the library declines go
+// to the stock function.  A cv::cvtColor call with a Bayer code ends in cv::demosaicing, so such call sites switch to this wrapper too.  Like mi355cv::pyrUp, this
+// wrapper has not yet been compiled against the reference's headers.
+inline void demosaicing(cv::InputArray _src, cv::OutputArray _dst, int code, int dstCn = 0)
+{
+    cv::Mat src = _src.getMat();
+    int pattern = -1, dcn = 0;
+    if (code >= 46 && code <= 49) { pattern = code - 46; dcn = dstCn > 0 ? dstCn : 3; }
+    else if (code >= 86 && code <= 89) { pattern = code - 86; dcn = 1; }
+    else if (code >= 139 && code <= 142) { pattern = code - 139; dcn = dstCn > 0 ? dstCn : 4; }
+    if (pattern >= 0 && (dcn == 1 || dcn == 3 || dcn == 4) && src.dims <= 2 && src.channels() == 1 && src.cols >= 3 && src.rows >= 3 && !_dst.isUMat()) {
+        // (when the destination is the source's own array, create() gives it a new buffer -- the types differ unless dcn == 1, and then the library declines the
+        // overlap -- and `src` keeps the old one)
+        _dst.create(src.size(), CV_MAKETYPE(src.depth(), dcn));
+        cv::Mat dst = _dst.getMat();
+        if (mi355cv_demosaic(src.data, src.step, dst.data, dst.step, src.cols, src.rows, src.depth(), dcn, pattern) == MI355CV_OK)
+            return;
+    }
+    cv::demosaicing(src, _dst, code, dstCn);
 }
 
 // cv::distanceTransform (imgproc.hpp; distransform.cpp), the unlabelled overload: DIST_L2 with DIST_MASK_PRECISE, DIST_L1 and DIST_C on the device as the exact

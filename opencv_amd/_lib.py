@@ -166,6 +166,8 @@ def _load():
         "mi355cv_pyrdownBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_pyrup": (c_int, [c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_pyrupBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
+        "mi355cv_demosaic": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int]),
+        "mi355cv_demosaicBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_distanceTransform": (c_int, [c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, c_int]),
         "mi355cv_distanceTransformBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int]),
         "mi355cv_connectedComponents": (c_int, [c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, c_int, ctypes.POINTER(c_int)]),

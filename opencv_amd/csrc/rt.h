@@ -37,6 +37,7 @@ constexpr int CCL_MAX_DIM = 16384;         // mi355cv_connectedComponents*: widt
 constexpr int HOUGH_MAX_DIM = 16384;       // mi355cv_houghLines*: width and height (packed 16-bit point coordinates, counts below 2^28; hough_math.h)
 constexpr int HOUGH_MAX_ACCUM = 1 << 26;   // ... and the cells of the accumulator, (numangle + 2) x (numrho + 2): a cell index is the low word of the sort key
 constexpr int MINMAX_MAX_DIM = 16384;      // mi355cv_minMaxLoc*: width and height (a raster pixel index below 2^28, item counts in 32 bits; minmax_math.h)
+constexpr int DEMOSAIC_MAX_DIM = 16384;    // mi355cv_demosaic*: width and height (the neighbours' bound; a destination row offset of 8 bytes per pixel stays far below 2^31)
 }
 
 struct ThreadCtx;

@@ -582,7 +582,8 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"adaptive_gaussian_max_block", SEP_MAX_TAPS}, {"adaptive_mean_max_block", ADAPTIVE_MEAN_MAX_BLOCK}, {"box_max_ksize", BOX_MAX_KSIZE},
         {"median8u_max_ksize", MEDIAN8U_MAX_KSIZE}, {"bilateral_max_d", 2 * BILATERAL_MAX_RADIUS + 1}, {"orb_max_levels", ORB_MAX_LEVELS}, {"filter2d_dft_taps", FILTER2D_DFT_TAPS},
         {"disttransform_max_dim", DISTTRANSFORM_MAX_DIM}, {"ccl_max_dim", CCL_MAX_DIM},
-        {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"minmax_max_dim", MINMAX_MAX_DIM}};
+        {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"minmax_max_dim", MINMAX_MAX_DIM},
+        {"demosaic_max_dim", DEMOSAIC_MAX_DIM}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;

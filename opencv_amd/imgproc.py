@@ -27,6 +27,12 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "COLOR_GRAY2RGBA", "COLOR_BGRA2GRAY", "COLOR_RGBA2GRAY",
            "matchTemplate", "matchTemplateBatch", "integral", "integralBatch", "TM_SQDIFF", "TM_SQDIFF_NORMED", "TM_CCORR", "TM_CCORR_NORMED",
            "TM_CCOEFF", "TM_CCOEFF_NORMED",
+           "demosaicing", "demosaicingBatch",
+           "COLOR_BayerBG2BGR", "COLOR_BayerGB2BGR", "COLOR_BayerRG2BGR", "COLOR_BayerGR2BGR", "COLOR_BayerBG2RGB", "COLOR_BayerGB2RGB", "COLOR_BayerRG2RGB", "COLOR_BayerGR2RGB",
+           "COLOR_BayerRGGB2BGR", "COLOR_BayerGRBG2BGR", "COLOR_BayerBGGR2BGR", "COLOR_BayerGBRG2BGR", "COLOR_BayerRGGB2RGB", "COLOR_BayerGRBG2RGB", "COLOR_BayerBGGR2RGB", "COLOR_BayerGBRG2RGB",
+           "COLOR_BayerBG2GRAY", "COLOR_BayerGB2GRAY", "COLOR_BayerRG2GRAY", "COLOR_BayerGR2GRAY", "COLOR_BayerRGGB2GRAY", "COLOR_BayerGRBG2GRAY", "COLOR_BayerBGGR2GRAY", "COLOR_BayerGBRG2GRAY",
+           "COLOR_BayerBG2BGRA", "COLOR_BayerGB2BGRA", "COLOR_BayerRG2BGRA", "COLOR_BayerGR2BGRA", "COLOR_BayerBG2RGBA", "COLOR_BayerGB2RGBA", "COLOR_BayerRG2RGBA", "COLOR_BayerGR2RGBA",
+           "COLOR_BayerRGGB2BGRA", "COLOR_BayerGRBG2BGRA", "COLOR_BayerBGGR2BGRA", "COLOR_BayerGBRG2BGRA", "COLOR_BayerRGGB2RGBA", "COLOR_BayerGRBG2RGBA", "COLOR_BayerBGGR2RGBA", "COLOR_BayerGBRG2RGBA",
            "pyrDown", "pyrUp", "pyrUpBatch", "distanceTransform", "distanceTransformBatch", "DIST_L1", "DIST_L2", "DIST_C", "DIST_MASK_3", "DIST_MASK_5",
            "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
            "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
@@ -330,6 +336,8 @@ def cvtColor(src, code, dst=None, dstCn=0):
         return out
     if code in _MISC:
         return _cvt_misc(src, s, code, dst, dstCn)
+    if code in _BAYER:                                                      # color.cpp: the Bayer codes end in demosaicing()
+        return demosaicing(src, code, dst, dstCn)
     raise NotImplementedError(f"cvtColor: conversion code {code} is outside the hot path built so far")
 
 
@@ -458,7 +466,9 @@ def cvtColorBGR2NV(src, swapBlue=False, nv21=False, dst=None):
 
 
 def cvtColorBatch(frames, code, dst=None):
-    """[N,H,W,C] device-resident frames -> gray [N,H,W], one launch."""
+    """[N,H,W,C] device-resident frames -> gray [N,H,W], one launch; the Bayer codes: [N,H,W] -> demosaicingBatch."""
+    if code in _BAYER:
+        return demosaicingBatch(frames, code, dst)
     if code not in _RGB2GRAY:
         raise NotImplementedError("cvtColorBatch: only *2GRAY")
     scn, swap = _RGB2GRAY[code]
@@ -1307,6 +1317,71 @@ def pyrUpBatch(frames, dst=None):
     rc = L.mi355cv_pyrupBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, d0.w, d0.h, n,
                               s0.depth, s0.cn, BORDER_DEFAULT)
     _lib.check(rc, "pyrupBatch")
+    return out
+
+
+# ----------------------------------------------------------------------------- Bayer demosaicing (no HAL hook: mi355cv_demosaic / ...Batch)
+# imgproc.hpp: a pattern is named after the colours of row 1, columns 1 and 2; the ...2RGB names are the ...2BGR codes with the B and R patterns exchanged, and the
+# sensor-order names of 4.x are aliases (RGGB = BG, GRBG = GB, BGGR = RG, GBRG = GR)
+COLOR_BayerBG2BGR, COLOR_BayerGB2BGR, COLOR_BayerRG2BGR, COLOR_BayerGR2BGR = 46, 47, 48, 49
+COLOR_BayerRG2RGB, COLOR_BayerGR2RGB, COLOR_BayerBG2RGB, COLOR_BayerGB2RGB = 46, 47, 48, 49
+COLOR_BayerRGGB2BGR, COLOR_BayerGRBG2BGR, COLOR_BayerBGGR2BGR, COLOR_BayerGBRG2BGR = 46, 47, 48, 49
+COLOR_BayerBGGR2RGB, COLOR_BayerGBRG2RGB, COLOR_BayerRGGB2RGB, COLOR_BayerGRBG2RGB = 46, 47, 48, 49
+COLOR_BayerBG2GRAY, COLOR_BayerGB2GRAY, COLOR_BayerRG2GRAY, COLOR_BayerGR2GRAY = 86, 87, 88, 89
+COLOR_BayerRGGB2GRAY, COLOR_BayerGRBG2GRAY, COLOR_BayerBGGR2GRAY, COLOR_BayerGBRG2GRAY = 86, 87, 88, 89
+COLOR_BayerBG2BGRA, COLOR_BayerGB2BGRA, COLOR_BayerRG2BGRA, COLOR_BayerGR2BGRA = 139, 140, 141, 142
+COLOR_BayerRG2RGBA, COLOR_BayerGR2RGBA, COLOR_BayerBG2RGBA, COLOR_BayerGB2RGBA = 139, 140, 141, 142
+COLOR_BayerRGGB2BGRA, COLOR_BayerGRBG2BGRA, COLOR_BayerBGGR2BGRA, COLOR_BayerGBRG2BGRA = 139, 140, 141, 142
+COLOR_BayerBGGR2RGBA, COLOR_BayerGBRG2RGBA, COLOR_BayerRGGB2RGBA, COLOR_BayerGRBG2RGBA = 139, 140, 141, 142
+# code -> (pattern 0..3 = BG, GB, RG, GR, channels the code asks for); the VNG (62-65) and edge-aware (135-138) codes are not built
+_BAYER = {46: (0, 3), 47: (1, 3), 48: (2, 3), 49: (3, 3), 86: (0, 1), 87: (1, 1), 88: (2, 1), 89: (3, 1), 139: (0, 4), 140: (1, 4), 141: (2, 4), 142: (3, 4)}
+_BAYER_OTHER = frozenset((62, 63, 64, 65, 135, 136, 137, 138))
+
+
+def _bayer_args(name, code, s, dstCn):
+    if code in _BAYER_OTHER:
+        raise NotImplementedError(f"{name}: VNG and edge-aware demosaicing (code {code}) are not built; only the bilinear codes are")
+    if code not in _BAYER:
+        raise ValueError(f"{name}: {code} is no Bayer conversion code")                 # demosaicing.cpp: "Unknown / unsupported color conversion code"
+    if s.cn != 1:
+        raise ValueError(f"{name}: the source must be single-channel")                  # CV_Assert(scn == 1)
+    pattern, dcn = _BAYER[code]
+    if dcn != 1 and dstCn > 0:
+        dcn = dstCn
+    if dcn not in (1, 3, 4):
+        raise ValueError(f"{name}: dstCn must be 3 or 4")                               # CV_Assert(dcn == 3 || dcn == 4)
+    return pattern, dcn
+
+
+def demosaicing(src, code, dst=None, dstCn=0):
+    """cv::demosaicing (demosaicing.cpp, Bayer2RGB_ / Bayer2Gray_; no HAL hook) -> mi355cv_demosaic: bilinear, [H,W] CV_8U / CV_16U -> [H,W,3], [H,W,4] (alpha = the
+    depth's maximum) or gray [H,W].  The pattern is relative to the origin of `src` (a view starting on an odd row or column sees the shifted pattern).  dstCn = 4
+    on a ...2BGR / ...2RGB code gives the four-channel result."""
+    s = Img(src)
+    pattern, dcn = _bayer_args("demosaicing", code, s, dstCn)
+    out = dst if dst is not None else _like(src, s.h, s.w, dcn, s.depth)
+    d = Img(out)
+    if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, dcn, s.depth):
+        raise ValueError("demosaicing: dst geometry mismatch")
+    bind_stream(s, d)
+    rc = L.mi355cv_demosaic(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, s.depth, dcn, pattern)
+    _lib.check(rc, "demosaic")
+    return out
+
+
+def demosaicingBatch(frames, code, dst=None, dstCn=0):
+    """cv::demosaicing over [N,H,W] frames -> [N,H,W,3], [N,H,W,4] or [N,H,W], one launch (host-resident batches: the pipelined path)"""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("demosaicingBatch: frames [N, H, W] of one channel")
+    pattern, dcn = _bayer_args("demosaicingBatch", code, s0, dstCn)
+    shape = (n, s0.h, s0.w) + ((dcn,) if dcn > 1 else ())
+    out = _batch_out(frames, dst, shape, frames.dtype)
+    d0 = Img(out[0])
+    bind_stream(s0, d0)
+    rc = L.mi355cv_demosaicBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz, s0.w, s0.h, n,
+                                 s0.depth, dcn, pattern)
+    _lib.check(rc, "demosaicBatch")
     return out
 
 
