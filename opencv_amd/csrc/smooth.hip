@@ -252,7 +252,11 @@ __global__ __launch_bounds__(256) void k_binomial_roll(
 //    drain vmcnt to 0 every row.  Every lane issues the same two loads per row (its 16 B + one side
 //    dword whose address only differs on lanes 0 / 63), image-border halos are rebuilt from the lane's
 //    own registers, and border rows are resolved to scalars before the loop;
-//  * a KS-deep ring of in-flight row loads per wave (a slot is refilled right after it is consumed);
+//  * a KS-deep ring of in-flight row loads per wave (a slot is refilled right after it is consumed).  RING = false is the loop of rounds 4-6:
+//    the tail guard inside its unrolled group made the compiler drain the ring (s_waitcnt vmcnt(0)) once per KS rows, and its KS-1 prologue
+//    rows were KS-1 serial round trips.  RING = true keeps the ring in flight: all 2 KS - 1 rows a work item starts with are issued back to
+//    back in row order, the loop runs over whole groups of KS rows without a guard (every row then waits with KS-1 newer rows outstanding)
+//    and the nrows % KS tail rows are peeled off behind it.  The waits stay the compiler's; tools/ring_isa.py prints them;
 //  * neighbour bytes through DPP wave_shr/wave_shl (one v_mov_dpp) instead of ds_bpermute;
 //  * optional non-temporal stores (results are never re-read by this kernel).
 // Handles BORDER_CONSTANT/REPLICATE/REFLECT/REFLECT_101 with W > KS/2 (halo source bytes then lie
@@ -358,7 +362,7 @@ __device__ __forceinline__ void hfilter2(uint32_t (&Hrow)[8], const RawRow2<Roll
     }
 }
 
-template <int KS, int CN, bool NT, bool NTL, int WPS, bool EB = true>
+template <int KS, int CN, bool NT, bool NTL, int WPS, bool EB = true, bool RING = false>
 __global__ __launch_bounds__(256, WPS) void k_binomial_roll2(
     const uchar* __restrict__ src, size_t sstep, size_t sframe,
     uchar* __restrict__ dst, size_t dstep, size_t dframe,
@@ -444,72 +448,121 @@ __global__ __launch_bounds__(256, WPS) void k_binomial_roll2(
     };
 
     uint32_t Hw[KS][8];
-#pragma unroll
-    for (int i = 0; i < KS - 1; i++) {      // prologue: logical rows -R .. R-1 -> slots 0..KS-2
-        const int ry = rowIdx(gy(min(i - R, nrows - 1 + R)));
-        if (ry < 0) {
-#pragma unroll
-            for (int j = 0; j < 8; j++) Hw[i][j] = 0;
-        } else {
-            RawRow2<HD> pre;
-            issueRow<KS, CN>(pre, src + (size_t)ry * sstep, mainOff, sideOff);
-            hfilter2<KS, CN, EB>(Hw[i], pre, hasFirst, hasLast, isLastChunk, es);
-        }
-    }
     RawRow2<HD> raw[KS];
     int rvalid[KS];
+    // slot u of the ring holds a landed row: filter it into the newest Hw slot (zeros for a BORDER_CONSTANT row outside the image)
+    auto consume = [&](int u) __attribute__((always_inline)) {
+        uint32_t (&Hn)[8] = Hw[(KS - 1 + u) % KS];
+        if (rvalid[u]) hfilter2<KS, CN, EB>(Hn, raw[u], hasFirst, hasLast, isLastChunk, es);
+        else {
 #pragma unroll
-    for (int u = 0; u < KS; u++) {          // prime the ring: logical rows R+u
-        const int ry = rowIdx(gy(min(u + R, nrows - 1 + R)));
+            for (int j = 0; j < 8; j++) Hn[j] = 0;
+        }
+    };
+    // refill ring slot u with logical row j (clamped: always a legal address)
+    auto refill = [&](int u, int j) __attribute__((always_inline)) {
+        const int ry = rowIdx(gy(min(j, nrows - 1 + R)));
         rvalid[u] = ry >= 0;
         issueRow<KS, CN, NTL>(raw[u], src + (size_t)max(ry, 0) * sstep, mainOff, sideOff);
-    }
-    for (int y = 0; y < nrows; y += KS) {
+    };
+    // vertical pass over the KS filtered rows that end in slot (KS - 1 + u) % KS, stored as logical row j
+    auto emit = [&](int u, int j) __attribute__((always_inline)) {
+        uint32_t o[4];
+        if constexpr (KS == 5) {
+            const uint32_t* h0 = Hw[(u + 0) % 5]; const uint32_t* h1 = Hw[(u + 1) % 5];
+            const uint32_t* h2 = Hw[(u + 2) % 5]; const uint32_t* h3 = Hw[(u + 3) % 5];
+            const uint32_t* h4 = Hw[(u + 4) % 5];
+            uint32_t v[8];
+#pragma unroll
+            for (int i = 0; i < 8; i++) {                // four full-rate operations per dword, no multiply by 6 (see k_binomial_roll)
+                if constexpr (EB) {
+                    const uint32_t b4 = lshlAdd(h1[i] + h3[i] + h2[i], 2, 0x00800080u);
+                    v[i] = h0[i] + h4[i] + lshlAdd(h2[i], 1, b4);
+                } else
+                    v[i] = (h0[i] + h4[i]) + ((h1[i] + h3[i]) << 2) + (h2[i] << 1) + (h2[i] << 2) + 0x00800080u;
+            }
+#pragma unroll
+            for (int k = 0; k < 4; k++) o[k] = __builtin_amdgcn_perm(v[4 + k], v[k], 0x07030501u);
+        } else {
+            const uint32_t* h0 = Hw[(u + 0) % 3]; const uint32_t* h1 = Hw[(u + 1) % 3]; const uint32_t* h2 = Hw[(u + 2) % 3];
+#pragma unroll
+            for (int k = 0; k < 4; k++) {
+                uint32_t ve = ((h0[k] + h2[k] + (h1[k] << 1) + 0x00080008u) >> 4) & 0x00FF00FFu;
+                uint32_t vo = ((h0[4 + k] + h2[4 + k] + (h1[4 + k] << 1) + 0x00080008u) >> 4) & 0x00FF00FFu;
+                o[k] = ve | (vo << 8);
+            }
+        }
+        if (active) {
+            typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
+            u32x4 ov = {o[0], o[1], o[2], o[3]};
+            u32x4* dp = reinterpret_cast<u32x4*>(dst + (size_t)gy(j) * dstep + 16 * (size_t)c);
+            if constexpr (NT) __builtin_nontemporal_store(ov, dp);
+            else *dp = ov;
+        }
+    };
+    if constexpr (RING) {
+        // all 2 KS - 1 rows the item starts with, issued back to back and oldest first (the scheduling barriers pin that order: the compiler's
+        // wait for a row then leaves every newer row in flight): logical rows -R .. R-1 for slots 0..KS-2, then the ring, logical rows R+u
+        RawRow2<HD> pre[KS - 1];
+        int pvalid[KS - 1];
+#pragma unroll
+        for (int i = 0; i < KS - 1; i++) {
+            const int ry = rowIdx(gy(min(i - R, nrows - 1 + R)));
+            pvalid[i] = ry >= 0;
+            issueRow<KS, CN>(pre[i], src + (size_t)max(ry, 0) * sstep, mainOff, sideOff);
+            __builtin_amdgcn_sched_barrier(0);
+        }
 #pragma unroll
         for (int u = 0; u < KS; u++) {
+            refill(u, u + R);
+            __builtin_amdgcn_sched_barrier(0);
+        }
+#pragma unroll
+        for (int i = 0; i < KS - 1; i++) {
+            // a BORDER_CONSTANT row outside the image is a select after the filter, not a branch around it: the compiler sinks a row's load into
+            // such a branch, behind the waits of the rows before it
+            hfilter2<KS, CN, EB>(Hw[i], pre[i], hasFirst, hasLast, isLastChunk, es);
+#pragma unroll
+            for (int j = 0; j < 8; j++) Hw[i][j] = pvalid[i] ? Hw[i][j] : 0u;
+        }
+        int y = 0;
+        for (; y + KS <= nrows; y += KS) {  // whole groups: straight-line, slot u is refilled right after it is consumed
+#pragma unroll
+            for (int u = 0; u < KS; u++) {
+                consume(u);
+                refill(u, y + u + KS + R);
+                emit(u, y + u);
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < KS - 1; u++) {  // the nrows % KS tail rows: y is a multiple of KS, so the slots stay static; nothing left to refill
             if (y + u < nrows) {
-                uint32_t (&Hn)[8] = Hw[(KS - 1 + u) % KS];
-                if (rvalid[u]) hfilter2<KS, CN, EB>(Hn, raw[u], hasFirst, hasLast, isLastChunk, es);
-                else {
+                consume(u);
+                emit(u, y + u);
+            }
+        }
+    } else {
 #pragma unroll
-                    for (int j = 0; j < 8; j++) Hn[j] = 0;
-                }
-                {   // refill this ring slot with the row needed KS iterations from now (clamped: always a legal address)
-                    const int ry = rowIdx(gy(min(y + u + KS + R, nrows - 1 + R)));
-                    rvalid[u] = ry >= 0;
-                    issueRow<KS, CN, NTL>(raw[u], src + (size_t)max(ry, 0) * sstep, mainOff, sideOff);
-                }
-                uint32_t o[4];
-                if constexpr (KS == 5) {
-                    const uint32_t* h0 = Hw[(u + 0) % 5]; const uint32_t* h1 = Hw[(u + 1) % 5];
-                    const uint32_t* h2 = Hw[(u + 2) % 5]; const uint32_t* h3 = Hw[(u + 3) % 5];
-                    const uint32_t* h4 = Hw[(u + 4) % 5];
-                    uint32_t v[8];
+        for (int i = 0; i < KS - 1; i++) {      // prologue: logical rows -R .. R-1 -> slots 0..KS-2
+            const int ry = rowIdx(gy(min(i - R, nrows - 1 + R)));
+            if (ry < 0) {
 #pragma unroll
-                    for (int i = 0; i < 8; i++) {                // four full-rate operations per dword, no multiply by 6 (see k_binomial_roll)
-                        if constexpr (EB) {
-                            const uint32_t b4 = lshlAdd(h1[i] + h3[i] + h2[i], 2, 0x00800080u);
-                            v[i] = h0[i] + h4[i] + lshlAdd(h2[i], 1, b4);
-                        } else
-                            v[i] = (h0[i] + h4[i]) + ((h1[i] + h3[i]) << 2) + (h2[i] << 1) + (h2[i] << 2) + 0x00800080u;
-                    }
+                for (int j = 0; j < 8; j++) Hw[i][j] = 0;
+            } else {
+                RawRow2<HD> pre;
+                issueRow<KS, CN>(pre, src + (size_t)ry * sstep, mainOff, sideOff);
+                hfilter2<KS, CN, EB>(Hw[i], pre, hasFirst, hasLast, isLastChunk, es);
+            }
+        }
 #pragma unroll
-                    for (int k = 0; k < 4; k++) o[k] = __builtin_amdgcn_perm(v[4 + k], v[k], 0x07030501u);
-                } else {
-                    const uint32_t* h0 = Hw[(u + 0) % 3]; const uint32_t* h1 = Hw[(u + 1) % 3]; const uint32_t* h2 = Hw[(u + 2) % 3];
+        for (int u = 0; u < KS; u++) refill(u, u + R);  // prime the ring: logical rows R+u
+        for (int y = 0; y < nrows; y += KS) {
 #pragma unroll
-                    for (int k = 0; k < 4; k++) {
-                        uint32_t ve = ((h0[k] + h2[k] + (h1[k] << 1) + 0x00080008u) >> 4) & 0x00FF00FFu;
-                        uint32_t vo = ((h0[4 + k] + h2[4 + k] + (h1[4 + k] << 1) + 0x00080008u) >> 4) & 0x00FF00FFu;
-                        o[k] = ve | (vo << 8);
-                    }
-                }
-                if (active) {
-                    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-                    u32x4 ov = {o[0], o[1], o[2], o[3]};
-                    u32x4* dp = reinterpret_cast<u32x4*>(dst + (size_t)gy(y + u) * dstep + 16 * (size_t)c);
-                    if constexpr (NT) __builtin_nontemporal_store(ov, dp);
-                    else *dp = ov;
+            for (int u = 0; u < KS; u++) {
+                if (y + u < nrows) {
+                    consume(u);
+                    refill(u, y + u + KS + R);          // the row needed KS iterations from now
+                    emit(u, y + u);
                 }
             }
         }
@@ -567,7 +620,8 @@ bool aligned16(const void* p, size_t step) { return (((uintptr_t)p | step) & 15)
 int envInt(const char* n, int d) { const char* v = getenv(n); return v ? atoi(v) : d; }
 
 int& tuneSeg() { static int v = envInt("MI355CV_GAUSS_SEG", 0); return v; }
-int& tuneVariant() { static int v = envInt("MI355CV_GAUSS_VARIANT", 3); return v; }   // 1: k_binomial_roll, 2: roll2, 3: roll2 + nt stores, 4: 3 with the edge halos as selects instead of branches, 5: 3 at 6 waves / SIMD
+constexpr int kGaussVariantDefault = 6;
+int& tuneVariant() { static int v = envInt("MI355CV_GAUSS_VARIANT", kGaussVariantDefault); return v; }   // 1: k_binomial_roll, 2: roll2, 3: roll2 + nt stores, 4: 3 with the edge halos as selects instead of branches, 5: 3 at 6 waves / SIMD, 6: 3 with the load ring kept in flight (RING)
 
 int& tuneAlt() { static int v = envInt("MI355CV_GAUSS_ALT", 1); return v; }   // 1: alternate walking direction of vertical neighbours
 int& tuneLaunchWaves() { static int v = envInt("MI355CV_GAUSS_LAUNCH_WAVES", 393216); return v; }   // work items per launch of a batch (0: one launch)
@@ -586,11 +640,16 @@ void launchRoll2(const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size
         long long per = (long long)nstrips * nframes;
         long long wantSeg = (2048 + per - 1) / per;
         seg = (int)((H + wantSeg - 1) / wantSeg);
-        const int best = 16;
+        // With the ring kept in flight (nt == 4) a work item starts with ONE exposed round trip instead of KS, so shorter items cost less and the best
+        // length moves down for one channel (interleaved A/Bs, profiles/r07_ab_gauss_ring.txt; GB/s, earlier loop at 16 rows -> ring at 16 -> ring at 12):
+        // 4K 5x5 5791 -> 5797 -> 5984 (8 / 11 / 13 / 14 rows 5909 / 5940 / 5897 / 5888, 15 / 20 / 30 rows 5450-5580; the earlier loop at 12 rows 5755),
+        // 4K 3x3 5381 -> 5577 -> 5718, 8K 5x5 5357 -> 5308 -> 5352.  Three channels (1080p, three loads per row) 5618 -> 5615 -> 5505: they keep 16 rows,
+        // and so do two and four channels, which were not measured.
+        const int best = (nt == 4 && CN == 1) ? 12 : 16;
         if (seg > best) seg = best;
         if (seg < KS) seg = KS;
     }
-    if (seg > H) seg = H;                       // any length works: the row loop guards its tail rows
+    if (seg > H) seg = H;                       // any length works: the row loop guards (RING: peels) its tail rows
     const int nseg = divUp(H, seg);
     // A pass over a large batch is issued as consecutive launches of at most ~tuneLaunchWaves() work items: the same 9216 x 4K frames ran at
     // 70.0-71.0 % of 8 TB/s as ONE launch and at 73.3-75.4 % as 18 launches of 512 frames (tools/split_probe.py, same buffers, launch gaps
@@ -601,14 +660,15 @@ void launchRoll2(const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size
     if (chunk < 1) chunk = 1;
     if (chunk > nframes) chunk = nframes;
     const int nlaunch = (int)((nframes + chunk - 1) / chunk);
-    noteKernel("k_binomial_roll2<%d,%d,%s,false,%d,%s> grid=%u x256 seg=%d rows alt=%d, %d launch(es) of <= %lld frames", KS, CN, nt >= 1 ? "true" : "false", nt == 3 ? 6 : 4,
-               nt == 2 ? "false" : "true", (unsigned)((perFrame * chunk + 3) / 4), seg, tuneAlt(), nlaunch, chunk);
+    noteKernel("k_binomial_roll2<%d,%d,%s,false,%d,%s%s> grid=%u x256 seg=%d rows alt=%d, %d launch(es) of <= %lld frames", KS, CN, nt >= 1 ? "true" : "false", nt == 3 ? 6 : 4,
+               nt == 2 ? "false" : "true", nt == 4 ? ",true" : "", (unsigned)((perFrame * chunk + 3) / 4), seg, tuneAlt(), nlaunch, chunk);
     for (long long f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = (int)(nframes - f0 < chunk ? nframes - f0 : chunk);
         const uchar* sp = s + (size_t)f0 * sf;
         uchar* dp = d + (size_t)f0 * df;
         dim3 grid((unsigned)((perFrame * nf + 3) / 4));
-        if (nt == 3)      hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 6>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
+        if (nt >= 4)      hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4, true, true>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
+        else if (nt == 3) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 6>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
         else if (nt == 2) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4, false>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
         else if (nt == 1) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
         else              hipLaunchKernelGGL((k_binomial_roll2<KS, CN, false, false, 4>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
@@ -934,13 +994,13 @@ MI355CV_API int mi355cv_gaussianBlurBatch(const uchar* src_data, size_t src_step
 }
 
 // tuning knobs for experiments (tools/tune_gauss.py): "gauss_seg" rows per work item (0 = heuristic),
-// "gauss_variant" 1|2|3
+// "gauss_variant" 1..6 (tuneVariant(); 0 = the default)
 MI355CV_API int mi355cv_setParam(const char* key, int value)
 {
     mi355::EntryGuard entry_(__func__);
     if (!key) return -1;
     if (!strcmp(key, "gauss_seg")) { tuneSeg() = value; return 0; }
-    if (!strcmp(key, "gauss_variant")) { tuneVariant() = value; return 0; }
+    if (!strcmp(key, "gauss_variant")) { tuneVariant() = value > 0 ? value : kGaussVariantDefault; return 0; }
     if (!strcmp(key, "gauss_alt")) { tuneAlt() = value; return 0; }
     if (!strcmp(key, "gauss_launch_waves")) { tuneLaunchWaves() = value; return 0; }
     return -1;
