@@ -171,7 +171,8 @@ def sepSmoothFixedU8(src, kx, ky, borderType=BORDER_DEFAULT, dst=None, margins=(
 
 def GaussianBlurBatch(frames, ksize, borderType=BORDER_DEFAULT, dst=None, sigmaX=0.0, sigmaY=0.0):
     """N independent frames [N,H,W(,C)] resident in HBM, one launch (frames shard, never split).  Frames in HOST memory (a CPU tensor,
-    ideally page-locked) take the library's pipelined path: chunks cross PCIe through two sets of device buffers, upload / filter / download overlapped."""
+    ideally page-locked) take the library's pipelined path: chunks cross PCIe through two sets of device buffers, upload / filter / download overlapped.
+    Device-resident frames (and dst) may be views of a wider / taller parent: row step and frame stride go to the library as they are; rows must be dense."""
     if torch is None or not isinstance(frames, torch.Tensor):
         raise ValueError("GaussianBlurBatch needs a tensor [N,H,W(,C)] (CUDA(ROCm) resident, or a CPU tensor for the pipelined host path)")
     if frames.dim() not in (3, 4) or frames.dtype != torch.uint8:
@@ -190,9 +191,9 @@ def GaussianBlurBatch(frames, ksize, borderType=BORDER_DEFAULT, dst=None, sigmaX
         return out
     n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
     cn = int(frames.shape[3]) if frames.dim() == 4 else 1
-    if not frames[0].is_contiguous():
-        raise ValueError("each frame must be contiguous")
-    out = dst if dst is not None else torch.empty_like(frames)
+    out = dst if dst is not None else torch.empty(frames.shape, dtype=frames.dtype, device=frames.device)
+    if tuple(out.shape) != tuple(frames.shape) or out.dtype != frames.dtype or not out.is_cuda:
+        raise ValueError("dst geometry mismatch")
     k = ksize if isinstance(ksize, int) else ksize[0]
     s0, d0 = Img(frames[0]), Img(out[0])
     bind_stream(s0, d0)
