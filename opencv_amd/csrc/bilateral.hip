@@ -191,13 +191,13 @@ __global__ __launch_bounds__(256) void k_bilateral_f32(const uchar* __restrict__
 int bilateral32f(const uchar* src_data, size_t src_step, uchar* dst_data, size_t dst_step, int width, int height, int cn, int radius, double gcc, double gsc, int border)
 {
     Stager stg;
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "host image below the policy threshold");
+    MI355_DECLINE_IF(!ensureDevice());
+    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return MI355_DECLINED("host image below the policy threshold");
     size_t dss, dds;
     const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * 4, height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * cn * 4, height, &dds);
     int* mm = (int*)stg.scratch(8);
-    if (!ds || !dd || !mm) return mi355::declined(__func__, __LINE__, "!ds || !dd || !mm");
+    MI355_DECLINE_IF(!ds || !dd || !mm);
     hipStream_t st = stream();
     // 1. the value range (cv::minMaxLoc over all channels): two ordered-int atomics, then the two floats cross to the host
     const int init[2] = {0x7fffffff, (int)0x80000000};
@@ -241,7 +241,7 @@ int bilateral32f(const uchar* src_data, size_t src_step, uchar* dst_data, size_t
     const float* dlut = (const float*)stg.param(lut.data(), lut.size() * sizeof(float));
     const float* dsw = (const float*)stg.param(sw.data(), sw.size() * sizeof(float));
     const short2* dof = (const short2*)stg.param(of.data(), of.size() * sizeof(short));
-    if (!dlut || !dsw || !dof) return mi355::declined(__func__, __LINE__, "!dlut || !dsw || !dof");
+    MI355_DECLINE_IF(!dlut || !dsw || !dof);
     BilArgsF a; a.W = width; a.H = height; a.radius = radius; a.maxk = maxk; a.border = border; a.scale_index = scale_index; a.bins = bins;
     const int tw = BT_W + 2 * radius, th = BT_H + 2 * radius;
     const size_t lds = (size_t)maxk * 8 + (size_t)tw * th * cn * 4;
@@ -266,11 +266,10 @@ extern "C" MI355CV_API int mi355cv_bilateralFilter(const uchar* src_data, size_t
                                                    int depth, int cn, int d, double sigma_color, double sigma_space, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || width <= 0 || height <= 0 || (depth != MI355CV_8U && depth != MI355CV_32F) || (cn != 1 && cn != 3) || inPlaceOnDevice(src_data, dst_data))
-        return mi355::declined(__func__, __LINE__, "disabled() || width <= 0 || height <= 0 || (depth != MI355CV_8U && depth != MI355CV_32F) || (cn != 1 && cn != 3) || inPlaceOnDevice(src_data, dst_data)");
+    MI355_DECLINE_IF(disabled() || width <= 0 || height <= 0 || (depth != MI355CV_8U && depth != MI355CV_32F) || (cn != 1 && cn != 3) || inPlaceOnDevice(src_data, dst_data));
     const int isolated = border_type & MI355CV_BORDER_ISOLATED;
     const int border = border_type & ~MI355CV_BORDER_ISOLATED;
-    if (border < B_CONSTANT || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border < B_CONSTANT || border > B_REFLECT_101");
+    MI355_DECLINE_IF(border < B_CONSTANT || border > B_REFLECT_101);
     if (!isolated && src_step != (size_t)width * cn * (depth == MI355CV_32F ? 4 : 1) && height > 1)
         return setError(MI355CV_NOT_IMPLEMENTED, "bilateralFilter: rows are not dense and BORDER_ISOLATED is not set (a submatrix is padded with its parent's pixels)");
     if (sigma_color <= 0) sigma_color = 1;
@@ -281,8 +280,8 @@ extern "C" MI355CV_API int mi355cv_bilateralFilter(const uchar* src_data, size_t
     if (radius > B_RMAX) return setError(MI355CV_NOT_IMPLEMENTED, "bilateralFilter: radius %d > %d", radius, B_RMAX);
     if (depth == MI355CV_32F) return bilateral32f(src_data, src_step, dst_data, dst_step, width, height, cn, radius, gcc, gsc, border);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
     std::vector<float> cw((size_t)256 * cn), sw;
     std::vector<short> of;
     for (int i = 0; i < 256 * cn; i++) cw[i] = (float)std::exp(i * i * gcc);
@@ -300,7 +299,7 @@ extern "C" MI355CV_API int mi355cv_bilateralFilter(const uchar* src_data, size_t
     const float* dcw = (const float*)stg.param(cw.data(), cw.size() * sizeof(float));
     const float* dsw = (const float*)stg.param(sw.data(), sw.size() * sizeof(float));
     const short2* dof = (const short2*)stg.param(of.data(), of.size() * sizeof(short));
-    if (!ds || !dd || !dcw || !dsw || !dof) return mi355::declined(__func__, __LINE__, "!ds || !dd || !dcw || !dsw || !dof");
+    MI355_DECLINE_IF(!ds || !dd || !dcw || !dsw || !dof);
     BilArgs a; a.W = width; a.H = height; a.radius = radius; a.maxk = maxk; a.border = border;
     a.body = cn == 1 ? (width / 8) * 8 : (width / 32) * 32;
     const int tw = BT_W + 2 * radius, th = BT_H + 2 * radius, tp = (tw * cn + 3) & ~3;

@@ -161,10 +161,10 @@ extern "C" MI355CV_API int mi355cv_canny(const uchar* src_data, size_t src_step,
                                          double lowThreshold, double highThreshold, int ksize, bool L2gradient)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 4 || (ksize != 3 && ksize != 5)) return mi355::declined(__func__, __LINE__, "disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 4 || (ksize != 3 && ksize != 5)");
+    MI355_DECLINE_IF(disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 4 || (ksize != 3 && ksize != 5));
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
     // canny.cpp:887-896 (the aperture-7 scaling and the swap happen before the hook)
     double lo = lowThreshold, hi = highThreshold;
     if (L2gradient) {
@@ -182,7 +182,7 @@ extern "C" MI355CV_API int mi355cv_canny(const uchar* src_data, size_t src_step,
     short* dy = (short*)stg.scratch(gstep * height);
     uchar* map = (uchar*)stg.scratch(pitch * (((size_t)height + TH - 1) / TH * TH));
     int* flag = (int*)stg.scratch(256);
-    if (!ds || !dd || !dx || !dy || !map || !flag) return mi355::declined(__func__, __LINE__, "!ds || !dd || !dx || !dy || !map || !flag");
+    MI355_DECLINE_IF(!ds || !dd || !dx || !dy || !map || !flag);
     int rc = mi355cv_sobel(ds, dss, (uchar*)dx, gstep, width, height, MI355CV_8U, MI355CV_16S, cn, 0, 0, 0, 0, 1, 0, ksize, 1.0, 0.0, B_REPLICATE);
     if (rc == MI355CV_OK) rc = mi355cv_sobel(ds, dss, (uchar*)dy, gstep, width, height, MI355CV_8U, MI355CV_16S, cn, 0, 0, 0, 0, 0, 1, ksize, 1.0, 0.0, B_REPLICATE);
     if (rc != MI355CV_OK) return rc;

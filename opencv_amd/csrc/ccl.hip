@@ -358,13 +358,13 @@ void launchWrite(const Scr& s, int order, int w, int h, int nf, uchar* d, size_t
 // the refusals that need no device; 0 when the arguments are served
 int cclArgs(const void* src, int w, int h, const void* labels, int nframes, int connectivity, int ltype, int ccltype, const int* nlabels)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src || !labels || !nlabels || nframes < 1) return mi355::declined(__func__, __LINE__, "!src || !labels || !nlabels || nframes < 1");
-    if (connectivity != 4 && connectivity != 8) return mi355::declined(__func__, __LINE__, "connectivity is not 4 or 8");
-    if (ltype != MI355CV_32S && ltype != MI355CV_16U) return mi355::declined(__func__, __LINE__, "ltype is not CV_32S or CV_16U");
-    if (ccl::orderOf(connectivity, ccltype) < 0) return mi355::declined(__func__, __LINE__, "ccltype is not CCL_DEFAULT (-1) or one of 0 .. 5");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src || !labels || !nlabels || nframes < 1);
+    if (connectivity != 4 && connectivity != 8) return MI355_DECLINED("connectivity is not 4 or 8");
+    if (ltype != MI355CV_32S && ltype != MI355CV_16U) return MI355_DECLINED("ltype is not CV_32S or CV_16U");
+    if (ccl::orderOf(connectivity, ccltype) < 0) return MI355_DECLINED("ccltype is not CCL_DEFAULT (-1) or one of 0 .. 5");
     // linear pixel indices and areas are 32-bit, coordinate sums stay below 2^53 (ccl_math.h)
-    if (w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM) return mi355::declined(__func__, __LINE__, "w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM");
+    MI355_DECLINE_IF(w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM);
     return 0;
 }
 
@@ -373,27 +373,27 @@ int runCCL(const char* entry, const uchar* src, size_t sstep, size_t sframe, int
 {
     if (const int rc = cclArgs(src, w, h, labels, nframes, connectivity, ltype, ccltype, nlabels)) return rc;
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY)));
     const size_t e = depthBytes(ltype);
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(h - 1) * sstep + w, lspan = (size_t)(nframes - 1) * lframe + (size_t)(h - 1) * lstep + w * e;
-    if (overlapOnDevice(src, sspan, labels, lspan)) return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, labels, lspan)");
+    MI355_DECLINE_IF(overlapOnDevice(src, sspan, labels, lspan));
     size_t dss = sstep, dls = lstep;
     const uchar* ds = src; uchar* dl = labels;
     if (nframes == 1) {
         ds = stg.in(src, sstep, w, h, &dss);
         dl = stg.out(labels, lstep, w * e, h, &dls);
-        if (!ds || !dl) return mi355::declined(__func__, __LINE__, "!ds || !dl");
-    } else if (!isDevicePtr(src) || !isDevicePtr(labels)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(labels)");
+        MI355_DECLINE_IF(!ds || !dl);
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(labels));
 
     const int order = ccl::orderOf(connectivity, ccltype), conn8 = connectivity == 8;
     const Geom q = geometry(w, h, order);
     // CV_16U: whether every frame's labels fit is known only after all frames are counted, and no destination may be written before: one group
     int group = (int)std::min<size_t>({(size_t)nframes, (size_t)65535, std::max<size_t>(1, (size_t(256) << 20) / q.bytes)});
-    if (ltype == MI355CV_16U) { if (nframes > 65535) return mi355::declined(__func__, __LINE__, "nframes > 65535 with ltype CV_16U"); group = nframes; }
+    if (ltype == MI355CV_16U) { if (nframes > 65535) return MI355_DECLINED("nframes > 65535 with ltype CV_16U"); group = nframes; }
     uchar* scratch = (uchar*)stg.scratch(q.bytes * group + pad256((size_t)group * 4));
     uint32_t* hostN = (uint32_t*)stg.pinned((size_t)nframes * 4);
-    if (!scratch || !hostN) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!scratch || !hostN) return MI355_DECLINED("no scratch");
     Scr s;
     uchar* at = scratch;
     s.P = (uint32_t*)at; at += q.pBytes * group;
@@ -428,7 +428,7 @@ int runCCL(const char* entry, const uchar* src, size_t sstep, size_t sframe, int
     if (hipStreamSynchronize(st) != hipSuccess) return setError(MI355CV_ERROR_UNKNOWN, "%s: execution failed: %s", entry, hipGetErrorString(hipGetLastError()));
     if (ltype == MI355CV_16U) {
         for (int f = 0; f < nframes; f++)
-            if (hostN[f] > 65535) return mi355::declined(__func__, __LINE__, "ltype CV_16U and a frame has more than 65535 components (N - 1 > 65535)");
+            if (hostN[f] > 65535) return MI355_DECLINED("ltype CV_16U and a frame has more than 65535 components (N - 1 > 65535)");
         launchWrite<unsigned short>(s, order, w, h, nframes, dl, dls, lframe, st);
     }
     for (int f = 0; f < nframes; f++) nlabels[f] = (int)hostN[f] + 1;
@@ -441,13 +441,13 @@ int runCCL(const char* entry, const uchar* src, size_t sstep, size_t sframe, int
 
 int statsArgs(const void* labels, int w, int h, int ltype, int nframes, const int* nlabels, int maxLabels, const void* stats)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!labels || !stats || !nlabels || nframes < 1) return mi355::declined(__func__, __LINE__, "!labels || !stats || !nlabels || nframes < 1");
-    if (ltype != MI355CV_32S && ltype != MI355CV_16U) return mi355::declined(__func__, __LINE__, "ltype is not CV_32S or CV_16U");
-    if (w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM) return mi355::declined(__func__, __LINE__, "w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM");
-    if (nframes > 65535) return mi355::declined(__func__, __LINE__, "nframes > 65535");
-    for (int f = 0; f < nframes; f++) if (nlabels[f] < 1) return mi355::declined(__func__, __LINE__, "nlabels < 1");
-    for (int f = 0; f < nframes; f++) if (nlabels[f] > maxLabels) return mi355::declined(__func__, __LINE__, "nlabels > max_labels");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!labels || !stats || !nlabels || nframes < 1);
+    if (ltype != MI355CV_32S && ltype != MI355CV_16U) return MI355_DECLINED("ltype is not CV_32S or CV_16U");
+    MI355_DECLINE_IF(w <= 0 || h <= 0 || w > lim::CCL_MAX_DIM || h > lim::CCL_MAX_DIM);
+    MI355_DECLINE_IF(nframes > 65535);
+    for (int f = 0; f < nframes; f++) if (nlabels[f] < 1) return MI355_DECLINED("nlabels < 1");
+    for (int f = 0; f < nframes; f++) if (nlabels[f] > maxLabels) return MI355_DECLINED("nlabels > max_labels");
     return 0;
 }
 
@@ -456,29 +456,29 @@ int runStats(const char* entry, const uchar* labels, size_t lstep, size_t lframe
 {
     if (const int rc = statsArgs(labels, w, h, ltype, nframes, nlabels, maxLabels, stats)) return rc;
     Stager stg;
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     if (batch && (!isDevicePtr(labels) || !isDevicePtr(stats) || (cent && !isDevicePtr(cent))))
-        return mi355::declined(__func__, __LINE__, "labels, stats and centroids of a batch must be device-resident (host-resident frames are not served)");
-    if (hostImageTooSmall(labels, (size_t)w * h, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(labels, (size_t)w * h, minPixels(HOST_HEAVY))");
+        return MI355_DECLINED("labels, stats and centroids of a batch must be device-resident (host-resident frames are not served)");
+    MI355_DECLINE_IF(hostImageTooSmall(labels, (size_t)w * h, minPixels(HOST_HEAVY)));
     const size_t e = depthBytes(ltype);
     const size_t lspan = (size_t)(nframes - 1) * lframe + (size_t)(h - 1) * lstep + w * e;
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(maxLabels - 1) * sstep + 20, cspan = (size_t)(nframes - 1) * cframe + (size_t)(maxLabels - 1) * cstep + 16;
     if (overlapOnDevice(labels, lspan, stats, sspan) || (cent && (overlapOnDevice(labels, lspan, cent, cspan) || overlapOnDevice(stats, sspan, cent, cspan))))
-        return mi355::declined(__func__, __LINE__, "labels, stats and centroids overlap on the device");
+        return MI355_DECLINED("labels, stats and centroids overlap on the device");
     size_t dls = lstep, dss = sstep, dcs = cstep;
     const uchar* dl = labels; uchar* dst = stats; uchar* dc = cent;
     if (!batch) {
         // outputs live where the label image lives
         if (isDevicePtr(labels) != isDevicePtr(stats) || (cent && isDevicePtr(labels) != isDevicePtr(cent)))
-            return mi355::declined(__func__, __LINE__, "stats and centroids must live where labels lives (all on the device or all on the host)");
+            return MI355_DECLINED("stats and centroids must live where labels lives (all on the device or all on the host)");
         dl = stg.in(labels, lstep, w * e, h, &dls);
         dst = stg.out(stats, sstep, 20, maxLabels, &dss);
         if (cent) dc = stg.out(cent, cstep, 16, maxLabels, &dcs);
-        if (!dl || !dst || (cent && !dc)) return mi355::declined(__func__, __LINE__, "!dl || !dst || (cent && !dc)");
+        MI355_DECLINE_IF(!dl || !dst || (cent && !dc));
     }
     ccl::Acc* acc = (ccl::Acc*)stg.scratch(sizeof(ccl::Acc) * (size_t)maxLabels * nframes);
     const int* dn = (const int*)stg.param(nlabels, (size_t)nframes * sizeof(int));
-    if (!acc || !dn) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!acc || !dn) return MI355_DECLINED("no scratch");
     hipStream_t st = stream();
     const dim3 lgrid(divUp(maxLabels, 256), nframes);
     hipLaunchKernelGGL(k_ccl_stats_init, lgrid, dim3(256), 0, st, acc, maxLabels);

@@ -383,18 +383,18 @@ MI355CV_API int mi355cv_clahe(const uchar* src_data, size_t src_step, uchar* dst
 {
     mi355::EntryGuard entry_(__func__);
     clahe::Plan p;
-    if (disabled() || !src_data || !dst_data) return mi355::declined(__func__, __LINE__, "disabled() || !src_data || !dst_data");
-    if (depth != MI355CV_8U && depth != MI355CV_16U) return mi355::declined(__func__, __LINE__, "depth != MI355CV_8U && depth != MI355CV_16U");
+    MI355_DECLINE_IF(disabled() || !src_data || !dst_data);
+    MI355_DECLINE_IF(depth != MI355CV_8U && depth != MI355CV_16U);
     if (!claheArgs(width, height, depth, margin_right, margin_bottom, clipLimit, tilesX, tilesY, p))
-        return mi355::declined(__func__, __LINE__, "width <= 0 || height <= 0 || tilesX <= 0 || tilesY <= 0 || margins < 0 || tile area beyond int");
+        return MI355_DECLINED("width <= 0 || height <= 0 || tilesX <= 0 || tilesY <= 0 || margins < 0 || tile area beyond int");
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
     const int e = depth == MI355CV_8U ? 1 : 2;
     size_t dss, dds;
     const uchar* ds = stg.in(src_data, src_step, (size_t)p.readW * e, p.readH, &dss);      // the parent margins the padding takes in travel with the image
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * e, height, &dds);
-    if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
+    MI355_DECLINE_IF(!ds || !dd);
     const int rc = claheFrames(stg, "mi355cv_clahe", ds, dss, 0, dd, dds, 0, 1, width, height, depth, p);
     if (rc != MI355CV_OK) return rc;
     return stg.finish("clahe");
@@ -406,9 +406,9 @@ MI355CV_API int mi355cv_claheBatch(const uchar* src_data, size_t src_step, size_
 {
     mi355::EntryGuard entry_(__func__);
     clahe::Plan p;
-    if (disabled() || !src_data || !dst_data || nframes < 1) return mi355::declined(__func__, __LINE__, "disabled() || !src_data || !dst_data || nframes < 1");
+    MI355_DECLINE_IF(disabled() || !src_data || !dst_data || nframes < 1);
     if (!claheArgs(width, height, depth, 0, 0, clipLimit, tilesX, tilesY, p))
-        return mi355::declined(__func__, __LINE__, "depth not 8U / 16U || width <= 0 || height <= 0 || tilesX <= 0 || tilesY <= 0 || tile area beyond int");
+        return MI355_DECLINED("depth not 8U / 16U || width <= 0 || height <= 0 || tilesX <= 0 || tilesY <= 0 || tile area beyond int");
     const size_t rowBytes = (size_t)width * (depth == MI355CV_8U ? 1 : 2);
     if (hostBatchEligible(src_data, dst_data, nframes)) {                                       // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, rowBytes, height, dst_data, dst_step, dst_frame_stride, rowBytes, height, nframes};

@@ -368,14 +368,14 @@ void launchPyrDown(const uchar* ds, size_t dss, size_t sframe, int sw, int sh, u
 int runPyrDown(const char* entry, const uchar* src, size_t sstep, size_t sframe, int sw, int sh, uchar* dst, size_t dstep, size_t dframe,
                int dw, int dh, int nframes, int depth, int cn, int mL, int mT, int mR, int mB, int border)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
+    MI355_DECLINE_IF(disabled());
     border &= ~MI355CV_BORDER_ISOLATED;
-    if (border == B_CONSTANT || border < 0 || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border == B_CONSTANT || border < 0 || border > B_REFLECT_101");   // pyramids.cpp:1352 forbids CONSTANT
-    if (!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4) return mi355::declined(__func__, __LINE__, "!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4");
-    if (sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || abs(dw * 2 - sw) > 2 || abs(dh * 2 - sh) > 2) return mi355::declined(__func__, __LINE__, "sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || abs(dw * 2 - sw) > 2 || abs(dh * 2 - sh) > 2");
+    MI355_DECLINE_IF(border == B_CONSTANT || border < 0 || border > B_REFLECT_101);   // pyramids.cpp:1352 forbids CONSTANT
+    MI355_DECLINE_IF(!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4);
+    MI355_DECLINE_IF(sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0 || abs(dw * 2 - sw) > 2 || abs(dh * 2 - sh) > 2);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)sw * sh, minPixels())) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)sw * sh, minPixels())");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)sw * sh, minPixels()));
     const int e = depth == D8U ? 1 : depth == D32F ? 4 : 2;
     size_t dss = sstep, dds = dstep;
     const uchar* ds = src; uchar* dd = dst;
@@ -383,9 +383,9 @@ int runPyrDown(const char* entry, const uchar* src, size_t sstep, size_t sframe,
         const uchar* top = src - (ptrdiff_t)mT * (ptrdiff_t)sstep - (ptrdiff_t)mL * cn * e;
         const uchar* dtop = stg.in(top, sstep, (size_t)(mL + sw + mR) * cn * e, mT + sh + mB, &dss);
         dd = stg.out(dst, dstep, (size_t)dw * cn * e, dh, &dds);
-        if (!dtop || !dd) return mi355::declined(__func__, __LINE__, "!dtop || !dd");
+        MI355_DECLINE_IF(!dtop || !dd);
         ds = dtop + (size_t)mT * dss + (size_t)mL * cn * e;
-    } else if (!isDevicePtr(src) || !isDevicePtr(dst)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(dst)");
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(dst));
     launchPyrDown(ds, dss, sframe, sw, sh, dd, dds, dframe, dw, dh, nframes, depth, cn, mL, mT, mR, mB, border, stream());
     return stg.finish(entry);
 }
@@ -868,8 +868,7 @@ int launchCorner(const uchar* ds, size_t dss, size_t sframe, uchar* dd, size_t d
     std::vector<int> d1, s0x, s0y;
     // Dx = Sobel(1,0): kx = derivative taps, ky = smoothing taps * scale; Dy = Sobel(0,1): kx = smoothing * scale, ky = derivative
     std::vector<int> dxr, dxc, dyr, dyc;
-    if (!derivTaps(1, ksize, scharr, dxr) || !derivTaps(0, ksize, scharr, dxc) || !derivTaps(0, ksize, scharr, dyr) || !derivTaps(1, ksize, scharr, dyc))
-        return mi355::declined(__func__, __LINE__, "!derivTaps(1, ksize, scharr, dxr) || !derivTaps(0, ksize, scharr, dxc) || !derivTaps(0, ksize, scharr, dyr) || !derivTaps(1, ksize, scharr, dyc)");
+    MI355_DECLINE_IF(!derivTaps(1, ksize, scharr, dxr) || !derivTaps(0, ksize, scharr, dxc) || !derivTaps(0, ksize, scharr, dyr) || !derivTaps(1, ksize, scharr, dyc));
     a.dxNRow = (int)dxr.size(); a.dxNCol = (int)dxc.size(); a.dyNRow = (int)dyr.size(); a.dyNCol = (int)dyc.size();
     for (int i = 0; i < a.dxNRow; i++) a.dxRow[i] = (float)dxr[i];
     for (int i = 0; i < a.dxNCol; i++) a.dxCol[i] = (float)((double)dxc[i] * scale);     // `ky *= scale` (dx != 0)
@@ -909,23 +908,23 @@ int launchCorner(const uchar* ds, size_t dss, size_t sframe, uchar* dd, size_t d
 int runCorner(const char* entry, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes,
               int W, int H, int src_type, int blockSize, int ksize, double k, int borderType, bool harris)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
+    MI355_DECLINE_IF(disabled());
     const int sdepth = MI355CV_MAT_DEPTH(src_type);
-    if (MI355CV_MAT_CN(src_type) != 1 || (sdepth != D8U && sdepth != D32F)) return mi355::declined(__func__, __LINE__, "MI355CV_MAT_CN(src_type) != 1 || (sdepth != D8U && sdepth != D32F)");   // corner.cpp:254
+    MI355_DECLINE_IF(MI355CV_MAT_CN(src_type) != 1 || (sdepth != D8U && sdepth != D32F));   // corner.cpp:254
     const int border = borderType & ~MI355CV_BORDER_ISOLATED;
-    if (border == B_WRAP || border < 0 || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border == B_WRAP || border < 0 || border > B_REFLECT_101");          // FilterEngine rejects WRAP
-    if (blockSize < 1 || blockSize > 16 || W <= 0 || H <= 0 || nframes <= 0) return mi355::declined(__func__, __LINE__, "blockSize < 1 || blockSize > 16 || W <= 0 || H <= 0 || nframes <= 0");
-    if (!(ksize == -1 || ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7)) return mi355::declined(__func__, __LINE__, "!(ksize == -1 || ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7)");
+    MI355_DECLINE_IF(border == B_WRAP || border < 0 || border > B_REFLECT_101);          // FilterEngine rejects WRAP
+    MI355_DECLINE_IF(blockSize < 1 || blockSize > 16 || W <= 0 || H <= 0 || nframes <= 0);
+    MI355_DECLINE_IF(!(ksize == -1 || ksize == 1 || ksize == 3 || ksize == 5 || ksize == 7));
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY)));
     size_t dss = sstep, dds = dstep;
     const uchar* ds = src; uchar* dd = dst;
     if (nframes == 1) {
         ds = stg.in(src, sstep, (size_t)W * (sdepth == D8U ? 1 : 4), H, &dss);
         dd = stg.out(dst, dstep, (size_t)W * 4, H, &dds);
-        if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
-    } else if (!isDevicePtr(src) || !isDevicePtr(dst)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(dst)");
+        MI355_DECLINE_IF(!ds || !dd);
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(dst));
     int rc = launchCorner(ds, dss, sframe, dd, dds, dframe, nframes, W, H, sdepth, blockSize, ksize, k, border, harris, stream());
     if (rc != MI355CV_OK) return rc;
     return stg.finish(entry);
@@ -1033,7 +1032,7 @@ MI355CV_API int mi355cv_buildPyramid(const uchar* src_data, size_t src_step, int
                                      uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (!dst_data || !dst_step || maxlevel < 0) return mi355::declined(__func__, __LINE__, "!dst_data || !dst_step || maxlevel < 0");
+    MI355_DECLINE_IF(!dst_data || !dst_step || maxlevel < 0);
     const uchar* s = src_data; size_t ss = src_step; int w = width, h = height;
     for (int l = 0; l < maxlevel; l++) {
         const int dw = (w + 1) / 2, dh = (h + 1) / 2;
@@ -1052,10 +1051,10 @@ MI355CV_API int mi355cv_buildPyramidBatch(const uchar* src_data, size_t src_step
                                           int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || !src_data || !dst_data || !dst_step || !dst_frame_stride || maxlevel < 1 || maxlevel > 30 || nframes < 1) return mi355::declined(__func__, __LINE__, "disabled() || !src_data || !dst_data || !dst_step || !dst_frame_stride || maxlevel < 1 || maxlevel > 30 || nframes < 1");
+    MI355_DECLINE_IF(disabled() || !src_data || !dst_data || !dst_step || !dst_frame_stride || maxlevel < 1 || maxlevel > 30 || nframes < 1);
     int border = border_type & ~MI355CV_BORDER_ISOLATED;
-    if (border == B_CONSTANT || border < 0 || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border == B_CONSTANT || border < 0 || border > B_REFLECT_101");
-    if (!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4 || width <= 0 || height <= 0) return mi355::declined(__func__, __LINE__, "!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4 || width <= 0 || height <= 0");
+    MI355_DECLINE_IF(border == B_CONSTANT || border < 0 || border > B_REFLECT_101);
+    MI355_DECLINE_IF(!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4 || width <= 0 || height <= 0);
     // every frame and every level in host memory: chunks of frames cross PCIe through two sets of device buffers, the upload of
     // chunk i + 1 under the kernels and the downloads of chunk i; the chunk itself is this entry on device pointers
     bool allHost = hostBatchEligible(src_data, dst_data[0], nframes) && maxlevel <= HOST_BATCH_MAX_OUT;
@@ -1070,7 +1069,7 @@ MI355CV_API int mi355cv_buildPyramidBatch(const uchar* src_data, size_t src_step
             return mi355cv_buildPyramidBatch(s, ss, sf, width, height, depth, cn, d, ds, df, maxlevel, nf, border_type); });
     }
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     if (!isDevicePtr(src_data)) return setError(MI355CV_NOT_IMPLEMENTED, "buildPyramidBatch: frames and levels all in device memory, or all in host memory");
     for (int l = 0; l < maxlevel; l++) if (!isDevicePtr(dst_data[l])) return setError(MI355CV_NOT_IMPLEMENTED, "buildPyramidBatch: frames and levels all in device memory, or all in host memory");
     const uchar* s = src_data; size_t ss = src_step, sf = nframes == 1 ? 0 : src_frame_stride; int w = width, h = height;

@@ -228,17 +228,17 @@ void launchDemosaic(const uchar* s, size_t ss, size_t sf, int w, int h, uchar* d
 // the refusals that need no device; 0 when the arguments are served
 int demosaicArgs(const void* src, size_t sstep, size_t sframe, const void* dst, size_t dstep, size_t dframe, int w, int h, int nframes, int depth, int dcn, int pattern)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src || !dst || nframes < 1) return mi355::declined(__func__, __LINE__, "!src || !dst || nframes < 1");
-    if (!(depth == D8U || depth == D16U)) return mi355::declined(__func__, __LINE__, "!(depth == D8U || depth == D16U)");
-    if (!(dcn == 1 || dcn == 3 || dcn == 4)) return mi355::declined(__func__, __LINE__, "!(dcn == 1 || dcn == 3 || dcn == 4)");
-    if (pattern < 0 || pattern > 3) return mi355::declined(__func__, __LINE__, "pattern < 0 || pattern > 3");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src || !dst || nframes < 1);
+    MI355_DECLINE_IF(!(depth == D8U || depth == D16U));
+    MI355_DECLINE_IF(!(dcn == 1 || dcn == 3 || dcn == 4));
+    MI355_DECLINE_IF(pattern < 0 || pattern > 3);
     // below 3 x 3 there is no interior pixel (the reference fills such a destination with zeros): left to it
-    if (w < 3 || h < 3) return mi355::declined(__func__, __LINE__, "w < 3 || h < 3");
-    if (w > lim::DEMOSAIC_MAX_DIM || h > lim::DEMOSAIC_MAX_DIM) return mi355::declined(__func__, __LINE__, "w > lim::DEMOSAIC_MAX_DIM || h > lim::DEMOSAIC_MAX_DIM");
+    MI355_DECLINE_IF(w < 3 || h < 3);
+    MI355_DECLINE_IF(w > lim::DEMOSAIC_MAX_DIM || h > lim::DEMOSAIC_MAX_DIM);
     const size_t e = depthBytes(depth);
-    if (sstep < (size_t)w * e || dstep < (size_t)w * dcn * e) return mi355::declined(__func__, __LINE__, "sstep < w * e || dstep < w * dcn * e");
-    if (((uintptr_t)src | sstep | sframe | (uintptr_t)dst | dstep | dframe) & (e - 1)) return mi355::declined(__func__, __LINE__, "pointer, pitch or frame stride not a multiple of the element size");
+    MI355_DECLINE_IF(sstep < (size_t)w * e || dstep < (size_t)w * dcn * e);
+    if (((uintptr_t)src | sstep | sframe | (uintptr_t)dst | dstep | dframe) & (e - 1)) return MI355_DECLINED("pointer, pitch or frame stride not a multiple of the element size");
     return 0;
 }
 
@@ -246,18 +246,18 @@ int runDemosaic(const char* entry, const uchar* src, size_t sstep, size_t sframe
 {
     if (const int rc = demosaicArgs(src, sstep, sframe, dst, dstep, dframe, w, h, nframes, depth, dcn, pattern)) return rc;
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)w * h, minPixels())) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels())");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)w * h, minPixels()));
     const size_t e = depthBytes(depth);
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(h - 1) * sstep + w * e, dspan = (size_t)(nframes - 1) * dframe + (size_t)(h - 1) * dstep + w * dcn * e;
-    if (overlapOnDevice(src, sspan, dst, dspan)) return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, dst, dspan)");
+    MI355_DECLINE_IF(overlapOnDevice(src, sspan, dst, dspan));
     size_t dss = sstep, dds = dstep;
     const uchar* ds = src; uchar* dd = dst;
     if (nframes == 1) {
         ds = stg.in(src, sstep, w * e, h, &dss);
         dd = stg.out(dst, dstep, w * dcn * e, h, &dds);
-        if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
-    } else if (!isDevicePtr(src) || !isDevicePtr(dst)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(dst)");
+        MI355_DECLINE_IF(!ds || !dd);
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(dst));
     launchDemosaic(ds, dss, sframe, w, h, dd, dds, dframe, nframes, depth, dcn, pattern, stream());
     MI355_CHECK_LAUNCH(entry);
     return stg.finish(entry);

@@ -113,16 +113,16 @@ bool launchDist(Stager& stg, const uchar* ds, size_t dss, size_t sframe, int w, 
 // the refusals that need no device; 0 when the arguments are served
 int distArgs(const void* src, int w, int h, const void* dst, int nframes, int distanceType, int maskSize, int dstDepth)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src || !dst || nframes < 1) return mi355::declined(__func__, __LINE__, "!src || !dst || nframes < 1");
-    if (distanceType != dt::L1 && distanceType != dt::L2 && distanceType != dt::C) return mi355::declined(__func__, __LINE__, "distanceType is not DIST_L1, DIST_L2 or DIST_C");
-    if (maskSize != 0 && maskSize != 3 && maskSize != 5) return mi355::declined(__func__, __LINE__, "maskSize is not 0, 3 or 5");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src || !dst || nframes < 1);
+    if (distanceType != dt::L1 && distanceType != dt::L2 && distanceType != dt::C) return MI355_DECLINED("distanceType is not DIST_L1, DIST_L2 or DIST_C");
+    if (maskSize != 0 && maskSize != 3 && maskSize != 5) return MI355_DECLINED("maskSize is not 0, 3 or 5");
     // DIST_L2 with a 3 x 3 or 5 x 5 mask is the reference's chamfer approximation, a raster-sequential recurrence: left to it
-    if (distanceType == dt::L2 && maskSize != 0) return mi355::declined(__func__, __LINE__, "DIST_L2 with maskSize != DIST_MASK_PRECISE");
-    if (dstDepth != MI355CV_32F && dstDepth != MI355CV_8U) return mi355::declined(__func__, __LINE__, "dstDepth is not CV_32F or CV_8U");
-    if (dstDepth == MI355CV_8U && distanceType != dt::L1) return mi355::declined(__func__, __LINE__, "CV_8U output without DIST_L1");       // the reference asserts it
+    if (distanceType == dt::L2 && maskSize != 0) return MI355_DECLINED("DIST_L2 with maskSize != DIST_MASK_PRECISE");
+    if (dstDepth != MI355CV_32F && dstDepth != MI355CV_8U) return MI355_DECLINED("dstDepth is not CV_32F or CV_8U");
+    if (dstDepth == MI355CV_8U && distanceType != dt::L1) return MI355_DECLINED("CV_8U output without DIST_L1");       // the reference asserts it
     // squared distances are 32-bit and g is 16-bit in the kernels (disttransform_math.h)
-    if (w <= 0 || h <= 0 || w > lim::DISTTRANSFORM_MAX_DIM || h > lim::DISTTRANSFORM_MAX_DIM) return mi355::declined(__func__, __LINE__, "w <= 0 || h <= 0 || w > lim::DISTTRANSFORM_MAX_DIM || h > lim::DISTTRANSFORM_MAX_DIM");
+    MI355_DECLINE_IF(w <= 0 || h <= 0 || w > lim::DISTTRANSFORM_MAX_DIM || h > lim::DISTTRANSFORM_MAX_DIM);
     return 0;
 }
 
@@ -131,19 +131,19 @@ int runDist(const char* entry, const uchar* src, size_t sstep, size_t sframe, in
 {
     if (const int rc = distArgs(src, w, h, dst, nframes, distanceType, maskSize, dstDepth)) return rc;
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY)));
     const size_t e = depthBytes(dstDepth);
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(h - 1) * sstep + w, dspan = (size_t)(nframes - 1) * dframe + (size_t)(h - 1) * dstep + w * e;
-    if (overlapOnDevice(src, sspan, dst, dspan)) return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, dst, dspan)");
+    MI355_DECLINE_IF(overlapOnDevice(src, sspan, dst, dspan));
     size_t dss = sstep, dds = dstep;
     const uchar* ds = src; uchar* dd = dst;
     if (nframes == 1) {
         ds = stg.in(src, sstep, w, h, &dss);
         dd = stg.out(dst, dstep, w * e, h, &dds);
-        if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
-    } else if (!isDevicePtr(src) || !isDevicePtr(dst)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(dst)");
-    if (!launchDist(stg, ds, dss, sframe, w, h, dd, dds, dframe, nframes, distanceType, dstDepth, stream())) return mi355::declined(__func__, __LINE__, "no scratch");
+        MI355_DECLINE_IF(!ds || !dd);
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(dst));
+    if (!launchDist(stg, ds, dss, sframe, w, h, dd, dds, dframe, nframes, distanceType, dstDepth, stream())) return MI355_DECLINED("no scratch");
     MI355_CHECK_LAUNCH(entry);
     return stg.finish(entry);
 }

@@ -930,13 +930,13 @@ int sepInit(FilterCtx& c, int stype, int dtype, const std::vector<double>& kx, c
     const int nx = (int)kx.size(), ny = (int)ky.size();
     const bool large = nx > 33 || ny > 33;
     if (nx < 1 || ny < 1 || nx > lim::SEP_MAX_TAPS || ny > lim::SEP_MAX_TAPS || (c.wide && (nx > lim::SEP_MAX_TAPS_64F || ny > lim::SEP_MAX_TAPS_64F)))
-        return mi355::declined(__func__, __LINE__, "nx < 1 || ny < 1 || nx or ny > lim::SEP_MAX_TAPS (lim::SEP_MAX_TAPS_64F into CV_64F)");
-    if (large && c.cn > 4) return mi355::declined(__func__, __LINE__, "more than 33 taps on more than 4 channels (seplong.hip covers 1-4)");
+        return MI355_DECLINED("nx < 1 || ny < 1 || nx or ny > lim::SEP_MAX_TAPS (lim::SEP_MAX_TAPS_64F into CV_64F)");
+    if (large && c.cn > 4) return MI355_DECLINED("more than 33 taps on more than 4 channels (seplong.hip covers 1-4)");
     if (ax < 0) ax = nx / 2;
     if (ay < 0) ay = ny / 2;
-    if (ax >= nx || ay >= ny) return mi355::declined(__func__, __LINE__, "ax >= nx || ay >= ny");
+    MI355_DECLINE_IF(ax >= nx || ay >= ny);
     c.border = border & ~MI355CV_BORDER_ISOLATED;
-    if (c.border < 0 || c.border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "c.border < 0 || c.border > B_REFLECT_101");
+    MI355_DECLINE_IF(c.border < 0 || c.border > B_REFLECT_101);
     c.ax = ax; c.ay = ay; c.lnx = nx; c.lny = ny; c.big = large;
     SepParams& p = c.sp;
     memset(&p, 0, sizeof p);
@@ -992,10 +992,10 @@ bool sepLong(Stager& stg, const FilterCtx& c, const uchar* src, size_t sstep, si
 int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep, uchar* dst, size_t dstep,
            int W, int H, int fullW, int fullH, int offX, int offY)
 {
-    if (disabled() || W <= 0 || H <= 0) return mi355::declined(__func__, __LINE__, "disabled() || W <= 0 || H <= 0");
+    MI355_DECLINE_IF(disabled() || W <= 0 || H <= 0);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY)));
     const int se = depthSize(c.sdepth), de = depthSize(c.ddepth);
     // stage the whole parent region so that non-isolated borders can read real neighbours
     const uchar* top = src - (ptrdiff_t)offY * (ptrdiff_t)sstep - (ptrdiff_t)offX * c.cn * se;
@@ -1004,7 +1004,7 @@ int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep
     size_t dss, dds;
     const uchar* dtop = stg.in(top, sstep, (size_t)fullW * c.cn * se, fullH, &dss);
     uchar* dd = stg.out(dst, dstep, (size_t)W * c.cn * de, H, &dds);
-    if (!dtop || !dd) return mi355::declined(__func__, __LINE__, "!dtop || !dd");
+    MI355_DECLINE_IF(!dtop || !dd);
     const uchar* ds = dtop + (size_t)offY * dss + (size_t)offX * c.cn * se;
     if (c.wide) {
         hipLaunchKernelGGL(k_sepfilter_generic64, dim3(divUp(W * c.cn, 64), divUp(H, 4)), dim3(256), 0, stream(), ds, dss, dd, dds, W, H, c.cn, c.sdepth,
@@ -1013,7 +1013,7 @@ int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep
         return stg.finish(entry);
     }
     if (c.big) {
-        if (!sepLong(stg, c, ds, dss, 0, dd, dds, 0, 1, W, H, fullW, fullH, offX, offY)) return mi355::declined(__func__, __LINE__, "seplongRun refused a kernel beyond 33 taps");
+        if (!sepLong(stg, c, ds, dss, 0, dd, dds, 0, 1, W, H, fullW, fullH, offX, offY)) return MI355_DECLINED("seplongRun refused a kernel beyond 33 taps");
         return stg.finish(entry);
     }
     const SepParams& p = c.sp;
@@ -1050,9 +1050,9 @@ int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep
 // where they apply, the generic kernel frame by frame otherwise (all in stream order, one synchronisation at most)
 int sepRunBatch(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes, int W, int H)
 {
-    if (disabled() || W <= 0 || H <= 0 || nframes < 1) return mi355::declined(__func__, __LINE__, "disabled() || W <= 0 || H <= 0 || nframes < 1");
+    MI355_DECLINE_IF(disabled() || W <= 0 || H <= 0 || nframes < 1);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     if (!isDevicePtr(src) || !isDevicePtr(dst)) return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
     const int se = depthSize(c.sdepth), de = depthSize(c.ddepth);
     // one check for every path below, the CV_64F and long-kernel ones included (they used to launch before it)
@@ -1066,7 +1066,7 @@ int sepRunBatch(const char* entry, const FilterCtx& c, const uchar* src, size_t 
         return stg.finish(entry);
     }
     if (c.big) {                                 // 34 .. lim::SEP_MAX_TAPS taps: the LDS-ring kernel, frames along grid z
-        if (!sepLong(stg, c, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, W, H, 0, 0)) return mi355::declined(__func__, __LINE__, "seplongRun refused a kernel beyond 33 taps");
+        if (!sepLong(stg, c, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, W, H, 0, 0)) return MI355_DECLINED("seplongRun refused a kernel beyond 33 taps");
         return stg.finish(entry);
     }
     if (nframes == 1) { sframe = 0; dframe = 0; }
@@ -1127,9 +1127,9 @@ int derivRun(const char* entry, const uchar* src, size_t sstep, uchar* dst, size
              int cn, int mL, int mT, int mR, int mB, int dx, int dy, int ksize, bool scharr, double scale, double delta, int border,
              int nframes = 0, size_t sframe = 0, size_t dframe = 0)
 {
-    if (dx < 0 || dy < 0 || (scharr ? dx + dy != 1 : dx + dy <= 0) || inPlaceOnDevice(src, dst)) return mi355::declined(__func__, __LINE__, "dx < 0 || dy < 0 || (scharr ? dx + dy != 1 : dx + dy <= 0) || inPlaceOnDevice(src, dst)");
+    MI355_DECLINE_IF(dx < 0 || dy < 0 || (scharr ? dx + dy != 1 : dx + dy <= 0) || inPlaceOnDevice(src, dst));
     std::vector<int> ix, iy;
-    if (!derivKernel(dx, ksize, scharr, ix) || !derivKernel(dy, ksize, scharr, iy)) return mi355::declined(__func__, __LINE__, "!derivKernel(dx, ksize, scharr, ix) || !derivKernel(dy, ksize, scharr, iy)");
+    MI355_DECLINE_IF(!derivKernel(dx, ksize, scharr, ix) || !derivKernel(dy, ksize, scharr, iy));
     // ktype = max(CV_32F, ddepth, sdepth): `kx *= scale` is evaluated in double and stored back in the kernel's type (deriv.cpp:421, :432-439) -- float unless
     // the source or the destination is CV_64F
     const bool wideK = MI355CV_MAT_DEPTH(sdepth) == D64F || MI355CV_MAT_DEPTH(ddepth) == D64F;
@@ -1159,11 +1159,10 @@ MI355CV_API int mi355cv_filterInit(cvhalFilter2D** context, uchar* kernel_data, 
     // allowInplace (src_data == dst_data at the call site, filter.dispatch.cpp:1176): a host image goes through separate device buffers, so it is served;
     // a device image filtered in place is refused by mi355cv_filter itself (overlapOnDevice), which the caller treats as "not replaced" (:1177-1183)
     (void)max_width; (void)max_height; (void)allowSubmatrix; (void)allowInplace;
-    if (!context || !kernel_data || disabled()) return mi355::declined(__func__, __LINE__, "!context || !kernel_data || disabled()");
-    if (MI355CV_MAT_CN(kernel_type) != 1 || kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024)
-        return mi355::declined(__func__, __LINE__, "MI355CV_MAT_CN(kernel_type) != 1 || kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024");
+    MI355_DECLINE_IF(!context || !kernel_data || disabled());
+    MI355_DECLINE_IF(MI355CV_MAT_CN(kernel_type) != 1 || kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024);
     FilterCtx* c = new (std::nothrow) FilterCtx();
-    if (!c) return mi355::declined(__func__, __LINE__, "!c");
+    MI355_DECLINE_IF(!c);
     c->kind = 1;
     c->sdepth = MI355CV_MAT_DEPTH(src_type); c->ddepth = MI355CV_MAT_DEPTH(dst_type); c->cn = MI355CV_MAT_CN(src_type);
     c->border = borderType & ~MI355CV_BORDER_ISOLATED;
@@ -1265,7 +1264,7 @@ MI355CV_API int mi355cv_filterBatch(cvhalFilter2D* context, const uchar* src_dat
 {
     mi355::EntryGuard entry_(__func__);
     FilterCtx* c = reinterpret_cast<FilterCtx*>(context);
-    if (!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled()) return mi355::declined(__func__, __LINE__, "!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled()");
+    MI355_DECLINE_IF(!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled());
     if (c->wide) return setError(MI355CV_NOT_IMPLEMENTED, "filterBatch: CV_64F destinations go frame by frame through mi355cv_filter");
     if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * c->cn * depthBytes(c->sdepth), height, dst_data, dst_step, dst_frame_stride, (size_t)width * c->cn * depthBytes(c->ddepth), height, nframes};
@@ -1273,12 +1272,12 @@ MI355CV_API int mi355cv_filterBatch(cvhalFilter2D* context, const uchar* src_dat
             return mi355cv_filterBatch(context, s, ss, sf, d, ds, df, nf, width, height); });
     }
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data)) return mi355::declined(__func__, __LINE__, "!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data)");
+    MI355_DECLINE_IF(!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data));
     if (nframes == 1) { src_frame_stride = 0; dst_frame_stride = 0; }
     if (!tryFilterRoll(c, src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, stream()) &&
         !tryFilterTile(stg, c, src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, width, height, 0, 0, stream())) {
         Tap2D* dt = (Tap2D*)stg.param(c->taps.data(), c->taps.size() * sizeof(Tap2D));
-        if (!dt) return mi355::declined(__func__, __LINE__, "!dt");
+        MI355_DECLINE_IF(!dt);
         const int se = depthSize(c->sdepth), de = depthSize(c->ddepth); (void)se; (void)de;
         for (int f = 0; f < nframes; f++) {
             dim3 grid(divUp(width * c->cn, 64), divUp(height, 4));
@@ -1299,14 +1298,14 @@ MI355CV_API int mi355cv_cvtBGRtoGrayFilterBatch(cvhalFilter2D* context, const uc
 {
     mi355::EntryGuard entry_(__func__);
     FilterCtx* c = reinterpret_cast<FilterCtx*>(context);
-    if (!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled() || (scn != 3 && scn != 4)) return mi355::declined(__func__, __LINE__, "!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled() || (scn != 3 && scn != 4)");
+    MI355_DECLINE_IF(!c || c->kind != 1 || width <= 0 || height <= 0 || nframes <= 0 || disabled() || (scn != 3 && scn != 4));
     if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * scn, height, dst_data, dst_step, dst_frame_stride, (size_t)width, height, nframes};
         return runHostBatch("cvtBGRtoGrayFilterBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_cvtBGRtoGrayFilterBatch(context, s, ss, sf, d, ds, df, nf, width, height, scn, swapBlue); });
     }
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data)) return mi355::declined(__func__, __LINE__, "!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data)");
+    MI355_DECLINE_IF(!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data));
     const int K = c->kw;
     if (c->cn != 1 || c->sdepth != D8U || c->ddepth != D8U || c->kw != c->kh || (K != 3 && K != 5) || c->ax != K / 2 || c->ay != K / 2)
         return setError(MI355CV_NOT_IMPLEMENTED, "cvtBGRtoGrayFilterBatch: needs a centred 3x3 / 5x5 CV_8UC1 filter context");
@@ -1331,10 +1330,10 @@ MI355CV_API int mi355cv_filter(cvhalFilter2D* context, uchar* src_data, size_t s
 {
     mi355::EntryGuard entry_(__func__);
     FilterCtx* c = reinterpret_cast<FilterCtx*>(context);
-    if (!c || c->kind != 1 || width <= 0 || height <= 0) return mi355::declined(__func__, __LINE__, "!c || c->kind != 1 || width <= 0 || height <= 0");
+    MI355_DECLINE_IF(!c || c->kind != 1 || width <= 0 || height <= 0);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
     const int se = depthSize(c->sdepth), de = depthSize(c->ddepth);
     // hal::filter2D tries the hook before its own DFT path (filter.dispatch.cpp:1436-1470): for a whole image and a kernel of >= 130 taps
     // (8U -> 8U / 16S, 32F -> 32F; >= 50 otherwise) the CPU result comes from float FFTs (dftFilter2D :1274-1340), which a direct sum does
@@ -1360,11 +1359,11 @@ MI355CV_API int mi355cv_filter(cvhalFilter2D* context, uchar* src_data, size_t s
     const uchar* dtop = stg.in(top, src_step, (size_t)full_width * c->cn * se, full_height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * c->cn * de, height, &dds);
     Tap2D* dt = (Tap2D*)stg.param(c->taps.data(), c->taps.size() * sizeof(Tap2D));
-    if (!dtop || !dd || !dt) return mi355::declined(__func__, __LINE__, "!dtop || !dd || !dt");
+    MI355_DECLINE_IF(!dtop || !dd || !dt);
     const uchar* ds = dtop + (size_t)offset_y * dss + (size_t)offset_x * c->cn * se;
     if (c->wide) {
         Tap2D64* dt64 = (Tap2D64*)stg.param(c->taps64.data(), c->taps64.size() * sizeof(Tap2D64));
-        if (!dt64) return mi355::declined(__func__, __LINE__, "!dt64");
+        MI355_DECLINE_IF(!dt64);
         hipLaunchKernelGGL(k_filter2d_generic64, dim3(divUp(width * c->cn, 64), divUp(height, 4)), dim3(256), 0, stream(), ds, dss, dd, dds, width, height, c->cn, c->sdepth,
                            full_width, full_height, offset_x, offset_y, dt64, (int)c->taps64.size(), c->ax, c->ay, c->delta64, c->border);
         noteKernel("k_filter2d_generic64 (depth %d -> CV_64F, %zu taps)", c->sdepth, c->taps64.size());
@@ -1393,13 +1392,13 @@ MI355CV_API int mi355cv_sepFilterInit(cvhalFilter2D** context, int src_type, int
         int anchor_x, int anchor_y, double delta, int borderType)
 {
     mi355::EntryGuard entry_(__func__);
-    if (!context || !kernelx_data || !kernely_data || disabled()) return mi355::declined(__func__, __LINE__, "!context || !kernelx_data || !kernely_data || disabled()");
-    if (MI355CV_MAT_CN(kernel_type) != 1 || kernelx_length < 1 || kernely_length < 1) return mi355::declined(__func__, __LINE__, "MI355CV_MAT_CN(kernel_type) != 1 || kernelx_length < 1 || kernely_length < 1");
+    MI355_DECLINE_IF(!context || !kernelx_data || !kernely_data || disabled());
+    MI355_DECLINE_IF(MI355CV_MAT_CN(kernel_type) != 1 || kernelx_length < 1 || kernely_length < 1);
     std::vector<double> kx(kernelx_length), ky(kernely_length);
     for (int i = 0; i < kernelx_length; i++) kx[i] = kernelAt(kernelx_data, 0, kernel_type, 0, i);
     for (int i = 0; i < kernely_length; i++) ky[i] = kernelAt(kernely_data, 0, kernel_type, 0, i);
     FilterCtx* c = new (std::nothrow) FilterCtx();
-    if (!c) return mi355::declined(__func__, __LINE__, "!c");
+    MI355_DECLINE_IF(!c);
     int rc = sepInit(*c, src_type, dst_type, kx, ky, anchor_x, anchor_y, delta, borderType);
     if (rc != MI355CV_OK) { delete c; return rc; }
     *context = reinterpret_cast<cvhalFilter2D*>(c);
@@ -1411,7 +1410,7 @@ MI355CV_API int mi355cv_sepFilter(cvhalFilter2D* context, uchar* src_data, size_
 {
     mi355::EntryGuard entry_(__func__);
     FilterCtx* c = reinterpret_cast<FilterCtx*>(context);
-    if (!c || c->kind != 2) return mi355::declined(__func__, __LINE__, "!c || c->kind != 2");
+    MI355_DECLINE_IF(!c || c->kind != 2);
     return sepRun("sepFilter", *c, src_data, src_step, dst_data, dst_step, width, height, full_width, full_height, offset_x, offset_y);
 }
 
@@ -1461,7 +1460,7 @@ MI355CV_API int mi355cv_sobelBatch(const uchar* src_data, size_t src_step, size_
         int nframes, int width, int height, int src_depth, int dst_depth, int cn, int dx, int dy, int ksize, double scale, double delta, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (nframes < 1) return mi355::declined(__func__, __LINE__, "nframes < 1");
+    MI355_DECLINE_IF(nframes < 1);
     if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * cn * depthBytes(src_depth), height, dst_data, dst_step, dst_frame_stride, (size_t)width * cn * depthBytes(dst_depth), height, nframes};
         return runHostBatch("sobelBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
@@ -1476,7 +1475,7 @@ MI355CV_API int mi355cv_sepFilterBatch(cvhalFilter2D* context, const uchar* src_
 {
     mi355::EntryGuard entry_(__func__);
     FilterCtx* c = reinterpret_cast<FilterCtx*>(context);
-    if (!c || c->kind != 2 || nframes < 1) return mi355::declined(__func__, __LINE__, "!c || c->kind != 2 || nframes < 1");
+    MI355_DECLINE_IF(!c || c->kind != 2 || nframes < 1);
     if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * c->cn * depthBytes(c->sdepth), height, dst_data, dst_step, dst_frame_stride, (size_t)width * c->cn * depthBytes(c->ddepth), height, nframes};
         return runHostBatch("sepFilterBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
@@ -1494,7 +1493,7 @@ MI355CV_API int mi355cv_boxFilterBatch(const uchar* src_data, size_t src_step, s
         int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (nframes < 1) return mi355::declined(__func__, __LINE__, "nframes < 1");
+    MI355_DECLINE_IF(nframes < 1);
     if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
         const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * cn * depthBytes(src_depth), height, dst_data, dst_step, dst_frame_stride, (size_t)width * cn * depthBytes(dst_depth), height, nframes};
         return runHostBatch("boxFilterBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
@@ -1557,14 +1556,14 @@ static int boxRun(const char* entry, const uchar* src_data, size_t src_step, siz
         int src_depth, int dst_depth, int cn, int margin_left, int margin_top, int margin_right, int margin_bottom,
         size_t ksize_width, size_t ksize_height, int anchor_x, int anchor_y, bool normalize, int border_type)
 {
-    if (disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 512 || inPlaceOnDevice(src_data, dst_data)) return mi355::declined(__func__, __LINE__, "disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 512 || inPlaceOnDevice(src_data, dst_data)");
+    MI355_DECLINE_IF(disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 512 || inPlaceOnDevice(src_data, dst_data));
     // cv::boxFilter hands its `ddepth` argument through as the caller gave it (box_filter.dispatch.cpp:451-474): a caller that passed a TYPE there (CV_8UC2 = 8 --
     // the reference's own Imgproc_Blur test does) arrives with channel bits set; the destination Mat was created from CV_MAKETYPE(ddepth, cn), i.e. from the depth bits
     src_depth = MI355CV_MAT_DEPTH(src_depth); dst_depth = MI355CV_MAT_DEPTH(dst_depth);
     const int kw = (int)ksize_width, kh = (int)ksize_height;
-    if (kw < 1 || kh < 1 || kw > lim::BOX_MAX_KSIZE || kh > lim::BOX_MAX_KSIZE) return mi355::declined(__func__, __LINE__, "kw < 1 || kh < 1 || kw or kh > lim::BOX_MAX_KSIZE");
+    MI355_DECLINE_IF(kw < 1 || kh < 1 || kw > lim::BOX_MAX_KSIZE || kh > lim::BOX_MAX_KSIZE);
     const int border = border_type & ~MI355CV_BORDER_ISOLATED;
-    if (border < 0 || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border < 0 || border > B_REFLECT_101");
+    MI355_DECLINE_IF(border < 0 || border > B_REFLECT_101);
     // integer sources: int sums into any of the destination depths the reference has a ColumnSum<int, T> for (8U -> 16S is what an un-normalised cv::boxFilter of
     // bytes usually asks for); a signed source into an unsigned destination is left to the caller's path
     const bool okDepth = (src_depth == D8U && (dst_depth == D8U || dst_depth == D16U || dst_depth == D16S || dst_depth == D32F)) ||
@@ -1576,7 +1575,7 @@ static int boxRun(const char* entry, const uchar* src_data, size_t src_step, siz
     BoxParams p; memset(&p, 0, sizeof p);
     p.kw = kw; p.kh = kh;
     p.ax = anchor_x < 0 ? kw / 2 : anchor_x; p.ay = anchor_y < 0 ? kh / 2 : anchor_y;
-    if (p.ax >= kw || p.ay >= kh) return mi355::declined(__func__, __LINE__, "p.ax >= kw || p.ay >= kh");
+    MI355_DECLINE_IF(p.ax >= kw || p.ay >= kh);
     p.normalize = normalize ? 1 : 0;
     const int area = kw * kh;
     const double scale = 1.0 / area;
@@ -1595,11 +1594,11 @@ static int boxRun(const char* entry, const uchar* src_data, size_t src_step, siz
     } else {
         p.mode = 1;
         const long long lim = src_depth == D8U ? (1LL << 23) : src_depth == D16U ? (1LL << 15) : (1LL << 16);
-        if (normalize && area > lim) return mi355::declined(__func__, __LINE__, "normalize && area > lim");    // the reference switches to double sums there
+        MI355_DECLINE_IF(normalize && area > lim);    // the reference switches to double sums there
     }
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
     const int se = depthSize(src_depth), de = depthSize(dst_depth);
     const int fullW = margin_left + width + margin_right, fullH = margin_top + height + margin_bottom;
     if (nframes >= 1) {
@@ -1624,7 +1623,7 @@ static int boxRun(const char* entry, const uchar* src_data, size_t src_step, siz
     const uchar* top = src_data - (ptrdiff_t)margin_top * (ptrdiff_t)src_step - (ptrdiff_t)margin_left * cn * se;
     const uchar* dtop = stg.in(top, src_step, (size_t)fullW * cn * se, fullH, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * cn * de, height, &dds);
-    if (!dtop || !dd) return mi355::declined(__func__, __LINE__, "!dtop || !dd");
+    MI355_DECLINE_IF(!dtop || !dd);
     const uchar* ds = dtop + (size_t)margin_top * dss + (size_t)margin_left * cn * se;
     const Roi roiv = {fullW, fullH, margin_left, margin_top};
     const Roi* roi = (fullW != width || fullH != height) ? &roiv : nullptr;       // a submatrix with real pixels around it: the rolling kernels store the window

@@ -129,15 +129,15 @@ inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
 // the refusals that need no device; 0 when the arguments are served
 int houghArgs(const void* src, int w, int h, double rho, double theta, double srn, double stn, double minTheta, double maxTheta, int useEdgeval, Geom* g)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src) return mi355::declined(__func__, __LINE__, "!src");
-    if (srn != 0 || stn != 0) return mi355::declined(__func__, __LINE__, "srn != 0 || stn != 0 (the multi-scale transform)");
-    if (useEdgeval) return mi355::declined(__func__, __LINE__, "use_edgeval");
-    if (w <= 0 || h <= 0 || w > lim::HOUGH_MAX_DIM || h > lim::HOUGH_MAX_DIM) return mi355::declined(__func__, __LINE__, "w <= 0 || h <= 0 || w > lim::HOUGH_MAX_DIM || h > lim::HOUGH_MAX_DIM");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src);
+    if (srn != 0 || stn != 0) return MI355_DECLINED("srn != 0 || stn != 0 (the multi-scale transform)");
+    if (useEdgeval) return MI355_DECLINED("use_edgeval");
+    MI355_DECLINE_IF(w <= 0 || h <= 0 || w > lim::HOUGH_MAX_DIM || h > lim::HOUGH_MAX_DIM);
     const int rc = hough::geometry(w, h, rho, theta, minTheta, maxTheta, g);
-    if (rc == 1) return mi355::declined(__func__, __LINE__, "rho <= 0, theta <= 0 or not 0 <= min_theta < max_theta <= CV_PI");
-    if (rc) return mi355::declined(__func__, __LINE__, "(numangle + 2) * (numrho + 2) > lim::HOUGH_MAX_ACCUM");
-    if (g->numangle > 65535) return mi355::declined(__func__, __LINE__, "numangle > 65535 (k_hough_vote has one grid row per angle)");
+    if (rc == 1) return MI355_DECLINED("rho <= 0, theta <= 0 or not 0 <= min_theta < max_theta <= CV_PI");
+    if (rc) return MI355_DECLINED("(numangle + 2) * (numrho + 2) > lim::HOUGH_MAX_ACCUM");
+    if (g->numangle > 65535) return MI355_DECLINED("numangle > 65535 (k_hough_vote has one grid row per angle)");
     return 0;
 }
 
@@ -206,31 +206,31 @@ int runHough(const char* entry, const uchar* src, size_t sstep, size_t sframe, i
              double rho, double theta, int threshold, double srn, double stn, double minTheta, double maxTheta, int* nlines)
 {
     Geom g;
-    if (!lines || !nlines || nframes < 1) return mi355::declined(__func__, __LINE__, "!lines || !nlines || nframes < 1");
+    MI355_DECLINE_IF(!lines || !nlines || nframes < 1);
     if (const int rc = houghArgs(src, w, h, rho, theta, srn, stn, minTheta, maxTheta, 0, &g)) return rc;
-    if (cn != 2 && cn != 3) return mi355::declined(__func__, __LINE__, "lines_cn is not 2 or 3");
-    if (maxLines < 1) return mi355::declined(__func__, __LINE__, "max_lines < 1");
+    if (cn != 2 && cn != 3) return MI355_DECLINED("lines_cn is not 2 or 3");
+    if (maxLines < 1) return MI355_DECLINED("max_lines < 1");
     const size_t lrow = (size_t)cn * 4;
-    if (nframes > 1 && (lframeBytes % 4 || lframeBytes < lrow * maxLines)) return mi355::declined(__func__, __LINE__, "lines_frame_stride is no multiple of 4 or below max_lines rows");
-    if (nframes > 65535) return mi355::declined(__func__, __LINE__, "nframes > 65535");
+    if (nframes > 1 && (lframeBytes % 4 || lframeBytes < lrow * maxLines)) return MI355_DECLINED("lines_frame_stride is no multiple of 4 or below max_lines rows");
+    MI355_DECLINE_IF(nframes > 65535);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const int skind = ptrKind(src), lkind = ptrKind(lines);
     if (skind == PTR_FOREIGN || lkind == PTR_FOREIGN || skind != lkind)
-        return mi355::declined(__func__, __LINE__, "image and lines must both live on this thread's device or both on the host");
+        return MI355_DECLINED("image and lines must both live on this thread's device or both on the host");
     const bool host = skind == PTR_HOST;
-    if (hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY)));
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(h - 1) * sstep + w, lspan = (size_t)(nframes - 1) * lframeBytes + lrow * maxLines;
-    if (overlapOnDevice(src, sspan, lines, lspan)) return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, lines, lspan)");
+    MI355_DECLINE_IF(overlapOnDevice(src, sspan, lines, lspan));
 
     Scr s;
-    if (!houghScratch(stg, g, w, h, nframes, true, &s)) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!houghScratch(stg, g, w, h, nframes, true, &s)) return MI355_DECLINED("no scratch");
     uint32_t* hostN = (uint32_t*)stg.pinned((size_t)nframes * 8);
     // host-resident frames: dense copies of a group of sources, and the lines of all frames, in HBM
     const size_t hstep = pad256((size_t)w), hl = lrow * maxLines;
     uchar* hsrc = host ? (uchar*)stg.scratch(hstep * h * s.group) : nullptr;
     float* hlines = host ? (float*)stg.scratch(hl * nframes) : nullptr;
-    if (!hostN || (host && (!hsrc || !hlines))) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!hostN || (host && (!hsrc || !hlines))) return MI355_DECLINED("no scratch");
     hipStream_t st = stream();
     for (int f0 = 0; f0 < nframes; f0 += s.group) {
         const int nf = std::min(s.group, nframes - f0);
@@ -304,26 +304,25 @@ MI355CV_API int mi355cv_houghLinesAccum(const uchar* src_data, size_t src_step, 
     mi355::EntryGuard entry_(__func__);
     const char* entry = "houghLinesAccum";
     Geom g;
-    if (!numangle || !numrho) return mi355::declined(__func__, __LINE__, "!numangle || !numrho");
+    MI355_DECLINE_IF(!numangle || !numrho);
     if (const int rc = houghArgs(src_data, width, height, rho, theta, 0, 0, min_theta, max_theta, 0, &g)) return rc;
     const size_t rowBytes = (size_t)(g.numrho + 2) * 4;
     const int rows = g.numangle + 2;
     if (!accum) { *numangle = g.numangle; *numrho = g.numrho; return MI355CV_OK; }        // the geometry alone: no device is touched
-    if (accum_step < rowBytes || accum_step % 4) return mi355::declined(__func__, __LINE__, "accum_step is below (numrho + 2) ints or no multiple of 4");
+    if (accum_step < rowBytes || accum_step % 4) return MI355_DECLINED("accum_step is below (numrho + 2) ints or no multiple of 4");
     Stager stg;
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const int skind = ptrKind(src_data), akind = ptrKind(accum);
     if (skind == PTR_FOREIGN || akind == PTR_FOREIGN || skind != akind)
-        return mi355::declined(__func__, __LINE__, "image and accumulator must both live on this thread's device or both on the host");
+        return MI355_DECLINED("image and accumulator must both live on this thread's device or both on the host");
     const bool host = skind == PTR_HOST;
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_HEAVY))");
-    if (overlapOnDevice(src_data, (size_t)(height - 1) * src_step + width, accum, (size_t)(rows - 1) * accum_step + rowBytes))
-        return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, accum, aspan)");
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
+    MI355_DECLINE_IF(overlapOnDevice(src_data, (size_t)(height - 1) * src_step + width, accum, (size_t)(rows - 1) * accum_step + rowBytes));
     Scr s;
-    if (!houghScratch(stg, g, width, height, 1, false, &s)) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!houghScratch(stg, g, width, height, 1, false, &s)) return MI355_DECLINED("no scratch");
     const size_t hstep = pad256((size_t)width);
     uchar* hsrc = host ? (uchar*)stg.scratch(hstep * height) : nullptr;
-    if (host && !hsrc) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (host && !hsrc) return MI355_DECLINED("no scratch");
     hipStream_t st = stream();
     const uchar* sp = src_data; size_t ss = src_step;
     if (host) {

@@ -225,22 +225,22 @@ extern "C" MI355CV_API int mi355cv_medianBlur(const uchar* src_data, size_t src_
                                               int depth, int cn, int ksize)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || width <= 0 || height <= 0) return mi355::declined(__func__, __LINE__, "disabled() || width <= 0 || height <= 0");
+    MI355_DECLINE_IF(disabled() || width <= 0 || height <= 0);
     const bool small = ksize == 3 || ksize == 5;
     const bool typed = depth == MI355CV_16U || depth == MI355CV_16S || depth == MI355CV_32F;      // sort networks: apertures 3 and 5 only, any channel count (the reference asserts the same)
-    if (ksize < 3 || !(ksize & 1) || cn < 1) return mi355::declined(__func__, __LINE__, "ksize < 3 || !(ksize & 1) || cn < 1");
+    MI355_DECLINE_IF(ksize < 3 || !(ksize & 1) || cn < 1);
     if (typed ? !small || cn > 512 : (depth != MI355CV_8U || ksize > lim::MEDIAN8U_MAX_KSIZE || (small ? cn > 512 : !(cn == 1 || cn == 3 || cn == 4))))
         return setError(MI355CV_NOT_IMPLEMENTED, "medianBlur: depth %d, %d channel(s), aperture %d (served: CV_8U with apertures 3 and 5 or, with 1 / 3 / 4 channels, up to 31; CV_16U / CV_16S / CV_32F with apertures 3 and 5)", depth, cn, ksize);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const bool devSrc = isDevicePtr(src_data);
-    if (!devSrc && (size_t)width * height < minPixels(HOST_HEAVY)) return mi355::declined(__func__, __LINE__, "!devSrc && (size_t)width * height < minPixels(HOST_HEAVY)");
-    if (devSrc && src_data == dst_data) return mi355::declined(__func__, __LINE__, "devSrc && src_data == dst_data");                  // in place on the device: a stencil cannot
+    MI355_DECLINE_IF(!devSrc && (size_t)width * height < minPixels(HOST_HEAVY));
+    MI355_DECLINE_IF(devSrc && src_data == dst_data);                  // in place on the device: a stencil cannot
     const int esz = depth == MI355CV_8U ? 1 : depth == MI355CV_32F ? 4 : 2;
     size_t dss, dds;
     const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * esz, height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * cn * esz, height, &dds);
-    if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
+    MI355_DECLINE_IF(!ds || !dd);
     hipStream_t st = stream();
     if (typed) {
         dim3 grid(divUp(width * cn, 64), divUp(height, 4));

@@ -227,28 +227,28 @@ bool upload(const uchar* p, size_t step, size_t frame, size_t rowBytes, int h, i
 int runMinMax(const char* entry, const uchar* src, size_t sstep, size_t sframe, int w, int h, int depth, const uchar* mask, size_t mstep, size_t mframe, int nframes,
               double* vals, int* locs)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src || !vals || !locs) return mi355::declined(__func__, __LINE__, "!src || !vals || !locs");
-    if (depth < 0 || depth > 6) return mi355::declined(__func__, __LINE__, "depth is not CV_8U .. CV_64F");
-    if (w <= 0 || h <= 0 || w > lim::MINMAX_MAX_DIM || h > lim::MINMAX_MAX_DIM) return mi355::declined(__func__, __LINE__, "w <= 0 || h <= 0 || w > lim::MINMAX_MAX_DIM || h > lim::MINMAX_MAX_DIM");
-    if (nframes < 1 || nframes > minmax::MAX_FRAMES) return mi355::declined(__func__, __LINE__, "nframes < 1 || nframes > 65535");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src || !vals || !locs);
+    if (depth < 0 || depth > 6) return MI355_DECLINED("depth is not CV_8U .. CV_64F");
+    MI355_DECLINE_IF(w <= 0 || h <= 0 || w > lim::MINMAX_MAX_DIM || h > lim::MINMAX_MAX_DIM);
+    if (nframes < 1 || nframes > minmax::MAX_FRAMES) return MI355_DECLINED("nframes < 1 || nframes > 65535");
     const size_t esz = (size_t)depthBytes(depth), rowBytes = (size_t)w * esz;
-    if (sstep < rowBytes || (mask && mstep < (size_t)w)) return mi355::declined(__func__, __LINE__, "src_step or mask_step is smaller than a row");
-    if (sstep % esz || sframe % esz || (uintptr_t)src % esz) return mi355::declined(__func__, __LINE__, "src, src_step or src_frame_stride is no multiple of the element size");
+    if (sstep < rowBytes || (mask && mstep < (size_t)w)) return MI355_DECLINED("src_step or mask_step is smaller than a row");
+    if (sstep % esz || sframe % esz || (uintptr_t)src % esz) return MI355_DECLINED("src, src_step or src_frame_stride is no multiple of the element size");
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const int skind = ptrKind(src), mkind = mask ? ptrKind(mask) : skind, vkind = ptrKind(vals), lkind = ptrKind(locs);
     if (skind == PTR_FOREIGN || mkind == PTR_FOREIGN || vkind == PTR_FOREIGN || lkind == PTR_FOREIGN)
-        return mi355::declined(__func__, __LINE__, "an argument lives on another device");
-    if (skind != mkind) return mi355::declined(__func__, __LINE__, "src and mask must both live on this thread's device or both on the host");
-    if (vkind != lkind) return mi355::declined(__func__, __LINE__, "vals and locs must both live on this thread's device or both on the host");
+        return MI355_DECLINED("an argument lives on another device");
+    if (skind != mkind) return MI355_DECLINED("src and mask must both live on this thread's device or both on the host");
+    if (vkind != lkind) return MI355_DECLINED("vals and locs must both live on this thread's device or both on the host");
     const bool shost = skind == PTR_HOST, rhost = vkind == PTR_HOST;
-    if (hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_CHEAP))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_CHEAP))");
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)w * h, minPixels(HOST_CHEAP)));
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(h - 1) * sstep + rowBytes, mspan = (size_t)(nframes - 1) * mframe + (size_t)(h - 1) * mstep + w;
     const size_t vspan = (size_t)nframes * 2 * sizeof(double), lspan = (size_t)nframes * 4 * sizeof(int);
     if (overlapOnDevice(src, sspan, vals, vspan) || overlapOnDevice(src, sspan, locs, lspan) || (mask && (overlapOnDevice(mask, mspan, vals, vspan) || overlapOnDevice(mask, mspan, locs, lspan))))
-        return mi355::declined(__func__, __LINE__, "the results overlap the source or the mask in HBM");
-    if (!rhost && overlapOnDevice(vals, vspan, locs, lspan)) return mi355::declined(__func__, __LINE__, "vals and locs overlap");
+        return MI355_DECLINED("the results overlap the source or the mask in HBM");
+    if (!rhost && overlapOnDevice(vals, vspan, locs, lspan)) return MI355_DECLINED("vals and locs overlap");
 
     Launch a;
     a.w = w; a.h = h;
@@ -259,7 +259,7 @@ int runMinMax(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
     uchar* part = (uchar*)stg.scratch(pad256(slots * ksz) + slots * 4);
     double* dvals = rhost ? (double*)stg.scratch(vspan + lspan) : vals;
     char* landing = rhost ? (char*)stg.pinned(vspan + lspan) : nullptr;
-    if (!part || !dvals || (rhost && !landing)) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (!part || !dvals || (rhost && !landing)) return MI355_DECLINED("no scratch");
     int* dlocs = rhost ? (int*)(dvals + 2 * (size_t)nframes) : locs;
     a.pk = part; a.pi = (uint32_t*)(part + pad256(slots * ksz));
     // host-resident frames: dense copies of a group of at most 1 GiB of them; a mask shared by all frames goes up once
@@ -269,7 +269,7 @@ int runMinMax(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
     const int group = shost ? (int)std::min<size_t>((size_t)nframes, std::max<size_t>(1, (size_t(1) << 30) / perFrame)) : nframes;
     uchar* hsrc = shost ? (uchar*)stg.scratch(hstep * h * group) : nullptr;
     uchar* hmask = shost && mask ? (uchar*)stg.scratch(hmstep * h * (sharedMask ? 1 : group)) : nullptr;
-    if (shost && (!hsrc || (mask && !hmask))) return mi355::declined(__func__, __LINE__, "no scratch");
+    if (shost && (!hsrc || (mask && !hmask))) return MI355_DECLINED("no scratch");
     hipStream_t st = stream();
     if (shost && sharedMask && !upload(mask, mstep, 0, (size_t)w, h, 1, hmask, hmstep, st))
         return setError(MI355CV_ERROR_UNKNOWN, "%s: H2D failed: %s", entry, hipGetErrorString(hipGetLastError()));

@@ -173,26 +173,26 @@ MI355CV_API int mi355cv_morphInit(cvhalFilter2D** context, int operation, int sr
 {
     mi355::EntryGuard entry_(__func__);
     (void)max_width; (void)max_height; (void)allowSubmatrix;
-    if (!context || disabled()) return mi355::declined(__func__, __LINE__, "!context || disabled()");
-    if (operation != 0 && operation != 1) return mi355::declined(__func__, __LINE__, "operation != 0 && operation != 1");          // MORPH_ERODE / MORPH_DILATE
+    MI355_DECLINE_IF(!context || disabled());
+    MI355_DECLINE_IF(operation != 0 && operation != 1);          // MORPH_ERODE / MORPH_DILATE
     (void)allowInplace;
-    if (iterations < 1 || iterations > 64 || src_type != dst_type) return mi355::declined(__func__, __LINE__, "iterations < 1 || iterations > 64 || src_type != dst_type");
+    MI355_DECLINE_IF(iterations < 1 || iterations > 64 || src_type != dst_type);
     const int depth = MI355CV_MAT_DEPTH(src_type), cn = MI355CV_MAT_CN(src_type);
-    if ((depth != D8U && depth != D16U && depth != D16S && depth != D32F && depth != D64F) || cn < 1 || cn > 512) return mi355::declined(__func__, __LINE__, "depth is none of 8U / 16U / 16S / 32F / 64F || cn < 1 || cn > 512");
-    if (!kernel_data || MI355CV_MAT_DEPTH(kernel_type) != D8U || MI355CV_MAT_CN(kernel_type) != 1) return mi355::declined(__func__, __LINE__, "!kernel_data || MI355CV_MAT_DEPTH(kernel_type) != D8U || MI355CV_MAT_CN(kernel_type) != 1");
-    if (kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024) return mi355::declined(__func__, __LINE__, "kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024");
+    if ((depth != D8U && depth != D16U && depth != D16S && depth != D32F && depth != D64F) || cn < 1 || cn > 512) return MI355_DECLINED("depth is none of 8U / 16U / 16S / 32F / 64F || cn < 1 || cn > 512");
+    MI355_DECLINE_IF(!kernel_data || MI355CV_MAT_DEPTH(kernel_type) != D8U || MI355CV_MAT_CN(kernel_type) != 1);
+    MI355_DECLINE_IF(kernel_width < 1 || kernel_height < 1 || kernel_width * kernel_height > 1024);
     const int border = borderType & ~MI355CV_BORDER_ISOLATED;
-    if (border < 0 || border > B_REFLECT_101 || border == B_WRAP) return mi355::declined(__func__, __LINE__, "border < 0 || border > B_REFLECT_101 || border == B_WRAP");
+    MI355_DECLINE_IF(border < 0 || border > B_REFLECT_101 || border == B_WRAP);
     MorphCtx* c = new (std::nothrow) MorphCtx();
-    if (!c) return mi355::declined(__func__, __LINE__, "!c");
+    MI355_DECLINE_IF(!c);
     c->iterations = iterations;
     c->magic = MORPH_MAGIC; c->op = operation; c->depth = depth; c->cn = cn; c->kw = kernel_width; c->kh = kernel_height; c->border = border;
     c->ax = anchor_x < 0 ? kernel_width / 2 : anchor_x; c->ay = anchor_y < 0 ? kernel_height / 2 : anchor_y;
-    if (c->ax >= kernel_width || c->ay >= kernel_height) { delete c; return mi355::declined(__func__, __LINE__, nullptr); }
+    if (c->ax >= kernel_width || c->ay >= kernel_height) { delete c; return MI355_DECLINED(nullptr); }
     for (int j = 0; j < kernel_height; j++)
         for (int i = 0; i < kernel_width; i++)
             if (kernel_data[(size_t)j * kernel_step + i]) c->taps.push_back({(short)i, (short)j});
-    if (c->taps.empty()) { delete c; return mi355::declined(__func__, __LINE__, nullptr); }               // the reference asserts a non-empty element
+    if (c->taps.empty()) { delete c; return MI355_DECLINED(nullptr); }               // the reference asserts a non-empty element
     c->rect = (int)c->taps.size() == kernel_width * kernel_height;
     c->defaultBorder = !borderValue || (borderValue[0] == DBL_MAX && borderValue[1] == DBL_MAX && borderValue[2] == DBL_MAX && borderValue[3] == DBL_MAX);
     for (int k = 0; k < 4; k++) {
@@ -216,23 +216,23 @@ MI355CV_API int mi355cv_morph(cvhalFilter2D* context, uchar* src_data, size_t sr
 {
     mi355::EntryGuard entry_(__func__);
     MorphCtx* c = reinterpret_cast<MorphCtx*>(context);
-    if (!c || c->magic != MORPH_MAGIC || width <= 0 || height <= 0) return mi355::declined(__func__, __LINE__, "!c || c->magic != MORPH_MAGIC || width <= 0 || height <= 0");
+    MI355_DECLINE_IF(!c || c->magic != MORPH_MAGIC || width <= 0 || height <= 0);
     const int iters = c->iterations;
     if (iters > 1 && !(dst_full_width == width && dst_full_height == height && dst_roi_x == 0 && dst_roi_y == 0))
         return setError(MI355CV_NOT_IMPLEMENTED, "morph: %d iterations into a destination submatrix (the passes after the first would read the parent's pixels around it)", iters);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     // a host image: small CV_8U rectangles are bandwidth-bound on the CPU too and stay there under the default policy; irregular elements and deeper images cost the reference
     // 1.3-7 ms per 4K frame (profiles/r06_filter_morph_tile.txt) against two PCIe crossings + 30-120 us here
     const int cost = (c->depth != D8U || !c->rect) && c->taps.size() >= 5 ? HOST_HEAVY : HOST_CHEAP;
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(cost))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(cost))");
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(cost)));
     const int e = c->depth == D8U ? 1 : c->depth == D32F ? 4 : c->depth == D64F ? 8 : 2;
     const bool inplaceDev = inPlaceOnDevice(src_data, dst_data);
     size_t dss, dds;
     const uchar* top = src_data - (ptrdiff_t)src_roi_y * (ptrdiff_t)src_step - (ptrdiff_t)src_roi_x * c->cn * e;
     const uchar* dtop = stg.in(top, src_step, (size_t)src_full_width * c->cn * e, src_full_height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * c->cn * e, height, &dds);
-    if (!dtop || !dd) return mi355::declined(__func__, __LINE__, "!dtop || !dd");
+    MI355_DECLINE_IF(!dtop || !dd);
     const uchar* ds = dtop + (size_t)src_roi_y * dss + (size_t)src_roi_x * c->cn * e;
     hipStream_t st = stream();
     // intermediate images: two for the ping-pong of iterated passes, one for an in-place call on the device
@@ -241,7 +241,7 @@ MI355CV_API int mi355cv_morph(cvhalFilter2D* context, uchar* src_data, size_t sr
     if (iters > 1 || inplaceDev) {
         tmp[0] = (uchar*)stg.scratch(tpitch * height);
         if (iters > 2) tmp[1] = (uchar*)stg.scratch(tpitch * height);
-        if (!tmp[0] || (iters > 2 && !tmp[1])) return mi355::declined(__func__, __LINE__, "scratch for the intermediate image");
+        if (!tmp[0] || (iters > 2 && !tmp[1])) return MI355_DECLINED("scratch for the intermediate image");
     }
     MorphTap* dt = nullptr;
     unsigned* dmask = nullptr;
@@ -300,7 +300,7 @@ MI355CV_API int mi355cv_morph(cvhalFilter2D* context, uchar* src_data, size_t sr
         uchar* out = last && !(inplaceDev && iters == 1) ? dd : tmp[(p - 1) & 1];
         const size_t outStep = out == dd ? dds : tpitch;
         if (!(p == 1 ? pass(cur, curStep, src_full_width, src_full_height, src_roi_x, src_roi_y, out, outStep) : pass(cur, curStep, width, height, 0, 0, out, outStep)))
-            return mi355::declined(__func__, __LINE__, "device copy of the structuring element");
+            return MI355_DECLINED("device copy of the structuring element");
         cur = out; curStep = outStep;
     }
     if (cur != dd && hipMemcpy2DAsync(dd, dds, cur, curStep, (size_t)width * c->cn * e, height, hipMemcpyDeviceToDevice, st) != hipSuccess)
@@ -312,7 +312,7 @@ MI355CV_API int mi355cv_morphFree(cvhalFilter2D* context)
 {
     mi355::EntryGuard entry_(__func__);
     MorphCtx* c = reinterpret_cast<MorphCtx*>(context);
-    if (!c || c->magic != MORPH_MAGIC) return mi355::declined(__func__, __LINE__, "!c || c->magic != MORPH_MAGIC");
+    MI355_DECLINE_IF(!c || c->magic != MORPH_MAGIC);
     c->magic = 0;
     delete c;
     return MI355CV_OK;

@@ -150,14 +150,14 @@ void launchPyrUp(const uchar* ds, size_t dss, size_t sframe, int sw, int sh, uch
 // the refusals that need no device; 0 when the arguments are served
 int pyrUpArgs(const void* src, int sw, int sh, const void* dst, int dw, int dh, int nframes, int depth, int cn, int border)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (!src || !dst || nframes < 1) return mi355::declined(__func__, __LINE__, "!src || !dst || nframes < 1");
-    if ((border & ~MI355CV_BORDER_ISOLATED) != B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border != BORDER_DEFAULT");      // the reference asserts it
-    if (!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4) return mi355::declined(__func__, __LINE__, "!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(!src || !dst || nframes < 1);
+    if ((border & ~MI355CV_BORDER_ISOLATED) != B_REFLECT_101) return MI355_DECLINED("border != BORDER_DEFAULT");      // the reference asserts it
+    MI355_DECLINE_IF(!(depth == D8U || depth == D16U || depth == D16S || depth == D32F) || cn < 1 || cn > 4);
     // 2 * sw * cn and 2 * sh are ints in the kernels
-    if (sw <= 0 || sh <= 0 || sw > (1 << 27) || sh > (1 << 29)) return mi355::declined(__func__, __LINE__, "sw <= 0 || sh <= 0 || sw > (1 << 27) || sh > (1 << 29)");
+    MI355_DECLINE_IF(sw <= 0 || sh <= 0 || sw > (1 << 27) || sh > (1 << 29));
     // the reference also admits 2w +- 1 / 2h +- 1 (its last column / row then repeats or is dropped): left to it
-    if (dw != 2 * sw || dh != 2 * sh) return mi355::declined(__func__, __LINE__, "dw != 2 * sw || dh != 2 * sh");
+    MI355_DECLINE_IF(dw != 2 * sw || dh != 2 * sh);
     return 0;
 }
 
@@ -166,18 +166,18 @@ int runPyrUp(const char* entry, const uchar* src, size_t sstep, size_t sframe, i
 {
     if (const int rc = pyrUpArgs(src, sw, sh, dst, dw, dh, nframes, depth, cn, border)) return rc;
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)sw * sh, minPixels())) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)sw * sh, minPixels())");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)sw * sh, minPixels()));
     const size_t e = (size_t)cn * depthBytes(depth);
     const size_t sspan = (size_t)(nframes - 1) * sframe + (size_t)(sh - 1) * sstep + sw * e, dspan = (size_t)(nframes - 1) * dframe + (size_t)(dh - 1) * dstep + dw * e;
-    if (overlapOnDevice(src, sspan, dst, dspan)) return mi355::declined(__func__, __LINE__, "overlapOnDevice(src, sspan, dst, dspan)");
+    MI355_DECLINE_IF(overlapOnDevice(src, sspan, dst, dspan));
     size_t dss = sstep, dds = dstep;
     const uchar* ds = src; uchar* dd = dst;
     if (nframes == 1) {
         ds = stg.in(src, sstep, sw * e, sh, &dss);
         dd = stg.out(dst, dstep, dw * e, dh, &dds);
-        if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
-    } else if (!isDevicePtr(src) || !isDevicePtr(dst)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(src) || !isDevicePtr(dst)");
+        MI355_DECLINE_IF(!ds || !dd);
+    } else MI355_DECLINE_IF(!isDevicePtr(src) || !isDevicePtr(dst));
     launchPyrUp(ds, dss, sframe, sw, sh, dd, dds, dframe, nframes, depth, cn, stream());
     MI355_CHECK_LAUNCH(entry);
     return stg.finish(entry);

@@ -60,6 +60,8 @@ bool hostImageTooSmall(const void* img, size_t pixels, size_t threshold);
 int  setError(int code, const char* fmt, ...);
 // a hook answers NOT_IMPLEMENTED: records WHY for mi355cv_lastError and the decline ledger (mi355cv_noteDecline) -- "<entry>:<line>: <the condition that held>" --
 // unless a more specific reason was already recorded during this call (staging failure, host-policy threshold, foreign device ...).  Returns MI355CV_NOT_IMPLEMENTED.
+// Call it through the macros below (next to MI355_CHECK_LAUNCH): MI355_DECLINE_IF(cond) where the condition is its own reason, `if (cond) return MI355_DECLINED("wording");`
+// where a human wording says more than the expression.
 int  declined(const char* fn, int line, const char* cond);
 // first line of every extern "C" entry: the outermost entry on a thread starts a new call serial, so that a reason recorded by an EARLIER call that failed before it
 // opened a Stager (argument checks, runSharded / replicate errors) is never reported as this call's; nested entries keep their caller's serial
@@ -166,6 +168,10 @@ __device__ __forceinline__ unsigned xcdContiguous(unsigned id, unsigned n)
 #define MI355_CHECK_LAUNCH(entry)                                                        \
     do { hipError_t e__ = hipGetLastError();                                             \
          if (e__ != hipSuccess) return mi355::setError(MI355CV_ERROR_UNKNOWN, "%s: launch failed: %s", entry, hipGetErrorString(e__)); } while (0)
+
+// the ONE way to decline: the reason is the condition's own source text, so the two cannot drift
+#define MI355_DECLINED(why)   mi355::declined(__func__, __LINE__, why)
+#define MI355_DECLINE_IF(...) do { if (__VA_ARGS__) return MI355_DECLINED(#__VA_ARGS__); } while (0)
 
 #ifdef __HIPCC__
 // (a << n) + b as ONE v_lshl_add_u32, and a + 4 b + 6 c on packed u16 pairs in four of them: written as plain C the optimiser folds the

@@ -418,23 +418,18 @@ bool hostBatchEligible(const void* src, const void* dst, int nframes)
     return nframes >= 1 && src && dst && !disabled() && resolveDevice() >= 0 && ptrKind(src) == PTR_HOST && ptrKind(dst) == PTR_HOST;
 }
 
-int runHostBatch(const char* entry, const HostBatch& hb, const HostBatchFn& run)
+// The pipeline itself, written once for any number of outputs; runHostBatch and runHostBatchN below are its front ends.  A front end refuses its own arguments, opens the
+// Stager, picks the frames per chunk by its own rule, takes the two buffer sets from the Stager (din[b]: cf source frames, dout[b][o]: cf frames of output o, rows at
+// hostBatchPitch) and has checked that the aux stream and its four pooled events ev0 .. ev0 + 3 exist.  Each front end has its OWN four: nothing proves that the two are
+// never live on one thread at once.
+static size_t hostBatchPitch(size_t rowBytes) { return (rowBytes + 255) & ~(size_t)255; }
+static int hostBatchPipeline(const char* entry, Stager& stg, const HostBatchN& hb, int cf, uchar* const* din, uchar* const* const* dout, int ev0, const HostBatchNFn& run)
 {
-    if (disabled() || hb.nframes < 1 || hb.srows < 1 || hb.drows < 1 || !hb.srowBytes || !hb.drowBytes) return mi355::declined(__func__, __LINE__, "disabled() || hb.nframes < 1 || hb.srows < 1 || hb.drows < 1 || !hb.srowBytes || !hb.drowBytes");
-    Stager stg;                                                          // outermost: the chunks' own hooks leave synchronisation to this one; first, so that a declined call also puts the host's device back
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    const size_t sp = (hb.srowBytes + 255) & ~(size_t)255, dp = (hb.drowBytes + 255) & ~(size_t)255;
-    const size_t sfb = sp * (size_t)hb.srows, dfb = dp * (size_t)hb.drows;
-    int cf = (int)((size_t)(64u << 20) / std::max(sfb, dfb));           // frames per chunk: <= 64 MB per buffer, <= 16 frames
-    cf = cf < 1 ? 1 : cf > 16 ? 16 : cf; if (cf > hb.nframes) cf = hb.nframes;
-    uchar* din[2]; uchar* dout[2];
-    for (int b = 0; b < 2; b++) {
-        din[b] = (uchar*)stg.scratch(sfb * cf); dout[b] = (uchar*)stg.scratch(dfb * cf);
-        if (!din[b] || !dout[b]) return mi355::declined(__func__, __LINE__, "!din[b] || !dout[b]");
-    }
+    const size_t sp = hostBatchPitch(hb.srowBytes), sfb = sp * (size_t)hb.srows;
+    size_t dp[HOST_BATCH_MAX_OUT], dfb[HOST_BATCH_MAX_OUT];
+    for (int o = 0; o < hb.nout; o++) { dp[o] = hostBatchPitch(hb.out[o].drowBytes); dfb[o] = dp[o] * (size_t)hb.out[o].drows; }
     hipStream_t st = stream(), aux = auxStream();
-    hipEvent_t inReady[2] = {pooledEvent(40), pooledEvent(41)}, bufFree[2] = {pooledEvent(42), pooledEvent(43)};
-    if (!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]) return mi355::declined(__func__, __LINE__, "!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]");
+    hipEvent_t inReady[2] = {pooledEvent(ev0), pooledEvent(ev0 + 1)}, bufFree[2] = {pooledEvent(ev0 + 2), pooledEvent(ev0 + 3)};
     const int nchunks = (hb.nframes + cf - 1) / cf;
     auto upload = [&](int c) -> bool {
         const int b = c & 1, f0 = c * cf, nf = std::min(cf, hb.nframes - f0);
@@ -460,58 +455,6 @@ int runHostBatch(const char* entry, const HostBatch& hb, const HostBatchFn& run)
         // scratch the chunk's hook took from the pool is free for the next chunk's: same thread, same stream, stream order
         for (size_t i = 0; i < tctx().pool.size(); i++) if (tctx().pool[i].busy && (i >= was.size() || !was[i])) tctx().pool[i].busy = false;
         if (rc != MI355CV_OK) return fail(rc);
-        for (int f = 0; f < nf; f++)
-            if (hipMemcpy2DAsync(hb.dst + (size_t)(f0 + f) * hb.dframe, hb.dstep, dout[b] + (size_t)f * dfb, dp, hb.drowBytes, hb.drows, hipMemcpyDeviceToHost, st) != hipSuccess)
-                return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: D2H failed: %s", entry, hipGetErrorString(hipGetLastError())));
-        if (hipEventRecord(bufFree[b], st) != hipSuccess) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: %s", entry, hipGetErrorString(hipGetLastError())));
-        g_stagedBytes += (long long)(hb.srowBytes * (size_t)hb.srows + hb.drowBytes * (size_t)hb.drows) * nf;
-    }
-    if (hipStreamSynchronize(st) != hipSuccess) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: %s", entry, hipGetErrorString(hipGetLastError())));
-    return stg.finish(entry);
-}
-
-int runHostBatchN(const char* entry, const HostBatchN& hb, const HostBatchNFn& run)
-{
-    if (disabled() || hb.nframes < 1 || hb.srows < 1 || !hb.srowBytes || hb.nout < 1 || hb.nout > HOST_BATCH_MAX_OUT) return mi355::declined(__func__, __LINE__, "disabled() || hb.nframes < 1 || hb.srows < 1 || !hb.srowBytes || hb.nout < 1 || hb.nout > HOST_BATCH_MAX_OUT");
-    for (int o = 0; o < hb.nout; o++) if (!hb.out[o].dst || hb.out[o].drows < 1 || !hb.out[o].drowBytes) return mi355::declined(__func__, __LINE__, "!hb.out[o].dst || hb.out[o].drows < 1 || !hb.out[o].drowBytes");
-    Stager stg;                                                          // outermost: the chunks' own hooks leave synchronisation to this one
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    const size_t sp = (hb.srowBytes + 255) & ~(size_t)255, sfb = sp * (size_t)hb.srows;
-    size_t dp[HOST_BATCH_MAX_OUT], dfb[HOST_BATCH_MAX_OUT], perFrame = sfb;
-    for (int o = 0; o < hb.nout; o++) { dp[o] = (hb.out[o].drowBytes + 255) & ~(size_t)255; dfb[o] = dp[o] * (size_t)hb.out[o].drows; perFrame += dfb[o]; }
-    int cf = (int)((size_t)(128u << 20) / perFrame);                     // frames per chunk: <= 128 MB per set of buffers, <= 16 frames
-    cf = cf < 1 ? 1 : cf > 16 ? 16 : cf; if (cf > hb.nframes) cf = hb.nframes;
-    uchar* din[2]; uchar* dout[2][HOST_BATCH_MAX_OUT]; size_t dfs[HOST_BATCH_MAX_OUT];
-    for (int b = 0; b < 2; b++) {
-        din[b] = (uchar*)stg.scratch(sfb * cf);
-        if (!din[b]) return mi355::declined(__func__, __LINE__, "!din[b]");
-        for (int o = 0; o < hb.nout; o++) { dout[b][o] = (uchar*)stg.scratch(dfb[o] * cf); dfs[o] = dfb[o]; if (!dout[b][o]) return mi355::declined(__func__, __LINE__, "!dout[b][o]"); }
-    }
-    hipStream_t st = stream(), aux = auxStream();
-    hipEvent_t inReady[2] = {pooledEvent(44), pooledEvent(45)}, bufFree[2] = {pooledEvent(46), pooledEvent(47)};
-    if (!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]) return mi355::declined(__func__, __LINE__, "!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]");
-    const int nchunks = (hb.nframes + cf - 1) / cf;
-    auto upload = [&](int c) -> bool {
-        const int b = c & 1, f0 = c * cf, nf = std::min(cf, hb.nframes - f0);
-        if (c >= 2 && hipStreamWaitEvent(aux, bufFree[b], 0) != hipSuccess) return false;          // the buffers' previous chunk has been consumed and downloaded
-        for (int f = 0; f < nf; f++)
-            if (hipMemcpy2DAsync(din[b] + (size_t)f * sfb, sp, hb.src + (size_t)(f0 + f) * hb.sframe, hb.sstep, hb.srowBytes, hb.srows, hipMemcpyHostToDevice, aux) != hipSuccess)
-                return false;
-        return hipEventRecord(inReady[b], aux) == hipSuccess;
-    };
-    auto fail = [&](int code) { (void)hipStreamSynchronize(aux); (void)hipStreamSynchronize(st); return code; };       // see runHostBatch
-    if (!upload(0)) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: H2D failed: %s", entry, hipGetErrorString(hipGetLastError())));
-    std::vector<char> was;
-    for (int c = 0; c < nchunks; c++) {
-        const int b = c & 1, f0 = c * cf, nf = std::min(cf, hb.nframes - f0);
-        if (c + 1 < nchunks && !upload(c + 1)) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: H2D failed: %s", entry, hipGetErrorString(hipGetLastError())));
-        if (hipStreamWaitEvent(st, inReady[b], 0) != hipSuccess) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: %s", entry, hipGetErrorString(hipGetLastError())));
-        auto& pool = tctx().pool;
-        was.assign(pool.size(), 0);
-        for (size_t i = 0; i < pool.size(); i++) was[i] = pool[i].busy;
-        const int rc = run(din[b], sp, sfb, dout[b], dp, dfs, nf);
-        for (size_t i = 0; i < tctx().pool.size(); i++) if (tctx().pool[i].busy && (i >= was.size() || !was[i])) tctx().pool[i].busy = false;
-        if (rc != MI355CV_OK) return fail(rc);
         long long bytes = (long long)(hb.srowBytes * (size_t)hb.srows) * nf;
         for (int o = 0; o < hb.nout; o++) {
             const HostBatchOut& ho = hb.out[o];
@@ -525,6 +468,52 @@ int runHostBatchN(const char* entry, const HostBatchN& hb, const HostBatchNFn& r
     }
     if (hipStreamSynchronize(st) != hipSuccess) return fail(setError(MI355CV_ERROR_UNKNOWN, "%s: %s", entry, hipGetErrorString(hipGetLastError())));
     return stg.finish(entry);
+}
+
+int runHostBatch(const char* entry, const HostBatch& hb, const HostBatchFn& run)
+{
+    MI355_DECLINE_IF(disabled() || hb.nframes < 1 || hb.srows < 1 || hb.drows < 1 || !hb.srowBytes || !hb.drowBytes);
+    Stager stg;                                                          // outermost: the chunks' own hooks leave synchronisation to this one; first, so that a declined call also puts the host's device back
+    MI355_DECLINE_IF(!ensureDevice());
+    const size_t sfb = hostBatchPitch(hb.srowBytes) * (size_t)hb.srows, dfb = hostBatchPitch(hb.drowBytes) * (size_t)hb.drows;
+    int cf = (int)((size_t)(64u << 20) / std::max(sfb, dfb));           // frames per chunk: <= 64 MB per buffer, <= 16 frames
+    cf = cf < 1 ? 1 : cf > 16 ? 16 : cf; if (cf > hb.nframes) cf = hb.nframes;
+    uchar* din[2]; uchar* dout[2];
+    for (int b = 0; b < 2; b++) {
+        din[b] = (uchar*)stg.scratch(sfb * cf); dout[b] = (uchar*)stg.scratch(dfb * cf);
+        MI355_DECLINE_IF(!din[b] || !dout[b]);
+    }
+    hipStream_t aux = auxStream();
+    hipEvent_t inReady[2] = {pooledEvent(40), pooledEvent(41)}, bufFree[2] = {pooledEvent(42), pooledEvent(43)};
+    MI355_DECLINE_IF(!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]);
+    const HostBatchN hn = {hb.src, hb.sstep, hb.sframe, hb.srowBytes, hb.srows, 1, {{hb.dst, hb.dstep, hb.dframe, hb.drowBytes, hb.drows}}, hb.nframes};
+    uchar* const* const douts[2] = {&dout[0], &dout[1]};
+    return hostBatchPipeline(entry, stg, hn, cf, din, douts, 40, [&](const uchar* s, size_t ss, size_t sf, uchar* const* d, const size_t* ds, const size_t* df, int nf) {
+        return run(s, ss, sf, d[0], ds[0], df[0], nf); });
+}
+
+int runHostBatchN(const char* entry, const HostBatchN& hb, const HostBatchNFn& run)
+{
+    MI355_DECLINE_IF(disabled() || hb.nframes < 1 || hb.srows < 1 || !hb.srowBytes || hb.nout < 1 || hb.nout > HOST_BATCH_MAX_OUT);
+    for (int o = 0; o < hb.nout; o++) MI355_DECLINE_IF(!hb.out[o].dst || hb.out[o].drows < 1 || !hb.out[o].drowBytes);
+    Stager stg;                                                          // outermost: the chunks' own hooks leave synchronisation to this one
+    MI355_DECLINE_IF(!ensureDevice());
+    const size_t sfb = hostBatchPitch(hb.srowBytes) * (size_t)hb.srows;
+    size_t dfb[HOST_BATCH_MAX_OUT], perFrame = sfb;
+    for (int o = 0; o < hb.nout; o++) { dfb[o] = hostBatchPitch(hb.out[o].drowBytes) * (size_t)hb.out[o].drows; perFrame += dfb[o]; }
+    int cf = (int)((size_t)(128u << 20) / perFrame);                     // frames per chunk: <= 128 MB per set of buffers, <= 16 frames
+    cf = cf < 1 ? 1 : cf > 16 ? 16 : cf; if (cf > hb.nframes) cf = hb.nframes;
+    uchar* din[2]; uchar* dout[2][HOST_BATCH_MAX_OUT];
+    for (int b = 0; b < 2; b++) {
+        din[b] = (uchar*)stg.scratch(sfb * cf);
+        MI355_DECLINE_IF(!din[b]);
+        for (int o = 0; o < hb.nout; o++) { dout[b][o] = (uchar*)stg.scratch(dfb[o] * cf); MI355_DECLINE_IF(!dout[b][o]); }
+    }
+    hipStream_t aux = auxStream();
+    hipEvent_t inReady[2] = {pooledEvent(44), pooledEvent(45)}, bufFree[2] = {pooledEvent(46), pooledEvent(47)};
+    MI355_DECLINE_IF(!aux || !inReady[0] || !inReady[1] || !bufFree[0] || !bufFree[1]);
+    uchar* const* const douts[2] = {dout[0], dout[1]};
+    return hostBatchPipeline(entry, stg, hb, cf, din, douts, 44, run);
 }
 
 } // namespace mi355

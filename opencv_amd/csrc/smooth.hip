@@ -720,15 +720,15 @@ int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
               int nframes, int W, int H, int cn, int mL, int mT, int mR, int mB,
               const uint16_t* kx, int nx, const uint16_t* ky, int ny, int border, bool binomial)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
-    if (W <= 0 || H <= 0 || nframes <= 0 || cn < 1 || cn > 4) return mi355::declined(__func__, __LINE__, "W <= 0 || H <= 0 || nframes <= 0 || cn < 1 || cn > 4");
-    if (nx < 1 || ny < 1 || nx > lim::GAUSS8U_MAX_KSIZE || ny > lim::GAUSS8U_MAX_KSIZE || !(nx & 1) || !(ny & 1)) return mi355::declined(__func__, __LINE__, "nx < 1 || ny < 1 || nx or ny > lim::GAUSS8U_MAX_KSIZE || !(nx & 1) || !(ny & 1)");
-    if (border < 0 || border > B_REFLECT_101) return mi355::declined(__func__, __LINE__, "border < 0 || border > B_REFLECT_101");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(W <= 0 || H <= 0 || nframes <= 0 || cn < 1 || cn > 4);
+    MI355_DECLINE_IF(nx < 1 || ny < 1 || nx > lim::GAUSS8U_MAX_KSIZE || ny > lim::GAUSS8U_MAX_KSIZE || !(nx & 1) || !(ny & 1));
+    MI355_DECLINE_IF(border < 0 || border > B_REFLECT_101);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const bool hostSrc = !isDevicePtr(src);
-    if (hostSrc && (size_t)W * H < minPixels()) return mi355::declined(__func__, __LINE__, "hostSrc && (size_t)W * H < minPixels()");
-    if (!hostSrc && src == dst) return mi355::declined(__func__, __LINE__, "!hostSrc && src == dst");            // in place on the device (cv::GaussianBlur itself clones, smooth.dispatch.cpp:685)
+    MI355_DECLINE_IF(hostSrc && (size_t)W * H < minPixels());
+    MI355_DECLINE_IF(!hostSrc && src == dst);            // in place on the device (cv::GaussianBlur itself clones, smooth.dispatch.cpp:685)
 
     size_t dss = 0, dds = 0;
     const size_t rowB = (size_t)W * cn;
@@ -737,10 +737,10 @@ int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
         // stage the ROI together with its real margins (non-isolated borders read them)
         const uchar* top = src - (ptrdiff_t)mT * (ptrdiff_t)sstep - (ptrdiff_t)mL * cn;
         const uchar* dtop = stg.in(top, sstep, (size_t)(mL + W + mR) * cn, mT + H + mB, &dss);
-        if (!dtop) return mi355::declined(__func__, __LINE__, "!dtop");
+        MI355_DECLINE_IF(!dtop);
         dsrc = dtop + (size_t)mT * dss + (size_t)mL * cn;
         ddst = stg.out(dst, dstep, rowB, H, &dds);
-        if (!ddst) return mi355::declined(__func__, __LINE__, "!ddst");
+        MI355_DECLINE_IF(!ddst);
     } else {
         // batches are an HBM-resident construct: no per-frame staging
         if (hostSrc || !isDevicePtr(dst)) return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
@@ -778,7 +778,7 @@ int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
                    return seplongRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, MI355CV_8U, MI355CV_8U, mL + W + mR, mT + H + mB, mL, mT, border, t, st); }()) {
     } else {
         // taps that can saturate the reference's fixed-point types (never cv::GaussianBlur's own: they sum to 256), or MI355CV_SMOOTH_GENERIC=1: one thread per byte, <= 33 taps
-        if (nx > 33 || ny > 33) return mi355::declined(__func__, __LINE__, "Q8.8 taps that sum beyond 256 with more than 33 of them");
+        if (nx > 33 || ny > 33) return MI355_DECLINED("Q8.8 taps that sum beyond 256 with more than 33 of them");
         FixedTaps t;
         t.nx = nx; t.ny = ny;
         for (int i = 0; i < 33; i++) { t.kx[i] = i < nx ? kx[i] : 0; t.ky[i] = i < ny ? ky[i] : 0; }
@@ -825,20 +825,20 @@ int runBinom16(const char* entry, const uchar* src, size_t sstep, uchar* dst, si
 {
     if (disabled() || W <= 0 || H <= 0 || cn < 1 || cn > 4 || (ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9) || border < 0 || border > B_REFLECT_101 ||
         mL < 0 || mT < 0 || mR < 0 || mB < 0 || ((sstep | dstep | (uintptr_t)src | (uintptr_t)dst) & 1))
-        return mi355::declined(__func__, __LINE__, "disabled() || W <= 0 || H <= 0 || cn < 1 || cn > 4 || ksize not in {3, 5, 7, 9} || border outside CONSTANT .. REFLECT_101 || negative margins || odd pointers / steps");
+        return MI355_DECLINED("disabled() || W <= 0 || H <= 0 || cn < 1 || cn > 4 || ksize not in {3, 5, 7, 9} || border outside CONSTANT .. REFLECT_101 || negative margins || odd pointers / steps");
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const bool hostSrc = !isDevicePtr(src);
-    if (hostSrc && (size_t)W * H < minPixels()) return mi355::declined(__func__, __LINE__, "hostSrc && (size_t)W * H < minPixels()");
-    if (!hostSrc && src == dst) return mi355::declined(__func__, __LINE__, "!hostSrc && src == dst");
+    MI355_DECLINE_IF(hostSrc && (size_t)W * H < minPixels());
+    MI355_DECLINE_IF(!hostSrc && src == dst);
     size_t dss = 0, dds = 0;
     const size_t esz = (size_t)cn * 2;
     const uchar* top = src - (ptrdiff_t)mT * (ptrdiff_t)sstep - (ptrdiff_t)mL * (ptrdiff_t)esz;
     const uchar* dtop = stg.in(top, sstep, (size_t)(mL + W + mR) * esz, mT + H + mB, &dss);
-    if (!dtop) return mi355::declined(__func__, __LINE__, "!dtop");
+    MI355_DECLINE_IF(!dtop);
     const uchar* dsrc = dtop + (size_t)mT * dss + (size_t)mL * esz;
     uchar* ddst = stg.out(dst, dstep, (size_t)W * esz, H, &dds);
-    if (!ddst) return mi355::declined(__func__, __LINE__, "!ddst");
+    MI355_DECLINE_IF(!ddst);
     const Roi roi = {mL + W + mR, mT + H + mB, mL, mT};
     if (cn == 1 && (ksize == 3 || ksize == 5) && border != B_WRAP &&
         seprollBinom16(dsrc, dss, 0, ddst, dds, 0, 1, W, H, ksize, border, stream(), (mL | mT | mR | mB) ? &roi : nullptr))
@@ -876,9 +876,9 @@ MI355CV_API int mi355cv_gaussianBlurBinomial(const uchar* src_data, size_t src_s
     if (depth == MI355CV_16U)
         return runBinom16("gaussianBlurBinomial", src_data, src_step, dst_data, dst_step, width, height, cn, (int)margin_left, (int)margin_top, (int)margin_right,
                                  (int)margin_bottom, (int)ksize, border_type & ~MI355CV_BORDER_ISOLATED);
-    if (depth != MI355CV_8U) return mi355::declined(__func__, __LINE__, "depth != MI355CV_8U");
+    MI355_DECLINE_IF(depth != MI355CV_8U);
     const uint16_t* k = binomTaps(ksize);
-    if (!k) return mi355::declined(__func__, __LINE__, "!k");
+    MI355_DECLINE_IF(!k);
     return runSmooth("gaussianBlurBinomial", src_data, src_step, 0, dst_data, dst_step, 0, 1, width, height, cn,
                      (int)margin_left, (int)margin_top, (int)margin_right, (int)margin_bottom,
                      k, (int)ksize, k, (int)ksize, border_type & ~MI355CV_BORDER_ISOLATED, true);
@@ -902,9 +902,9 @@ MI355CV_API int mi355cv_gaussianBlurBinomialBatch(const uchar* src_data, size_t 
         int width, int height, int depth, int cn, size_t ksize, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (depth != MI355CV_8U) return mi355::declined(__func__, __LINE__, "depth != MI355CV_8U");
+    MI355_DECLINE_IF(depth != MI355CV_8U);
     const uint16_t* k = binomTaps(ksize);
-    if (!k) return mi355::declined(__func__, __LINE__, "!k");
+    MI355_DECLINE_IF(!k);
     if (nframes > 1 && width > 0 && height > 0 && cn >= 1 && cn <= 4 && hostBatchEligible(src_data, dst_data, nframes))
         return gaussBatchFromHost(src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, cn, k, (int)ksize,
                                   border_type & ~MI355CV_BORDER_ISOLATED);
@@ -926,15 +926,15 @@ MI355CV_API int mi355cv_gaussianBlur(const uchar* src_data, size_t src_step, uch
     // createGaussianKernels (:279-304: getGaussianKernel(ksize, sigma, max(depth, CV_32F)), ky = kx for a square kernel with equal sigmas) -- :825.  Until round 5 the
     // hook declined and the separable hook served that second call (257 declined calls in the reference's Imgproc_GaussianBlur tests); now the same call is made here.
     if (depth != MI355CV_8U) {
-        if (depth != MI355CV_16U && depth != MI355CV_16S && depth != MI355CV_32F) return mi355::declined(__func__, __LINE__, "depth is none of 8U / 16U / 16S / 32F");
+        if (depth != MI355CV_16U && depth != MI355CV_16S && depth != MI355CV_32F) return MI355_DECLINED("depth is none of 8U / 16U / 16S / 32F");
         const int n = (int)ksize_width, m = (int)ksize_height;
-        if (n < 1 || m < 1 || n > lim::GAUSS_FLOAT_MAX_KSIZE || m > lim::GAUSS_FLOAT_MAX_KSIZE || !(n & 1) || !(m & 1)) return mi355::declined(__func__, __LINE__, "kernel size outside 1 .. lim::GAUSS_FLOAT_MAX_KSIZE or even");
+        if (n < 1 || m < 1 || n > lim::GAUSS_FLOAT_MAX_KSIZE || m > lim::GAUSS_FLOAT_MAX_KSIZE || !(n & 1) || !(m & 1)) return MI355_DECLINED("kernel size outside 1 .. lim::GAUSS_FLOAT_MAX_KSIZE or even");
         if (sigmaY <= 0) sigmaY = sigmaX;
         const double s1 = sigmaX > 0 ? sigmaX : 0, s2 = sigmaY > 0 ? sigmaY : 0;
         std::vector<double> dx, dy;
-        if (!gaussianKernelBitExact(n, s1, dx)) return mi355::declined(__func__, __LINE__, "!gaussianKernelBitExact(n, s1, dx)");
+        MI355_DECLINE_IF(!gaussianKernelBitExact(n, s1, dx));
         if (m == n && std::fabs(s1 - s2) < 2.220446049250313e-16) dy = dx;
-        else if (!gaussianKernelBitExact(m, s2, dy)) return mi355::declined(__func__, __LINE__, "!gaussianKernelBitExact(m, s2, dy)");
+        else MI355_DECLINE_IF(!gaussianKernelBitExact(m, s2, dy));
         std::vector<float> fx(dx.begin(), dx.end()), fy(dy.begin(), dy.end());          // getGaussianKernel(.., CV_32F): the bit-exact doubles rounded to float
         const int type = MI355CV_MAKETYPE(depth, cn);
         cvhalFilter2D* ctx = nullptr;
@@ -950,14 +950,14 @@ MI355CV_API int mi355cv_gaussianBlur(const uchar* src_data, size_t src_step, uch
     // sepFilter2D itself, whose hook (mi355cv_sepFilter, ROI offsets included) reproduces that arithmetic.
     if (margin_left | margin_top | margin_right | margin_bottom)
         return mi355::setError(MI355CV_NOT_IMPLEMENTED, "gaussianBlur: submatrix with real margins is the reference's sepFilter2D case");
-    if (ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE) return mi355::declined(__func__, __LINE__, "ksize_width or ksize_height > lim::GAUSS8U_MAX_KSIZE");
+    MI355_DECLINE_IF(ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE);
     if (sigmaY <= 0) sigmaY = sigmaX;
     std::vector<int64_t> qx, qy;
-    if (!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx)) return mi355::declined(__func__, __LINE__, "!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx)");
-    if (!gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy)) return mi355::declined(__func__, __LINE__, "!gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy)");
+    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx));
+    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy));
     uint16_t kx[lim::GAUSS8U_MAX_KSIZE], ky[lim::GAUSS8U_MAX_KSIZE];
-    for (size_t i = 0; i < ksize_width; i++) { if (qx[i] < 0 || qx[i] > 65535) return mi355::declined(__func__, __LINE__, "qx[i] < 0 || qx[i] > 65535"); kx[i] = (uint16_t)qx[i]; }
-    for (size_t i = 0; i < ksize_height; i++) { if (qy[i] < 0 || qy[i] > 65535) return mi355::declined(__func__, __LINE__, "qy[i] < 0 || qy[i] > 65535"); ky[i] = (uint16_t)qy[i]; }
+    for (size_t i = 0; i < ksize_width; i++) { MI355_DECLINE_IF(qx[i] < 0 || qx[i] > 65535); kx[i] = (uint16_t)qx[i]; }
+    for (size_t i = 0; i < ksize_height; i++) { MI355_DECLINE_IF(qy[i] < 0 || qy[i] > 65535); ky[i] = (uint16_t)qy[i]; }
     bool binom = ksize_width == ksize_height && (ksize_width == 3 || ksize_width == 5);
     if (binom) {
         const uint16_t* b = binomTaps(ksize_width);
@@ -974,16 +974,16 @@ MI355CV_API int mi355cv_gaussianBlurBatch(const uchar* src_data, size_t src_step
         int nframes, int width, int height, int depth, int cn, size_t ksize_width, size_t ksize_height, double sigmaX, double sigmaY, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (depth != MI355CV_8U) return mi355::declined(__func__, __LINE__, "depth != MI355CV_8U");
+    MI355_DECLINE_IF(depth != MI355CV_8U);
     if (nframes < 1 || !(ksize_width & 1) || !(ksize_height & 1) || ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE)
-        return mi355::declined(__func__, __LINE__, "nframes < 1 || even kernel size || ksize > lim::GAUSS8U_MAX_KSIZE");
+        return MI355_DECLINED("nframes < 1 || even kernel size || ksize > lim::GAUSS8U_MAX_KSIZE");
     if (sigmaY <= 0) sigmaY = sigmaX;
     std::vector<int64_t> qx, qy;
     if (!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx) || !gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy))
-        return mi355::declined(__func__, __LINE__, "!gaussianKernelFixedQ");
+        return MI355_DECLINED("!gaussianKernelFixedQ");
     uint16_t kx[lim::GAUSS8U_MAX_KSIZE], ky[lim::GAUSS8U_MAX_KSIZE];
-    for (size_t i = 0; i < ksize_width; i++) { if (qx[i] < 0 || qx[i] > 65535) return mi355::declined(__func__, __LINE__, "qx[i] < 0 || qx[i] > 65535"); kx[i] = (uint16_t)qx[i]; }
-    for (size_t i = 0; i < ksize_height; i++) { if (qy[i] < 0 || qy[i] > 65535) return mi355::declined(__func__, __LINE__, "qy[i] < 0 || qy[i] > 65535"); ky[i] = (uint16_t)qy[i]; }
+    for (size_t i = 0; i < ksize_width; i++) { MI355_DECLINE_IF(qx[i] < 0 || qx[i] > 65535); kx[i] = (uint16_t)qx[i]; }
+    for (size_t i = 0; i < ksize_height; i++) { MI355_DECLINE_IF(qy[i] < 0 || qy[i] > 65535); ky[i] = (uint16_t)qy[i]; }
     bool binom = ksize_width == ksize_height && (ksize_width == 3 || ksize_width == 5);
     if (binom) {
         const uint16_t* b = binomTaps(ksize_width);
@@ -1010,7 +1010,7 @@ MI355CV_API int mi355cv_setParam(const char* key, int value)
 MI355CV_API int mi355cv_copyProbe(const void* src, void* dst, size_t bytes, int perThread, int nt)
 {
     mi355::EntryGuard entry_(__func__);
-    if (!ensureDevice() || (bytes & 15) || perThread < 1) return mi355::declined(__func__, __LINE__, "!ensureDevice() || (bytes & 15) || perThread < 1");
+    MI355_DECLINE_IF(!ensureDevice() || (bytes & 15) || perThread < 1);
     size_t n16 = bytes / 16;
     size_t blocks = (n16 + (size_t)256 * perThread - 1) / ((size_t)256 * perThread);
     if (nt) hipLaunchKernelGGL((k_copy16<true>), dim3((unsigned)blocks), dim3(256), 0, stream(), (const uint4*)src, (uint4*)dst, n16, perThread);
@@ -1023,7 +1023,7 @@ MI355CV_API int mi355cv_copyProbe(const void* src, void* dst, size_t bytes, int 
 MI355CV_API int mi355cv_copyProbeColwalk(const void* src, void* dst, int W, int H, int nframes, int segRows, int unroll)
 {
     mi355::EntryGuard entry_(__func__);
-    if (!ensureDevice() || (W & 15)) return mi355::declined(__func__, __LINE__, "!ensureDevice() || (W & 15)");
+    MI355_DECLINE_IF(!ensureDevice() || (W & 15));
     const int nchunks = W / 16, nstrips = divUp(nchunks, 64), nseg = divUp(H, segRows);
     const long long items = (long long)nstrips * nseg * nframes;
     dim3 grid((unsigned)((items + 3) / 4));
@@ -1042,7 +1042,7 @@ MI355CV_API int mi355cv_getGaussianKernelQ(int n, double sigma, int fractionBits
 {
     mi355::EntryGuard entry_(__func__);
     std::vector<int64_t> q;
-    if (!gaussianKernelFixedQ(n, sigma, fractionBits, q)) return mi355::declined(__func__, __LINE__, "!gaussianKernelFixedQ(n, sigma, fractionBits, q)");
+    MI355_DECLINE_IF(!gaussianKernelFixedQ(n, sigma, fractionBits, q));
     for (int i = 0; i < n; i++) taps[i] = q[i];
     return MI355CV_OK;
 }
@@ -1051,7 +1051,7 @@ MI355CV_API int mi355cv_getGaussianKernel(int n, double sigma, double* taps)
 {
     mi355::EntryGuard entry_(__func__);
     std::vector<double> k;
-    if (!gaussianKernelBitExact(n, sigma, k)) return mi355::declined(__func__, __LINE__, "!gaussianKernelBitExact(n, sigma, k)");
+    MI355_DECLINE_IF(!gaussianKernelBitExact(n, sigma, k));
     for (int i = 0; i < n; i++) taps[i] = k[i];
     return MI355CV_OK;
 }
@@ -1061,7 +1061,7 @@ MI355CV_API int mi355cv_sepSmoothFixedU8(const uchar* src_data, size_t src_step,
         const uint16_t* kx, int kxlen, const uint16_t* ky, int kylen, int border_type)
 {
     mi355::EntryGuard entry_(__func__);
-    if (!kx || !ky) return mi355::declined(__func__, __LINE__, "!kx || !ky");
+    MI355_DECLINE_IF(!kx || !ky);
     bool binom = kxlen == kylen && (kxlen == 3 || kxlen == 5);
     if (binom) {
         const uint16_t* b = binomTaps(kxlen);

@@ -1107,12 +1107,12 @@ thread_local bool t_fourProducts = false;      // set by runMatchMask: its TM_CC
 int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, int nframes, int iw, int ih,
              const uchar* tpl, size_t tstep, int tw, int th, int type, uchar* res, size_t rstep, size_t rframe, int method, WOut* wout = nullptr)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
+    MI355_DECLINE_IF(disabled());
     const int depth = MI355CV_MAT_DEPTH(type), cn = MI355CV_MAT_CN(type);
-    if ((depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > (wout ? 6 : 5)) return mi355::declined(__func__, __LINE__, "(depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > (wout ? 6 : 5)");   // 6: internal, see k_tm_finish_planes
-    if (tw < 1 || th < 1 || iw < tw || ih < th || nframes < 1) return mi355::declined(__func__, __LINE__, "tw < 1 || th < 1 || iw < tw || ih < th || nframes < 1");   // the size swap of :1172-1182 is left to the caller
+    MI355_DECLINE_IF((depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > (wout ? 6 : 5));   // 6: internal, see k_tm_finish_planes
+    MI355_DECLINE_IF(tw < 1 || th < 1 || iw < tw || ih < th || nframes < 1);   // the size swap of :1172-1182 is left to the caller
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     const int e = depth == D8U ? 1 : 4;
     const int rw = iw - tw + 1, rh = ih - th + 1;
     size_t dis = istep, dts, drs = rstep;
@@ -1120,11 +1120,11 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
     if (nframes == 1) {
         di = stg.in(img, istep, (size_t)iw * cn * e, ih, &dis);
         dr = stg.out(res, rstep, (size_t)rw * 4, rh, &drs);
-        if (!di || !dr) return mi355::declined(__func__, __LINE__, "!di || !dr");
-    } else if (!isDevicePtr(img) || !isDevicePtr(res)) return mi355::declined(__func__, __LINE__, "!isDevicePtr(img) || !isDevicePtr(res)");
+        MI355_DECLINE_IF(!di || !dr);
+    } else MI355_DECLINE_IF(!isDevicePtr(img) || !isDevicePtr(res));
     // the template stays where it is (a host template is staged like any input); its statistics are computed on the device
     const uchar* dt = stg.in(tpl, tstep, (size_t)tw * cn * e, th, &dts);
-    if (!dt) return mi355::declined(__func__, __LINE__, "!dt");
+    MI355_DECLINE_IF(!dt);
     NormArgs na; memset(&na, 0, sizeof na);
     na.method = method; na.cn = cn; na.tw = tw; na.th = th; na.rw = rw; na.rh = rh;
     const double area = (double)tw * th; na.invArea = 1. / area;
@@ -1159,10 +1159,10 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
     if (needInt) {
         dsum = (double*)stg.scratch(iframeD * nframes * sizeof(double));
         dsq = (double*)stg.scratch(iframeD * nframes * sizeof(double));
-        if (!dsum || !dsq) return mi355::declined(__func__, __LINE__, "!dsum || !dsq");
+        MI355_DECLINE_IF(!dsum || !dsq);
         const int nseg = divUp(ih, IS_SEG);
         double* aux = (double*)stg.scratch((size_t)nseg * isteps * nframes * sizeof(double));
-        if (!aux) return mi355::declined(__func__, __LINE__, "!aux");
+        MI355_DECLINE_IF(!aux);
         hipLaunchKernelGGL(k_integral_rows<double>, dim3(ih, cn, nframes), dim3(256), 0, st, di, dis, iframe, iw, ih, cn, depth, dsum, isteps, iframeD, dsq, isteps, iframeD);
         integralColumns<double>(dsum, isteps, iframeD, (int)isteps, ih, nframes, aux, st);
         integralColumns<double>(dsq, isteps, iframeD, (int)isteps, ih, nframes, aux, st);
@@ -1187,15 +1187,15 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
         unsigned* w1 = (unsigned*)stg.scratch(wframe * nframes * 4);
         unsigned* w2 = (unsigned*)stg.scratch(wframe * nframes * 4);
         uchar* dtx = (uchar*)stg.scratch((size_t)th * MT_TPITCH);                // signed, zero-padded copy of the template in the kernels' LDS layout
-        if ((!fused && (!s1 || !q1)) || !w1 || !w2 || !dtx) return mi355::declined(__func__, __LINE__, "(!fused && (!s1 || !q1)) || !w1 || !w2 || !dtx");
+        MI355_DECLINE_IF((!fused && (!s1 || !q1)) || !w1 || !w2 || !dtx);
         na.useW = 1; na.wp = wp;
         if (wout) { wout->w1 = w1; wout->w2 = w2; wout->wp = wp; wout->wframe = wframe; }
         const NormArgs* dna = uploadStats(dtx);
-        if (!dna) return mi355::declined(__func__, __LINE__, "!dna");
+        MI355_DECLINE_IF(!dna);
         const bool serial = std::getenv("MI355CV_TM_SERIAL") != nullptr;            // experiments: everything on one stream
         hipStream_t aux = serial ? st : auxStream();
         hipEvent_t evIn = pooledEvent(0), evDone = pooledEvent(1);
-        if ((!serial && !aux) || !evIn || !evDone) return mi355::declined(__func__, __LINE__, "(!serial && !aux) || !evIn || !evDone");
+        MI355_DECLINE_IF((!serial && !aux) || !evIn || !evDone);
         const size_t lds = (size_t)(MT_BM + th - 1) * MT_PPITCH + (size_t)th * MT_TPITCH;
         const int KS = (tw + 62) / 32;
         (void)hipEventRecord(evIn, st);                               // inputs (staged copies, template) are ordered on the main stream
@@ -1338,7 +1338,7 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
                 }
                 if (method != 2) {
                     const NormArgs* dna = uploadStats(nullptr);
-                    if (!dna) return mi355::declined(__func__, __LINE__, "!dna");
+                    MI355_DECLINE_IF(!dna);
                     hipLaunchKernelGGL((k_wsum_rows<float, double>), dim3(ih, 1, nframes), dim3(256), (size_t)(iw + 1) * 8, st, di, dis, nframes > 1 ? iframe : 0, iw, tw, rw, s1, q1, s1frame);
                     hipLaunchKernelGGL((k_wsum_cols<double>), dim3(divUp(rw, 256), divUp(rh, WS_CH), nframes), dim3(256), 0, st, s1, q1, s1frame, th, rw, rh, w1, w2, wframe);
                     hipLaunchKernelGGL(k_tm_finish_f, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, rf, drs, rfr, w1, w2, wframe, rw, dna);
@@ -1353,7 +1353,7 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
             hipLaunchKernelGGL(k_ccorr_direct, grid, dim3(256), 0, st, di, dis, iframe, dt, dts, tw, th, cn, depth, reinterpret_cast<float*>(dr), drs, rframe, rw, rh);
         if (method != 2) {
             const NormArgs* dna = uploadStats(nullptr);
-            if (!dna) return mi355::declined(__func__, __LINE__, "!dna");
+            MI355_DECLINE_IF(!dna);
             dim3 g2(divUp(rw, 64), divUp(rh, 4), nframes);
             hipLaunchKernelGGL(k_tm_normalize, g2, dim3(256), 0, st, reinterpret_cast<float*>(dr), drs, rframe, dsum, dsq, isteps, iframeD, dna);
         }
@@ -1434,13 +1434,13 @@ __global__ __launch_bounds__(256) void k_tm_mask_finish(const float* __restrict_
 int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int ih, const uchar* tpl, size_t tstep, int tw, int th, int type,
                  const uchar* mask, size_t mstep, int mtype, uchar* res, size_t rstep, int method)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
+    MI355_DECLINE_IF(disabled());
     const int depth = MI355CV_MAT_DEPTH(type), cn = MI355CV_MAT_CN(type), mdepth = MI355CV_MAT_DEPTH(mtype), mcn = MI355CV_MAT_CN(mtype);
-    if ((depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > 5) return mi355::declined(__func__, __LINE__, "(depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > 5");
-    if ((mdepth != D8U && mdepth != D32F) || (mcn != 1 && mcn != cn) || !mask) return mi355::declined(__func__, __LINE__, "(mdepth != D8U && mdepth != D32F) || (mcn != 1 && mcn != cn) || !mask");   // CV_Assert :764-765
-    if (tw < 1 || th < 1 || iw < tw || ih < th) return mi355::declined(__func__, __LINE__, "tw < 1 || th < 1 || iw < tw || ih < th");                             // CV_Assert :767
+    MI355_DECLINE_IF((depth != D8U && depth != D32F) || cn < 1 || cn > 4 || method < 0 || method > 5);
+    MI355_DECLINE_IF((mdepth != D8U && mdepth != D32F) || (mcn != 1 && mcn != cn) || !mask);   // CV_Assert :764-765
+    MI355_DECLINE_IF(tw < 1 || th < 1 || iw < tw || ih < th);                             // CV_Assert :767
     Stager stg;
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     hipStream_t st = stream();
     const int e = depth == D8U ? 1 : 4, me = mdepth == D8U ? 1 : 4;
     const int rw = iw - tw + 1, rh = ih - th + 1;
@@ -1486,7 +1486,7 @@ int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int 
     size_t dis = istep, drs = rstep;
     const uchar* di = stg.in(img, istep, (size_t)iw * cn * e, ih, &dis);
     uchar* dr = stg.out(res, rstep, (size_t)rw * 4, rh, &drs);
-    if (!di || !dr) return mi355::declined(__func__, __LINE__, "!di || !dr");
+    MI355_DECLINE_IF(!di || !dr);
     const bool needI2 = method != 2 && method != 4;
     const int ipitch = (iw + 3) & ~3; const size_t iplane = (size_t)ipitch * ih;
     const int rpitch = (rw + 3) & ~3; const size_t rplane = (size_t)rpitch * rh;
@@ -1499,7 +1499,7 @@ int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int 
         for (size_t i = 0; i < nt * cn; i++) { K8[i] = (uchar)(T[i] * M[i]); M8[i] = (uchar)M[i]; }
         uchar* dk8 = (uchar*)stg.param(K8.data(), nt * cn);
         uchar* dm8 = needI2 ? (uchar*)stg.param(M8.data(), nt * cn) : nullptr;
-        if (!b8 || !part || !dk8 || (needI2 && !dm8)) return mi355::declined(__func__, __LINE__, "out of scratch memory for the byte planes");
+        if (!b8 || !part || !dk8 || (needI2 && !dm8)) return MI355_DECLINED("out of scratch memory for the byte planes");
         uchar* pI = b8; uchar* pHi = needI2 ? b8 + plane8 * cn : nullptr; uchar* pLo = needI2 ? b8 + 2 * plane8 * cn : nullptr;
         hipLaunchKernelGGL(k_tm_mask_planes_u8, dim3(divUp(p8, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, pI, pHi, pLo, p8, plane8);
         fin.pitch = rpitch; fin.plane = rplane;
@@ -1525,7 +1525,7 @@ int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int 
     float* dk = (float*)stg.param(K.data(), nt * cn * 4);
     float* dm = coeff ? (float*)stg.param(M.data(), nt * cn * 4) : nullptr;
     float* dm2 = (needI2 || (method == 5 && !binary)) ? (float*)stg.param(M2.data(), nt * cn * 4) : nullptr;
-    if (!f || (needI2 && !f2) || !part || !dk || (coeff && !dm) || ((needI2 || (method == 5 && !binary)) && !dm2)) return mi355::declined(__func__, __LINE__, "out of scratch memory for the float planes");
+    if (!f || (needI2 && !f2) || !part || !dk || (coeff && !dm) || ((needI2 || (method == 5 && !binary)) && !dm2)) return MI355_DECLINED("out of scratch memory for the float planes");
     hipLaunchKernelGGL(k_tm_mask_planes, dim3(divUp(ipitch, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, depth, f, f2, ipitch, iplane);
     fin.pitch = rpitch; fin.plane = rplane;
     struct FourProducts { FourProducts() { t_fourProducts = true; } ~FourProducts() { t_fourProducts = false; } } guard;
@@ -1596,7 +1596,7 @@ MI355CV_API int mi355cv_integral(int depth, int sdepth, int sqdepth, const uchar
                                  uchar* sqsum_data, size_t sqsum_step, uchar* tilted_data, size_t tilted_step, int width, int height, int cn)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || !sum_data || !src_data) return mi355::declined(__func__, __LINE__, "disabled() || !sum_data || !src_data");
+    MI355_DECLINE_IF(disabled() || !sum_data || !src_data);
     if (!integralOrderedTriple(depth, sdepth, sqdepth) || cn < 1)
         return setError(MI355CV_NOT_IMPLEMENTED, "integral: depths %d -> sum %d, sqsum %d%s, %d channels: not a row of the reference's table", depth, sdepth, sqdepth, sqsum_data ? "" : " (no sqsum)", cn);
     const bool tiledKind = !tilted_data && cn <= 4 && depth == D8U && (sdepth == D32S || sdepth == D64F) && (!sqsum_data || sqdepth == D64F) &&
@@ -1606,34 +1606,34 @@ MI355CV_API int mi355cv_integral(int depth, int sdepth, int sqdepth, const uchar
             return setError(MI355CV_NOT_IMPLEMENTED, "integral: CV_8U -> CV_32F sums past 2^24 without a squared / tilted sum depend on the CPU's vector width");
         const size_t e1 = sdepth == D64F ? 8 : 4, e2 = sqdepth == D64F ? 8 : 4, es = depth == D8U ? 1 : depth == D32F ? 4 : depth == D64F ? 8 : 2;
         if (width <= 0 || height <= 0 || (sum_step % e1) || (sqsum_data && (sqsum_step % e2)) || (tilted_data && (tilted_step % e1)) || (src_step % es))
-            return mi355::declined(__func__, __LINE__, "width <= 0 || height <= 0 || a step that is not a multiple of its element size");
-        if ((double)(width + 1) * cn * (height + 1) >= 2147483647.0) return mi355::declined(__func__, __LINE__, "more than 2^31 elements");
+            return MI355_DECLINED("width <= 0 || height <= 0 || a step that is not a multiple of its element size");
+        if ((double)(width + 1) * cn * (height + 1) >= 2147483647.0) return MI355_DECLINED("more than 2^31 elements");
         Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-        if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+        MI355_DECLINE_IF(!ensureDevice());
         // (HOST_HEAVY: the reference's scalar loops take 10-60 ms per 4K image on one core -- worth two PCIe crossings, unlike the 8-bit vector paths of the tiled kind)
-        if (hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY))");
+        MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
         size_t dss, d1, d2 = 0, d3 = 0;
         const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * es, height, &dss);
         uchar* s1 = stg.out(sum_data, sum_step, (size_t)(width + 1) * cn * e1, height + 1, &d1);
         uchar* s2 = sqsum_data ? stg.out(sqsum_data, sqsum_step, (size_t)(width + 1) * cn * e2, height + 1, &d2) : nullptr;
         uchar* s3 = tilted_data ? stg.out(tilted_data, tilted_step, (size_t)(width + 1) * cn * e1, height + 1, &d3) : nullptr;
         void* aux = tilted_data ? stg.scratch(integralOrderedAuxBytes(width, height, cn, sdepth, true)) : nullptr;
-        if (!ds || !s1 || (sqsum_data && !s2) || (tilted_data && (!s3 || !aux))) return mi355::declined(__func__, __LINE__, "staging / scratch for the ordered integral");
+        if (!ds || !s1 || (sqsum_data && !s2) || (tilted_data && (!s3 || !aux))) return MI355_DECLINED("staging / scratch for the ordered integral");
         if (!integralOrdered(depth, sdepth, sqdepth, ds, dss, s1, d1, s2, d2, s3, d3, width, height, cn, aux, stream()))
-            return mi355::declined(__func__, __LINE__, "!integralOrdered(...)");
+            return MI355_DECLINED("!integralOrdered(...)");
         noteKernel("k_iseq_rows + k_iseq_cols%s (ordered sums, depths %d -> %d / %d)", tilted_data ? " + k_iseq_tbuf / tcol0 / tdiag" : "", depth, sdepth, sqdepth);
         return stg.finish("integral");
     }
     const size_t se = sdepth == D32S ? 4 : 8;
-    if (width <= 0 || height <= 0 || (sum_step % se) || (sqsum_data && (sqsum_step % 8))) return mi355::declined(__func__, __LINE__, "width <= 0 || height <= 0 || (sum_step % se) || (sqsum_data && (sqsum_step % 8))");
+    MI355_DECLINE_IF(width <= 0 || height <= 0 || (sum_step % se) || (sqsum_data && (sqsum_step % 8)));
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)width * height, minPixels())) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)width * height, minPixels())");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels()));
     size_t dss, d1, d2 = 0;
     const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * (depth == D8U ? 1 : 4), height, &dss);
     uchar* s1 = stg.out(sum_data, sum_step, (size_t)(width + 1) * cn * se, height + 1, &d1);
     uchar* s2 = sqsum_data ? stg.out(sqsum_data, sqsum_step, (size_t)(width + 1) * cn * 8, height + 1, &d2) : nullptr;
-    if (!ds || !s1 || (sqsum_data && !s2)) return mi355::declined(__func__, __LINE__, "!ds || !s1 || (sqsum_data && !s2)");
+    MI355_DECLINE_IF(!ds || !s1 || (sqsum_data && !s2));
     const int Wc = (width + 1) * cn, nseg = divUp(height, IS_SEG);
     hipStream_t st = stream();
     static const bool tiledOff = getenv("MI355CV_INTEGRAL_TILED") && atoi(getenv("MI355CV_INTEGRAL_TILED")) == 0;
@@ -1644,7 +1644,7 @@ MI355CV_API int mi355cv_integral(int depth, int sdepth, int sqdepth, const uchar
             return stg.finish("integral");
     }
     void* aux = stg.scratch((size_t)nseg * Wc * 8);
-    if (!aux) return mi355::declined(__func__, __LINE__, "!aux");
+    MI355_DECLINE_IF(!aux);
     const size_t ldsFast = (((size_t)(width + 1) * se + 15) & ~(size_t)15) + (s2 ? (size_t)(width + 1) * 8 : 0);
     const bool fastRows = depth == D8U && cn == 1 && ldsFast <= 60 * 1024;
     if (sdepth == D32S) {
@@ -1667,10 +1667,10 @@ MI355CV_API int mi355cv_integralBatch(const uchar* src_data, size_t src_step, si
                                       uchar* sqsum_data, size_t sqsum_step, size_t sqsum_frame_stride, int nframes, int width, int height, int sdepth)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || !src_data || !sum_data || nframes < 1 || width <= 0 || height <= 0 || (sdepth != D32S && sdepth != D64F)) return mi355::declined(__func__, __LINE__, "disabled() || !src_data || !sum_data || nframes < 1 || width <= 0 || height <= 0 || (sdepth != D32S && sdepth != D64F)");
+    MI355_DECLINE_IF(disabled() || !src_data || !sum_data || nframes < 1 || width <= 0 || height <= 0 || (sdepth != D32S && sdepth != D64F));
     const size_t se = sdepth == D32S ? 4 : 8;
-    if ((sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8)))) return mi355::declined(__func__, __LINE__, "(sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8)))");
-    if (sdepth == D32S && (double)width * height * 255.0 > 2147483647.0) return mi355::declined(__func__, __LINE__, "sdepth == D32S && (double)width * height * 255.0 > 2147483647.0");
+    MI355_DECLINE_IF((sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8))));
+    MI355_DECLINE_IF(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(sum_data) || (sqsum_data && !isDevicePtr(sqsum_data)))
         return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: device-resident frames only");

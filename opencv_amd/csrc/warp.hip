@@ -2502,30 +2502,30 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
             const double* M, int kind, int interpolation, int borderType, const double* bv,
             const float* mapx, size_t mxstep, const float* mapy, size_t mystep, int nframes = 1, size_t sframe = 0, size_t dframe = 0)
 {
-    if (disabled()) return mi355::declined(__func__, __LINE__, "disabled()");
+    MI355_DECLINE_IF(disabled());
     const int depth = MI355CV_MAT_DEPTH(src_type), cn = MI355CV_MAT_CN(src_type);
     const bool is64 = depth == MI355CV_64F;                                                      // CV_64F images: the per-pixel kernel k_warp64
     // channels: the samplers loop over them (border value of channel k = borderValue[k & 3], imgwarp.cpp:340 / :692); the reference itself asserts <= 4 for bicubic / Lanczos
     // (imgwarp.cpp:2795), and so does this entry further down
-    if (!(depthOk(depth) || is64) || cn < 1 || cn > 512 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return mi355::declined(__func__, __LINE__, "depth is none of 8U / 16U / 16S / 32F / 64F || cn < 1 || cn > 512 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0");
-    if (is64 && (kind == 6 || kind == 7)) return mi355::declined(__func__, __LINE__, "warpPolar on CV_64F images");
+    if (!(depthOk(depth) || is64) || cn < 1 || cn > 512 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0) return MI355_DECLINED("depth is none of 8U / 16U / 16S / 32F / 64F || cn < 1 || cn > 512 || sw <= 0 || sh <= 0 || dw <= 0 || dh <= 0");
+    if (is64 && (kind == 6 || kind == 7)) return MI355_DECLINED("warpPolar on CV_64F images");
     const bool relative = (interpolation & 32) != 0 && kind >= 2 && kind <= 5;              // WARP_RELATIVE_MAP (cv::remap only, imgwarp.cpp:1724)
     if (relative) interpolation &= ~32;
     if (interpolation == MI355CV_INTER_AREA) interpolation = MI355CV_INTER_LINEAR;          // imgwarp.cpp:2818
     if (interpolation != MI355CV_INTER_NEAREST && interpolation != MI355CV_INTER_LINEAR && interpolation != MI355CV_INTER_CUBIC && interpolation != MI355CV_INTER_LANCZOS4)
-        return mi355::declined(__func__, __LINE__, "interpolation is none of NEAREST, LINEAR, CUBIC, AREA, LANCZOS4");
+        return MI355_DECLINED("interpolation is none of NEAREST, LINEAR, CUBIC, AREA, LANCZOS4");
     const bool taps = interpolation == MI355CV_INTER_CUBIC || interpolation == MI355CV_INTER_LANCZOS4;
-    if (taps && cn > 4) return mi355::declined(__func__, __LINE__, "bicubic / Lanczos sampling of more than 4 channels (the reference asserts on it)");
-    if (taps && (kind == 5 || kind == 6 || kind == 7)) return mi355::declined(__func__, __LINE__, "bicubic / Lanczos sampling with a CV_16SC2 map alone, or in warpPolar");
-    if (borderType < 0 || borderType > B_TRANSPARENT) return mi355::declined(__func__, __LINE__, "borderType < 0 || borderType > B_TRANSPARENT");
-    if (sw > 32767 || sh > 32767) return mi355::declined(__func__, __LINE__, "sw > 32767 || sh > 32767");                         // coordinates saturate to short in the reference
+    if (taps && cn > 4) return MI355_DECLINED("bicubic / Lanczos sampling of more than 4 channels (the reference asserts on it)");
+    if (taps && (kind == 5 || kind == 6 || kind == 7)) return MI355_DECLINED("bicubic / Lanczos sampling with a CV_16SC2 map alone, or in warpPolar");
+    MI355_DECLINE_IF(borderType < 0 || borderType > B_TRANSPARENT);
+    MI355_DECLINE_IF(sw > 32767 || sh > 32767);                         // coordinates saturate to short in the reference
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src, (size_t)dw * dh, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src, (size_t)dw * dh, minPixels(HOST_HEAVY))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)dw * dh, minPixels(HOST_HEAVY)));
     if (nframes < 1 || (nframes > 1 && (!isDevicePtr(src) || !isDevicePtr(dst))))
         return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
     const short* g_tabDev = deviceTab();
-    if (!g_tabDev) return mi355::declined(__func__, __LINE__, "!g_tabDev");
+    MI355_DECLINE_IF(!g_tabDev);
     const int e = is64 ? 8 : eszOf(depth);
     size_t dss, dds, mxs = mxstep, mys = mystep;
     const uchar* ds = stg.in(src, sstep, (size_t)sw * cn * e, sh, &dss);
@@ -2534,31 +2534,31 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
         // untouched pixels must keep their previous contents: stage dst in as well
         const uchar* din = stg.in(dst, dstep, (size_t)dw * cn * e, dh, &dds);
         size_t dds2; dd = stg.out(dst, dstep, (size_t)dw * cn * e, dh, &dds2);
-        if (!din || !dd) return mi355::declined(__func__, __LINE__, "!din || !dd");
-        if (hipMemcpy2DAsync(dd, dds2, din, dds, (size_t)dw * cn * e, dh, hipMemcpyDeviceToDevice, stream()) != hipSuccess) return mi355::declined(__func__, __LINE__, "hipMemcpy2DAsync(dd, dds2, din, dds, (size_t)dw * cn * e, dh, hipMemcpyDeviceToDevice, stream()) != hipSuccess");
+        MI355_DECLINE_IF(!din || !dd);
+        MI355_DECLINE_IF(hipMemcpy2DAsync(dd, dds2, din, dds, (size_t)dw * cn * e, dh, hipMemcpyDeviceToDevice, stream()) != hipSuccess);
         dds = dds2;
     } else dd = stg.out(dst, dstep, (size_t)dw * cn * e, dh, &dds);
     const uchar* dmx = nullptr; const uchar* dmy = nullptr;
     if (kind == 2) {
         dmx = stg.in((const uchar*)mapx, mxstep, (size_t)dw * 4, dh, &mxs);
         dmy = stg.in((const uchar*)mapy, mystep, (size_t)dw * 4, dh, &mys);
-        if (!dmx || !dmy) return mi355::declined(__func__, __LINE__, "!dmx || !dmy");
+        MI355_DECLINE_IF(!dmx || !dmy);
     } else if (kind == 3) {                                                                  // one CV_32FC2 map
         dmx = stg.in((const uchar*)mapx, mxstep, (size_t)dw * 8, dh, &mxs);
-        if (!dmx) return mi355::declined(__func__, __LINE__, "!dmx");
+        MI355_DECLINE_IF(!dmx);
     } else if (kind == 4 || kind == 5) {                                                     // CV_16SC2 (+ CV_16UC1 fractions)
         dmx = stg.in((const uchar*)mapx, mxstep, (size_t)dw * 4, dh, &mxs);
         if (kind == 4) dmy = stg.in((const uchar*)mapy, mystep, (size_t)dw * 2, dh, &mys);
-        if (!dmx || (kind == 4 && !dmy)) return mi355::declined(__func__, __LINE__, "!dmx || (kind == 4 && !dmy)");
+        MI355_DECLINE_IF(!dmx || (kind == 4 && !dmy));
     } else if (kind == 7) {                                                                  // inverse warpPolar: the 512-float log table (host array)
         dmx = (const uchar*)stg.param(mapx, 512 * sizeof(float));
-        if (!dmx) return mi355::declined(__func__, __LINE__, "!dmx");
+        MI355_DECLINE_IF(!dmx);
     } else if (kind == 6) {                                                                  // warpPolar tables (host arrays: dw radii, dh (cos, sin) pairs)
         dmx = (const uchar*)stg.param(mapx, (size_t)dw * 4);
         dmy = (const uchar*)stg.param(mapy, (size_t)dh * 16);
-        if (!dmx || !dmy) return mi355::declined(__func__, __LINE__, "!dmx || !dmy");
+        MI355_DECLINE_IF(!dmx || !dmy);
     }
-    if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
+    MI355_DECLINE_IF(!ds || !dd);
     SampleArgs s; s.sw = sw; s.sh = sh; s.depth = depth; s.cn = cn; s.linear = interpolation == MI355CV_INTER_LINEAR ? 1 : taps ? interpolation : 0; s.border = borderType;
     for (int k = 0; k < 4; k++) { s.cval[k] = bv ? (float)bv[k] : 0.f; s.cvalD[k] = bv ? bv[k] : 0.0; }
     WarpArgs w; memset(&w, 0, sizeof w);
@@ -2570,7 +2570,7 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
     { static const int pe = [] { const char* v = getenv("MI355CV_PERSP_EXACT"); return v ? atoi(v) : 0; }(); w.pexact = pe; }
     if (is64) {
         const TapTabs* tt = deviceTapTabs();
-        if (!tt) return mi355::declined(__func__, __LINE__, "the bicubic / Lanczos weight tables could not be placed on the device");
+        if (!tt) return MI355_DECLINED("the bicubic / Lanczos weight tables could not be placed on the device");
         dim3 grid(divUp(dw, 64), divUp(dh, 4), nframes);
         hipLaunchKernelGGL(k_warp64, grid, dim3(256), 0, stream(), ds, dss, dd, dds, s, w, tt->cubic1, tt->lanczos1, dmx, mxs, dmy, mys);
         noteKernel("k_warp64 grid=%ux%ux%u x256 kind=%d mode=%d", grid.x, grid.y, grid.z, kind, s.linear);
@@ -2579,14 +2579,14 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
     if (taps) {
         // bicubic / Lanczos: the per-pixel kernel over the shared coordinate generation
         const TapTabs* tt = deviceTapTabs();
-        if (!tt) return mi355::declined(__func__, __LINE__, "the bicubic / Lanczos weight tables could not be placed on the device");
+        if (!tt) return MI355_DECLINED("the bicubic / Lanczos weight tables could not be placed on the device");
         // the LDS form (MI355CV_WARP_TAPS_LDS=0 keeps the plain per-pixel kernel for A/B runs): 1-, 3- and 4-channel images whose rows can be read as unaligned dwords
         // affine maps: the column / row terms once per call
         int* terms = nullptr;
         if (kind == 0) {
             terms = (int*)stg.scratch((size_t)(2 * dw + 2 * dh) * sizeof(int));
             uint32_t* work0 = (uint32_t*)stg.scratch(sizeof(uint32_t));
-            if (!terms || !work0) return mi355::declined(__func__, __LINE__, "scratch for the coordinate terms");
+            if (!terms || !work0) return MI355_DECLINED("scratch for the coordinate terms");
             hipLaunchKernelGGL(k_warp32_terms, dim3(divUp(std::max(dw, dh), 256)), dim3(256), 0, stream(), w, terms, work0);
         }
         // CV_8U bicubic on the tile path of warp8.h.  Round 5, first run on the GPU (profiles/r05_warp_taps_tile_call1.txt, 4K, 7 degrees): one channel 42.7 us against the
@@ -2632,7 +2632,7 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
             // one flag byte per 64-pixel row strip: set by the LDS kernel where pixels next to the border were left out
             const size_t strips = (size_t)tilesX * dh * nframes;
             uchar* stripFlag = (uchar*)stg.scratch(strips);
-            if (!stripFlag || hipMemsetAsync(stripFlag, 0, strips, stream()) != hipSuccess) return mi355::declined(__func__, __LINE__, "scratch for the border-strip flags");
+            if (!stripFlag || hipMemsetAsync(stripFlag, 0, strips, stream()) != hipSuccess) return MI355_DECLINED("scratch for the border-strip flags");
 #define WTA(KS_, DEP_, CN_, BLK_, PP_) do { \
                 if (lds > 64 * 1024) (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_warp_taps_lds<KS_, DEP_, CN_, BLK_, PP_>), hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); \
                 hipLaunchKernelGGL((k_warp_taps_lds<KS_, DEP_, CN_, BLK_, PP_>), dim3(gridN), dim3(BLK_), lds, stream(), ds, dss, dd, dds, s, w, tI, t1, dmx, mxs, dmy, mys, tilesX, tilesY, nframes, \
@@ -2755,11 +2755,11 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
                 segs = divUp(dh, a.segRows);
                 int* terms = (int*)stg.scratch((size_t)(2 * dw + 2 * dh) * sizeof(int));
                 uint32_t* work = (uint32_t*)stg.scratch(16);
-                if (!terms || !work) return mi355::declined(__func__, __LINE__, "scratch for the coordinate terms");
+                if (!terms || !work) return MI355_DECLINED("scratch for the coordinate terms");
                 const size_t lds = (size_t)WS_NR * a.pitch * sizeof(float);
                 const size_t nflags = (size_t)nframes * dh * strips;                       // one byte per wave and row: "this row piece has lanes left to the generic sampler"
                 uchar* flags = (uchar*)stg.scratch(nflags);
-                if (!flags) return mi355::declined(__func__, __LINE__, "scratch for the row-piece flags");
+                if (!flags) return MI355_DECLINED("scratch for the row-piece flags");
                 static bool attr[64] = {}; const int dv = activeDevice() & 63;
                 if (!attr[dv]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_warp32_strip), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attr[dv] = true; }
                 hipLaunchKernelGGL(k_warp32_terms, dim3(divUp(std::max(dw, dh), 256)), dim3(256), 0, stream(), w, terms, work);
@@ -2780,7 +2780,7 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
             const size_t ntiles = (size_t)g3.x * g3.y * nframes;
             int* terms = (int*)stg.scratch((size_t)(2 * dw + 2 * dh) * sizeof(int));
             uint32_t* work = (uint32_t*)stg.scratch((ntiles + 1) * sizeof(uint32_t));
-            if (!terms || !work) return mi355::declined(__func__, __LINE__, "scratch for the coordinate terms / the tile list");
+            if (!terms || !work) return MI355_DECLINED("scratch for the coordinate terms / the tile list");
             hipLaunchKernelGGL(k_warp32_terms, dim3(divUp(std::max(dw, dh), 256)), dim3(256), 0, stream(), w, terms, work);
             hipLaunchKernelGGL(k_warp32_tile, dim3(divUp((int)g3.x, tpw32), g3.y, nframes), dim3(256), 0, stream(), ds, (uint32_t)dss, dd, (uint32_t)dds, s, w, tpw32, terms, work);
             hipLaunchKernelGGL(k_warp32_rest, dim3((unsigned)std::min<size_t>(ntiles, 1u << 22)), dim3(256), 0, stream(), ds, (uint32_t)dss, dd, (uint32_t)dds, s, w, g_tabDev, terms, work);
@@ -2808,9 +2808,9 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
                      uchar* dst_data, size_t dst_step, size_t dst_frame, int dst_width, int dst_height, int nframes, double inv_scale_x, double inv_scale_y,
                      int interpolation)
 {
-    if (disabled() || nframes < 1) return mi355::declined(__func__, __LINE__, "disabled() || nframes < 1");
+    MI355_DECLINE_IF(disabled() || nframes < 1);
     const int depth = MI355CV_MAT_DEPTH(src_type), cn = MI355CV_MAT_CN(src_type);
-    if (!depthOk(depth) || cn < 1 || cn > 512 || src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0) return mi355::declined(__func__, __LINE__, "!depthOk(depth) || cn < 1 || cn > 512 || src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0");
+    MI355_DECLINE_IF(!depthOk(depth) || cn < 1 || cn > 512 || src_width <= 0 || src_height <= 0 || dst_width <= 0 || dst_height <= 0);
     if (inv_scale_x < 2.220446049250313e-16 || inv_scale_y < 2.220446049250313e-16) {        // resize.cpp:3834-3838
         inv_scale_x = (double)dst_width / src_width; inv_scale_y = (double)dst_height / src_height;
     }
@@ -2822,7 +2822,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
     if (interpolation == MI355CV_INTER_NEAREST) a.mode = 0;
     else if (interpolation == MI355CV_INTER_NEAREST_EXACT) {
         // resizeNN_bitexact (resize.cpp:1267-1289): source pixel = (ifx * x + ifx0) >> 16 in int arithmetic, steps rounded to 16.16, pixel centres aligned
-        if (src_width >= 32768 || src_height >= 32768) return mi355::declined(__func__, __LINE__, "src_width >= 32768 || src_height >= 32768");          // (size << 16) must stay an int, as in the reference
+        MI355_DECLINE_IF(src_width >= 32768 || src_height >= 32768);          // (size << 16) must stay an int, as in the reference
         a.mode = 0; a.nnExact = 1;
         a.ifx = ((src_width << 16) + dst_width / 2) / dst_width; a.ifx0 = a.ifx / 2 - src_width % 2;
         a.ify = ((src_height << 16) + dst_height / 2) / dst_height; a.ify0 = a.ify / 2 - src_height % 2;
@@ -2838,12 +2838,12 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         }
         else if (interpolation == 2 /*INTER_CUBIC*/) a.mode = 5;
         else if (interpolation == 4 /*INTER_LANCZOS4*/) a.mode = 6;
-        else return mi355::declined(__func__, __LINE__, nullptr);                                                // LINEAR_EXACT on other depths
+        else return MI355_DECLINED(nullptr);                                                // LINEAR_EXACT on other depths
     }
-    if (a.mode == 4 && cn > 4) return mi355::declined(__func__, __LINE__, "true INTER_AREA of more than 4 channels (the reference asserts on it, resize.cpp:4045)");
+    if (a.mode == 4 && cn > 4) return MI355_DECLINED("true INTER_AREA of more than 4 channels (the reference asserts on it, resize.cpp:4045)");
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-    if (hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(a.mode >= 3 ? HOST_HEAVY : HOST_CHEAP))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(a.mode >= 3 ? HOST_HEAVY : HOST_CHEAP))");
+    MI355_DECLINE_IF(!ensureDevice());
+    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(a.mode >= 3 ? HOST_HEAVY : HOST_CHEAP)));
     const int e = eszOf(depth);
     if (nframes > 1) {
         // batches are an HBM-resident construct; nearest / bilinear / area-fast run as ONE launch (grid z = frame), the table-driven modes frame by frame
@@ -2861,7 +2861,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
     size_t dss, dds;
     const uchar* ds = stg.in(src_data, src_step, (size_t)src_width * cn * e, src_height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)dst_width * cn * e, dst_height, &dds);
-    if (!ds || !dd) return mi355::declined(__func__, __LINE__, "!ds || !dd");
+    MI355_DECLINE_IF(!ds || !dd);
     if (a.mode == 5 || a.mode == 6) {
         dim3 gt(divUp(dst_width * cn, 64), divUp(dst_height, 16)), g1(divUp(dst_width * cn, 64), divUp(dst_height, 4));
         int rows = 0, unused = 0;
@@ -2881,8 +2881,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         };
         if (a.mode == 5) {
             const CubicTap *dxt, *dyt;
-            if (!cachedTab<CubicTap>(5, dst_width, a.scale_x, 4, buildCubicTab, &dxt, &unused, &keepX) || !cachedTab<CubicTap>(5, dst_height, a.scale_y, 4, buildCubicTab, &dyt, &rows, &keepY))
-                return mi355::declined(__func__, __LINE__, "!cachedTab<CubicTap>(5, dst_width, a.scale_x, 4, buildCubicTab, &dxt, &unused, &keepX) || !cachedTab<CubicTap>(5, dst_height, a.scale_y, 4, buildCubicTab, &dyt, &rows, &keepY)");
+            MI355_DECLINE_IF(!cachedTab<CubicTap>(5, dst_width, a.scale_x, 4, buildCubicTab, &dxt, &unused, &keepX) || !cachedTab<CubicTap>(5, dst_height, a.scale_y, 4, buildCubicTab, &dyt, &rows, &keepY));
             const TapT<4>* tx = reinterpret_cast<const TapT<4>*>(dxt); const TapT<4>* ty = reinterpret_cast<const TapT<4>*>(dyt);
 #define RZ_TILED(T_, NT_) hipLaunchKernelGGL((k_resize_tiled<T_, NT_>), gt, dim3(256), (size_t)rows * 256, stream(), ds, dss, dd, dds, src_width, src_height, dst_width, dst_height, cn, tx, ty)
 #define RZ_BY_DEPTH(M_) do { if (depth == D8U) M_(uchar); else if (depth == D16U) M_(unsigned short); else if (depth == D16S) M_(short); else M_(float); } while (0)
@@ -2894,8 +2893,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
             } else if (rows) RZ_BY_DEPTH(RZ_T4); else RZ_BY_DEPTH(RZ_C);
         } else {
             const LanczosTap *dxt, *dyt;
-            if (!cachedTab<LanczosTap>(6, dst_width, a.scale_x, 8, buildLanczosTab, &dxt, &unused, &keepX) || !cachedTab<LanczosTap>(6, dst_height, a.scale_y, 8, buildLanczosTab, &dyt, &rows, &keepY))
-                return mi355::declined(__func__, __LINE__, "!cachedTab<LanczosTap>(6, dst_width, a.scale_x, 8, buildLanczosTab, &dxt, &unused, &keepX) || !cachedTab<LanczosTap>(6, dst_height, a.scale_y, 8, buildLanczosTab, &dyt, &rows, &keepY)");
+            MI355_DECLINE_IF(!cachedTab<LanczosTap>(6, dst_width, a.scale_x, 8, buildLanczosTab, &dxt, &unused, &keepX) || !cachedTab<LanczosTap>(6, dst_height, a.scale_y, 8, buildLanczosTab, &dyt, &rows, &keepY));
             const TapT<8>* tx = reinterpret_cast<const TapT<8>*>(dxt); const TapT<8>* ty = reinterpret_cast<const TapT<8>*>(dyt);
 #define RZ_T8(T_) RZ_TILED(T_, 8)
 #define RZ_L(T_) hipLaunchKernelGGL(k_resize_lanczos<T_>, g1, dim3(256), 0, stream(), ds, dss, dd, dds, src_width, src_height, dst_width, dst_height, cn, dxt, dyt)
@@ -2916,8 +2914,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         const int shift = depth == D8U ? 8 : 16;
         const ExactTap *dx, *dy;
         DevRef keepX, keepY;                                        // the tables stay alive until the launch below is enqueued
-        if (!cachedExactTab(inv_scale_x, src_width, dst_width, shift, &dx, &keepX) || !cachedExactTab(inv_scale_y, src_height, dst_height, shift, &dy, &keepY))
-            return mi355::declined(__func__, __LINE__, "!cachedExactTab(inv_scale_x, src_width, dst_width, shift, &dx, &keepX) || !cachedExactTab(inv_scale_y, src_height, dst_height, shift, &dy, &keepY)");
+        MI355_DECLINE_IF(!cachedExactTab(inv_scale_x, src_width, dst_width, shift, &dx, &keepX) || !cachedExactTab(inv_scale_y, src_height, dst_height, shift, &dy, &keepY));
         dim3 g7(divUp(dst_width * cn, 64), divUp(dst_height, 4));
         if (depth == D8U) hipLaunchKernelGGL((k_resize_exact<uchar, 8>), g7, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, dx, dy);
         else if (depth == D16U) hipLaunchKernelGGL((k_resize_exact<unsigned short, 16>), g7, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, dx, dy);
@@ -2941,7 +2938,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
     }
     if (a.mode == 4) {
         AreaDev ax, ay;
-        if (!cachedAreaTab(src_width, dst_width, a.scale_x, &ax) || !cachedAreaTab(src_height, dst_height, a.scale_y, &ay)) return mi355::declined(__func__, __LINE__, "!cachedAreaTab(src_width, dst_width, a.scale_x, &ax) || !cachedAreaTab(src_height, dst_height, a.scale_y, &ay)");
+        MI355_DECLINE_IF(!cachedAreaTab(src_width, dst_width, a.scale_x, &ax) || !cachedAreaTab(src_height, dst_height, a.scale_y, &ay));
         const AreaTap* dxt = ax.tab; const int* dxo = ax.ofs; const AreaTap* dyt = ay.tab; const int* dyo = ay.ofs;
         dim3 g4(divUp(dst_width * cn, 64), divUp(dst_height, 4));
 #define RA(T_) hipLaunchKernelGGL(k_resize_area<T_>, g4, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, depth, dxt, dxo, dyt, dyo)
@@ -3021,7 +3018,7 @@ MI355CV_API int mi355cv_warpAffineBatch(int src_type, const uchar* src_data, siz
         const double borderValue[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!M) return mi355::declined(__func__, __LINE__, "!M");
+    MI355_DECLINE_IF(!M);
     if (src_width > 0 && src_height > 0 && dst_width > 0 && dst_height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {        // frames in host memory
         // BORDER_TRANSPARENT keeps the caller's pixels where the map leaves the source: the pipeline's device buffers do not hold them, so
         // such a batch goes frame by frame through the single-image path, which stages dst in as well
@@ -3048,7 +3045,7 @@ MI355CV_API int mi355cv_warpPerspectiveBatch(int src_type, const uchar* src_data
         const double borderValue[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!M) return mi355::declined(__func__, __LINE__, "!M");
+    MI355_DECLINE_IF(!M);
     if (src_width > 0 && src_height > 0 && dst_width > 0 && dst_height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {        // frames in host memory
         // BORDER_TRANSPARENT keeps the caller's pixels where the map leaves the source: the pipeline's device buffers do not hold them, so
         // such a batch goes frame by frame through the single-image path, which stages dst in as well
@@ -3075,7 +3072,7 @@ MI355CV_API int mi355cv_warpAffine(int src_type, const uchar* src_data, size_t s
         const double borderValue[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!M) return mi355::declined(__func__, __LINE__, "!M");
+    MI355_DECLINE_IF(!M);
     return runWarp("warpAffine", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    M, 0, interpolation, borderType, borderValue, nullptr, 0, nullptr, 0);
 }
@@ -3085,7 +3082,7 @@ MI355CV_API int mi355cv_warpPerspective(int src_type, const uchar* src_data, siz
         const double borderValue[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!M) return mi355::declined(__func__, __LINE__, "!M");
+    MI355_DECLINE_IF(!M);
     return runWarp("warpPerspective", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    M, 1, interpolation, borderType, borderValue, nullptr, 0, nullptr, 0);
 }
@@ -3095,7 +3092,7 @@ MI355CV_API int mi355cv_remap32f(int src_type, const uchar* src_data, size_t src
         int interpolation, int border_type, const double border_value[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!mapx || !mapy) return mi355::declined(__func__, __LINE__, "!mapx || !mapy");
+    MI355_DECLINE_IF(!mapx || !mapy);
     return runWarp("remap32f", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    nullptr, 2, interpolation, border_type, border_value, mapx, mapx_step, mapy, mapy_step);
 }
@@ -3108,7 +3105,7 @@ MI355CV_API int mi355cv_remap(int src_type, const uchar* src_data, size_t src_st
         const void* map2, size_t map2_step, int map2_type, int interpolation, int border_type, const double border_value[4])
 {
     mi355::EntryGuard entry_(__func__);
-    if (!map1) return mi355::declined(__func__, __LINE__, "!map1");
+    MI355_DECLINE_IF(!map1);
     const int t32fc1 = MI355CV_MAKETYPE(MI355CV_32F, 1), t32fc2 = MI355CV_MAKETYPE(MI355CV_32F, 2), t16sc2 = MI355CV_MAKETYPE(MI355CV_16S, 2);
     const int t16uc1 = MI355CV_MAKETYPE(MI355CV_16U, 1), t16sc1 = MI355CV_MAKETYPE(MI355CV_16S, 1);
     int interp = interpolation & 7;
@@ -3122,7 +3119,7 @@ MI355CV_API int mi355cv_remap(int src_type, const uchar* src_data, size_t src_st
     else if (map1_type == t32fc2 && !map2) kind = 3;
     else if (map1_type == t16sc2 && map2 && (map2_type == t16uc1 || map2_type == t16sc1)) kind = 4;
     else if (map1_type == t16sc2 && !map2 && (interp & 7) == MI355CV_INTER_NEAREST) kind = 5;
-    else return mi355::declined(__func__, __LINE__, nullptr);
+    else return MI355_DECLINED(nullptr);
     return runWarp("remap", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    nullptr, kind, interp, border_type, border_value, (const float*)map1, map1_step, (const float*)map2, map2_step);
 }
@@ -3133,16 +3130,16 @@ MI355CV_API int mi355cv_convertMaps(const void* map1, size_t map1_step, int map1
         void* dstmap1, size_t dstmap1_step, int dstmap1_type, void* dstmap2, size_t dstmap2_step, int width, int height, int nninterpolate)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || !map1 || !dstmap1 || width <= 0 || height <= 0) return mi355::declined(__func__, __LINE__, "disabled() || !map1 || !dstmap1 || width <= 0 || height <= 0");
+    MI355_DECLINE_IF(disabled() || !map1 || !dstmap1 || width <= 0 || height <= 0);
     const int t32fc1 = MI355CV_MAKETYPE(MI355CV_32F, 1), t32fc2 = MI355CV_MAKETYPE(MI355CV_32F, 2), t16sc2 = MI355CV_MAKETYPE(MI355CV_16S, 2);
     const int t16uc1 = MI355CV_MAKETYPE(MI355CV_16U, 1), t16sc1 = MI355CV_MAKETYPE(MI355CV_16S, 1);
     const bool toFixed = dstmap1_type == t16sc2 && ((map1_type == t32fc1 && map2 && map2_type == t32fc1) || (map1_type == t32fc2 && !map2));
     const bool toFloat = map1_type == t16sc2 && (!map2 || map2_type == t16uc1 || map2_type == t16sc1) && (dstmap1_type == t32fc1 || dstmap1_type == t32fc2);
-    if (!toFixed && !toFloat) return mi355::declined(__func__, __LINE__, "!toFixed && !toFloat");
-    if (toFixed && !nninterpolate && !dstmap2) return mi355::declined(__func__, __LINE__, "toFixed && !nninterpolate && !dstmap2");
-    if (toFloat && dstmap1_type == t32fc1 && !dstmap2) return mi355::declined(__func__, __LINE__, "toFloat && dstmap1_type == t32fc1 && !dstmap2");
+    MI355_DECLINE_IF(!toFixed && !toFloat);
+    MI355_DECLINE_IF(toFixed && !nninterpolate && !dstmap2);
+    MI355_DECLINE_IF(toFloat && dstmap1_type == t32fc1 && !dstmap2);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
+    MI355_DECLINE_IF(!ensureDevice());
     size_t s1 = 0, s2 = 0, o1 = 0, o2 = 0;
     const size_t e1 = map1_type == t32fc1 ? 4 : map1_type == t32fc2 ? 8 : 4;
     const uchar* a = stg.in((const uchar*)map1, map1_step, (size_t)width * e1, height, &s1);
@@ -3151,7 +3148,7 @@ MI355CV_API int mi355cv_convertMaps(const void* map1, size_t map1_step, int map1
     uchar* c = stg.out((uchar*)dstmap1, dstmap1_step, (size_t)width * f1, height, &o1);
     const bool needD2 = toFixed ? !nninterpolate : dstmap1_type == t32fc1;
     uchar* d = needD2 ? stg.out((uchar*)dstmap2, dstmap2_step, (size_t)width * (toFixed ? 2 : 4), height, &o2) : nullptr;
-    if (!a || (map2 && !b) || !c || (needD2 && !d)) return mi355::declined(__func__, __LINE__, "!a || (map2 && !b) || !c || (needD2 && !d)");
+    MI355_DECLINE_IF(!a || (map2 && !b) || !c || (needD2 && !d));
     dim3 grid(divUp(width, 64), divUp(height, 4));
     if (toFixed) hipLaunchKernelGGL(k_convert_maps_to_fixed, grid, dim3(256), 0, stream(), a, s1, b, s2, map1_type == t32fc2 ? 1 : 0, c, o1, d, o2, width, height, nninterpolate ? 1 : 0);
     else hipLaunchKernelGGL(k_convert_maps_to_float, grid, dim3(256), 0, stream(), a, s1, b, s2, c, o1, d, o2, dstmap1_type == t32fc2 ? 1 : 0, width, height);
@@ -3166,22 +3163,22 @@ MI355CV_API int mi355cv_warpPolar(int src_type, const uchar* src_data, size_t sr
         uchar* dst_data, size_t dst_step, int dst_width, int dst_height, float center_x, float center_y, double maxRadius, int flags)
 {
     mi355::EntryGuard entry_(__func__);
-    if (disabled() || dst_width <= 0 || dst_height <= 0 || src_width <= 0 || src_height <= 0) return mi355::declined(__func__, __LINE__, "disabled() || dst_width <= 0 || dst_height <= 0 || src_width <= 0 || src_height <= 0");
+    MI355_DECLINE_IF(disabled() || dst_width <= 0 || dst_height <= 0 || src_width <= 0 || src_height <= 0);
     const bool semiLog = (flags & 256) != 0;                                                  // WARP_POLAR_LOG
     const double bv[4] = {0, 0, 0, 0};
     if (flags & MI355CV_WARP_INVERSE_MAP) {
         // polar / semi-log polar image -> Cartesian image (imgwarp.cpp:3795-3845): the source gets one wrapped row above and below (copyMakeBorder BORDER_WRAP),
         // the map is evaluated per destination pixel in the kernel (k_warp kind 7), then cv::remap's sampling
         const int depth = MI355CV_MAT_DEPTH(src_type), cn = MI355CV_MAT_CN(src_type);
-        if (!depthOk(depth) || cn < 1 || cn > 4 || src_height + 2 > 32767) return mi355::declined(__func__, __LINE__, "!depthOk(depth) || cn < 1 || cn > 4 || src_height + 2 > 32767");
+        MI355_DECLINE_IF(!depthOk(depth) || cn < 1 || cn > 4 || src_height + 2 > 32767);
         Stager outer;                                  // first: a declined call must also put the host's device back (~Stager)
-        if (!ensureDevice()) return mi355::declined(__func__, __LINE__, "!ensureDevice()");
-        if (hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(HOST_HEAVY))) return mi355::declined(__func__, __LINE__, "hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(HOST_HEAVY))");
+        MI355_DECLINE_IF(!ensureDevice());
+        MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)dst_width * dst_height, minPixels(HOST_HEAVY)));
         const size_t rowB = (size_t)src_width * cn * eszOf(depth), bstep = (rowB + 255) & ~(size_t)255;
         size_t dss;
         const uchar* ds = outer.in(src_data, src_step, rowB, src_height, &dss);
         uchar* bordered = (uchar*)outer.scratch(bstep * (size_t)(src_height + 2));
-        if (!ds || !bordered) return mi355::declined(__func__, __LINE__, "!ds || !bordered");
+        MI355_DECLINE_IF(!ds || !bordered);
         hipStream_t st = stream();
         if (hipMemcpy2DAsync(bordered + bstep, bstep, ds, dss, rowB, src_height, hipMemcpyDeviceToDevice, st) != hipSuccess ||
             hipMemcpyAsync(bordered, ds + (size_t)(src_height - 1) * dss, rowB, hipMemcpyDeviceToDevice, st) != hipSuccess ||

@@ -141,3 +141,11 @@ def test_host_policy_switch():
     out = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=300)
     assert out.stdout.split()[0] == "0", out.stdout                              # an explicit environment choice is respected
     assert L.mi355cv_setHostPolicy(7) != 0
+
+
+def test_decline_reason_is_the_enclosing_function_and_the_conditions_own_text():
+    """MI355_DECLINE_IF (rt.h): the reason a decline records is "<enclosing function>:<line>: outside the GPU path because (<the condition as written in the source>)"."""
+    import re
+    a = np.zeros((4, 4), np.uint8); d = np.zeros((8, 8), np.uint8)
+    assert L.mi355cv_pyrupBatch(vp(a), 4, 16, 4, 4, vp(d), 8, 64, 8, 8, 0, 0, 1, 4) == NOT_IMPLEMENTED            # nframes = 0
+    assert re.fullmatch(r"pyrUpArgs:\d+: outside the GPU path because \(!src \|\| !dst \|\| nframes < 1\)", reason()), reason()
