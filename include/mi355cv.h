@@ -440,6 +440,40 @@ MI355CV_API int mi355cv_minMaxLoc(const mi355cv_uchar* src_data, size_t src_step
  * set does not affect the others.  1 <= nframes <= 65535. */
 MI355CV_API int mi355cv_minMaxLocBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, int depth,
         const mi355cv_uchar* mask_data, size_t mask_step, size_t mask_frame_stride, int nframes, double* vals, int* locs);
+/* cv::calcHist (csrc/calchist.hip).  src: ONE interleaved image of cn = 1 .. 4 channels, depth CV_8U (0), CV_16U (2) or CV_32F (5), its base aligned to the element
+ * only.  dims = 1 .. 3; channels[d] in [0, cn), repeats and any order allowed; histSize[d] = n_d >= 1.  ranges: 2 * dims floats (lo_d, hi_d) when uniform, otherwise
+ * the concatenated n_d + 1 strictly ascending boundaries of each dimension (CV_8U and CV_16U only).  mask: NULL, or CV_8UC1 with its own pitch; non-zero selects.
+ *   uniform      a = n / ((double)hi - (double)lo), b = -a * lo, t = v * a + b with the product and the sum rounded separately (no fused multiply-add).
+ *                CV_8U / CV_16U: v is counted iff lo <= v < hi, bin = min(max(floor(t), 0), n - 1).  CV_32F: counted iff 0 <= t < n (NaN, +-inf never), bin = floor(t).
+ *   non-uniform  the bin is the k with r[k] <= v < r[k + 1]; outside [r[0], r[n]) not counted.
+ *   counting     a pixel is counted iff the mask selects it and every dimension counts it; it adds 1 to the dense row-major cell [b0][b1][b2].
+ *   hist         nframes x prod(n_d) cells of hist_depth CV_32S (4: the exact counts) or CV_32F (5: (float)count, round to nearest even), in HBM or in host memory.
+ *   accumulate   non-zero: a cell starts from its incoming value (CV_32F through cvRound, ties to even, saturated to int32); a count beyond 2^31 - 1 is unspecified.
+ * The reference was not available: this is the project's restatement (tests/calchist_restate.py) and the kernels are held against it bit for bit.  No cv_hal_calcHist
+ * binding is made: the hook's parameter list could not be checked.
+ * src and mask both in HBM, or both in host memory (staged under the host policy, cost class HOST_CHEAP, in groups of at most 1 GiB).
+ * Answered MI355CV_NOT_IMPLEMENTED with hist untouched: a null src, channels, histSize, ranges or hist; another depth; cn outside 1 .. 4; dims outside 1 .. 3; a channel
+ * index outside [0, cn); n_d < 1 or > 65536, or prod(n_d) above mi355cv_limit("calchist_max_bins") = 1048576; hi <= lo, a non-finite range value, boundaries that are
+ * not strictly ascending; non-uniform ranges on CV_32F; width or height <= 0 or above mi355cv_limit("calchist_max_dim") = 16384; nframes < 1 or > 65535; a pitch smaller
+ * than the row or no multiple of the element size; hist_depth other than CV_32S / CV_32F; arguments on different devices; a histogram that overlaps the source or the
+ * mask in HBM. */
+MI355CV_API int mi355cv_calcHist(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn, const int* channels, int dims,
+        const int* histSize, const float* ranges, int uniform, const mi355cv_uchar* mask_data, size_t mask_step, void* hist, int hist_depth, int accumulate);
+/* `nframes` frames of one geometry, `src_frame_stride` bytes apart, one histogram per frame, dense; mask_frame_stride 0: one mask for all frames.  A fixed number of
+ * launches whatever nframes is. */
+MI355CV_API int mi355cv_calcHistBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, int depth, int cn, int nframes,
+        const int* channels, int dims, const int* histSize, const float* ranges, int uniform, const mi355cv_uchar* mask_data, size_t mask_step, size_t mask_frame_stride,
+        void* hist, int hist_depth, int accumulate);
+/* cv::calcBackProject (csrc/calchist.hip): the same bin rule on the same image kinds, no mask.  hist: dense CV_32F of shape histSize with finite values, in HBM or in
+ * host memory.  dst: one channel of the source's depth, where the source lives.  A pixel that any dimension does not count gets 0; otherwise p = (double)hist[bin] * scale,
+ * stored as cvRound(p) (ties to even) saturated to the type for CV_8U / CV_16U and as (float)p for CV_32F.  The refusals of mi355cv_calcHist, and: a null hist or dst; a
+ * destination pitch below the row or no multiple of the element size; a destination that overlaps the source or the histogram in HBM.  dst is left untouched then. */
+MI355CV_API int mi355cv_calcBackProject(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn, const int* channels, int dims,
+        const int* histSize, const float* ranges, int uniform, const float* hist, double scale, mi355cv_uchar* dst_data, size_t dst_step);
+/* hist_frame_stride (bytes) 0: one histogram shared by all frames, otherwise one per frame. */
+MI355CV_API int mi355cv_calcBackProjectBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, int depth, int cn, int nframes,
+        const int* channels, int dims, const int* histSize, const float* ranges, int uniform, const float* hist, size_t hist_frame_stride, double scale,
+        mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

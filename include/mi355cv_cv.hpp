@@ -1,6 +1,6 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
 // (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, demosaicing, distanceTransform, connectedComponents,
-// connectedComponentsWithStats, HoughLines, minMaxLoc, matchTemplate -- and for the map
+// connectedComponentsWithStats, HoughLines, minMaxLoc, calcHist, calcBackProject, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -314,6 +314,74 @@ inline void minMaxLoc(cv::InputArray _src, double* minVal, double* maxVal = 0, c
         }
     }
     cv::minMaxLoc(_src, minVal, maxVal, minLoc, maxLoc, _mask);
+}
+
+// cv::calcHist (imgproc.hpp, the `const Mat* images, int nimages` form): ONE image (nimages == 1) of CV_8U / CV_16U / CV_32F with 1-4 channels, dims 1-3, a dense
+// CV_32F histogram.  The bin rule is this project's restatement (mi355cv.h; the reference was not available to pin it).  Several images, other depths, SparseMat
+// and everything the library declines go to the stock function.  Like mi355cv::minMaxLoc, not yet compiled against the reference's headers.
+namespace detail {
+// the ranges of the C ABI: 2 * dims floats when uniform, else the concatenated histSize[d] + 1 boundaries
+inline bool flatRanges(const float** ranges, int dims, const int* histSize, bool uniform, std::vector<float>& out)
+{
+    if (!ranges || !histSize || dims < 1 || dims > 3) return false;
+    for (int d = 0; d < dims; d++) {
+        if (!ranges[d] || histSize[d] < 1) return false;
+        out.insert(out.end(), ranges[d], ranges[d] + (uniform ? 2 : histSize[d] + 1));
+    }
+    return true;
+}
+} // namespace detail
+
+inline void calcHist(const cv::Mat* images, int nimages, const int* channels, cv::InputArray _mask, cv::OutputArray _hist, int dims, const int* histSize,
+                     const float** ranges, bool uniform = true, bool accumulate = false)
+{
+    std::vector<float> rg;
+    cv::Mat mask = _mask.getMat();
+    if (nimages == 1 && images && channels && images[0].dims <= 2 && !images[0].empty() && detail::flatRanges(ranges, dims, histSize, uniform, rg) &&
+        (mask.empty() || (mask.type() == CV_8UC1 && mask.size() == images[0].size())) && !_hist.isUMat()) {
+        const cv::Mat& src = images[0];
+        cv::Mat hist;
+        if (accumulate) hist = _hist.getMat();
+        bool shaped = !hist.empty() && hist.type() == CV_32F && hist.isContinuous() && hist.dims == (dims == 1 ? 2 : dims);
+        for (int d = 0; shaped && d < dims; d++) shaped = hist.size[d] == histSize[d];
+        if (shaped && dims == 1) shaped = hist.size[1] == 1;
+        if (!accumulate || shaped) {
+            cv::Mat out = accumulate ? hist : cv::Mat(dims, histSize, CV_32F);
+            if (mi355cv_calcHist(src.data, src.step, src.cols, src.rows, src.depth(), src.channels(), channels, dims, histSize, rg.data(), uniform ? 1 : 0,
+                                 mask.empty() ? 0 : mask.data, mask.empty() ? 0 : (size_t)mask.step, out.data, CV_32F, accumulate ? 1 : 0) == MI355CV_OK) {
+                if (!accumulate) out.copyTo(_hist);
+                return;
+            }
+        }
+    }
+    cv::calcHist(images, nimages, channels, _mask, _hist, dims, histSize, ranges, uniform, accumulate);
+}
+
+// cv::calcBackProject: ONE image, a dense CV_32F histogram of 1-3 dimensions; the rest goes to the stock function.
+// The signature carries no `dims`: it is taken from the histogram, and a cv::Mat has no one-dimensional form, so an n x 1 Mat is read as ONE dimension of n bins
+// (what mi355cv::calcHist writes for dims == 1).  A genuinely two-dimensional histogram whose second size is 1 (two channels, histSize {n, 1}) cannot be told from
+// it here and is read as one dimension too: its second channel's range test is then not made.  A caller that has one calls mi355cv_calcBackProject with dims = 2.
+inline void calcBackProject(const cv::Mat* images, int nimages, const int* channels, cv::InputArray _hist, cv::OutputArray _backProject, const float** ranges,
+                            double scale = 1, bool uniform = true)
+{
+    cv::Mat hist = _hist.getMat();
+    int dims = hist.dims, hs[3] = {0, 0, 0};
+    if (dims == 2 && hist.size[1] == 1) dims = 1;                            // a 1-D histogram is an n x 1 Mat
+    std::vector<float> rg;
+    if (nimages == 1 && images && channels && images[0].dims <= 2 && !images[0].empty() && !_hist.isUMat() && !_backProject.isUMat() && dims >= 1 && dims <= 3 &&
+        hist.type() == CV_32F && hist.isContinuous()) {
+        for (int d = 0; d < dims; d++) hs[d] = hist.size[d];
+        const cv::Mat& src = images[0];
+        if (detail::flatRanges(ranges, dims, hs, uniform, rg)) {
+            cv::Mat dst(src.rows, src.cols, CV_MAKETYPE(src.depth(), 1));
+            if (mi355cv_calcBackProject(src.data, src.step, src.cols, src.rows, src.depth(), src.channels(), channels, dims, hs, rg.data(), uniform ? 1 : 0,
+                                        hist.ptr<float>(), scale, dst.data, dst.step) == MI355CV_OK) {
+                dst.copyTo(_backProject);
+                return;
+            }
+        }
+    }
+    cv::calcBackProject(images, nimages, channels, _hist, _backProject, ranges, scale, uniform);
 }
 
 inline void matchTemplate(cv::InputArray _image, cv::InputArray _templ, cv::OutputArray _result, int method, cv::InputArray _mask = cv::noArray())

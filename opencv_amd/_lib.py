@@ -181,6 +181,14 @@ def _load():
         "mi355cv_houghLinesAccum": (c_int, [c_u8p, c_sz, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, ctypes.c_void_p, c_sz, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
         "mi355cv_minMaxLoc": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_u8p, c_sz, ctypes.c_void_p, ctypes.c_void_p]),
         "mi355cv_minMaxLocBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_u8p, c_sz, c_sz, c_int, ctypes.c_void_p, ctypes.c_void_p]),
+        "mi355cv_calcHist": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, c_u8p, c_sz, ctypes.c_void_p, c_int,
+                                     c_int]),
+        "mi355cv_calcHistBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, c_u8p, c_sz, c_sz,
+                                          ctypes.c_void_p, c_int, c_int]),
+        "mi355cv_calcBackProject": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, c_dbl, c_u8p,
+                                            c_sz]),
+        "mi355cv_calcBackProjectBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                                 ctypes.c_void_p, c_sz, c_dbl, c_u8p, c_sz, c_sz]),
         "mi355cv_buildPyramid": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_sz), c_int, c_int]),
         "mi355cv_cornerHarris": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int]),
         "mi355cv_cornerMinEigenVal": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),

@@ -38,6 +38,8 @@ constexpr int HOUGH_MAX_DIM = 16384;       // mi355cv_houghLines*: width and hei
 constexpr int HOUGH_MAX_ACCUM = 1 << 26;   // ... and the cells of the accumulator, (numangle + 2) x (numrho + 2): a cell index is the low word of the sort key
 constexpr int MINMAX_MAX_DIM = 16384;      // mi355cv_minMaxLoc*: width and height (a raster pixel index below 2^28, item counts in 32 bits; minmax_math.h)
 constexpr int DEMOSAIC_MAX_DIM = 16384;    // mi355cv_demosaic*: width and height (the neighbours' bound; a destination row offset of 8 bytes per pixel stays far below 2^31)
+constexpr int CALCHIST_MAX_DIM = 16384;    // mi355cv_calcHist* / mi355cv_calcBackProject*: width and height (the neighbours' bound; a frame has at most 2^28 pixels, so no count of one call passes int32; calchist_math.h)
+constexpr int CALCHIST_MAX_BINS = 1 << 20; // ... and the cells of the dense histogram, the product of histSize (each histSize also <= 65536): 4 MiB of counters per frame, a cell offset far from the table's SKIP mark
 }
 
 struct ThreadCtx;

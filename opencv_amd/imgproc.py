@@ -37,7 +37,7 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
            "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
            "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI",
-           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "minMaxLoc", "minMaxLocBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "minMaxLoc", "minMaxLocBatch", "calcHist", "calcHistBatch", "calcBackProject", "calcBackProjectBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1659,6 +1659,146 @@ def minMaxLocBatch(frames, mask=None, device=False):
     rc = L.mi355cv_minMaxLocBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, s0.depth, mptr, mstep, mframe, n, _vp(vals.data_ptr()), _vp(locs.data_ptr()))
     _lib.check(rc, "minMaxLocBatch")
     return vals, locs
+
+
+# ----------------------------------------------------------------------------- cv::calcHist / cv::calcBackProject (no HAL binding made: mi355cv_calcHist*, mi355cv_calcBackProject*)
+def _is_tensor(a):
+    return torch is not None and isinstance(a, torch.Tensor)
+
+
+def _hist_binning(name, channels, histSize, ranges, uniform):
+    """(channels, dims, histSize, ranges, uniform) as the C ABI takes them.  ranges: flat floats or one sequence per dimension; only its LENGTH is checked here, the
+    library refuses everything else"""
+    channels, histSize = [int(c) for c in channels], [int(n) for n in histSize]
+    if len(channels) != len(histSize) or not channels:
+        raise ValueError(name + ": channels and histSize must have one entry per dimension")
+    parts = [np.asarray(r, dtype=np.float32).ravel() for r in ranges] if len(ranges) and np.ndim(ranges[0]) else [np.asarray(ranges, dtype=np.float32).ravel()]
+    flat = np.ascontiguousarray(np.concatenate(parts))
+    want = 2 * len(histSize) if uniform else sum(max(n, 0) + 1 for n in histSize)
+    if flat.size != want:
+        raise ValueError("%s: ranges holds %d values, %d expected" % (name, flat.size, want))
+    dims = len(channels)
+    return (ctypes.c_int * dims)(*channels), dims, (ctypes.c_int * dims)(*histSize), flat, 1 if uniform else 0
+
+
+def _hist_depth(name, dtype):
+    if dtype in (np.float32, "float32") or (torch is not None and dtype == torch.float32):
+        return CV_32F
+    if dtype in (np.int32, "int32") or (torch is not None and dtype == torch.int32):
+        return CV_32S
+    raise ValueError(name + ": dtype must be float32 (cv::calcHist's) or int32 (the exact counts)")
+
+
+def _one_image(name, images):
+    if not isinstance(images, (list, tuple)):
+        raise ValueError(name + ": images is a list holding one image, as in cv2")
+    if len(images) != 1:
+        raise NotImplementedError(name + ": several source images in one call are not served")
+    return images[0]
+
+
+def _ptr(a):
+    return a.data_ptr() if _is_tensor(a) else a.ctypes.data
+
+
+def calcHist(images, channels, mask, histSize, ranges, hist=None, accumulate=False, uniform=True, dtype=np.float32):
+    """cv::calcHist -> mi355cv_calcHist (cv2's argument order): [image] of 1-4 interleaved channels, CV_8U / CV_16U / CV_32F -> the dense histogram of shape histSize,
+    float32 ((float)count, cv::calcHist's type) or, with dtype=int32, the exact counts; of the image's kind (numpy, or a tensor on its device).  accumulate=True adds to
+    `hist`.  The bin rule is the project's restatement (tests/calchist_restate.py)."""
+    src = _one_image("calcHist", images)
+    s = Img(src)
+    ch, dims, hs, rg, uni = _hist_binning("calcHist", channels, histSize, ranges, uniform)
+    mask = _minmax_mask("calcHist", mask, s.obj, ((s.h, s.w),))
+    m = Img(mask) if mask is not None else None
+    shape = tuple(int(n) for n in histSize)
+    if hist is None:
+        if accumulate:
+            raise ValueError("calcHist: accumulate needs the histogram to add to")
+        depth = _hist_depth("calcHist", dtype)
+        if _is_tensor(src):
+            hist = torch.empty(shape, dtype=torch.float32 if depth == CV_32F else torch.int32, device=src.device)
+        else:
+            hist = np.empty(shape, np.float32 if depth == CV_32F else np.int32)
+    else:
+        depth = _hist_depth("calcHist", hist.dtype)
+        if tuple(hist.shape) != shape or not (hist.is_contiguous() if _is_tensor(hist) else hist.flags.c_contiguous):
+            raise ValueError("calcHist: hist must be dense and of shape histSize")
+    bind_stream(s)
+    rc = L.mi355cv_calcHist(_vp(s.ptr), s.step, s.w, s.h, s.depth, s.cn, ch, dims, hs, _vp(rg.ctypes.data), uni, _vp(m.ptr) if m is not None else None,
+                            m.step if m is not None else 0, _vp(_ptr(hist)), depth, 1 if accumulate else 0)
+    _lib.check(rc, "calcHist")
+    return hist
+
+
+def calcHistBatch(frames, channels, mask, histSize, ranges, uniform=True, dtype=np.float32, device=False):
+    """cv::calcHist over [B,H,W] or [B,H,W,C] frames (strided views such as frames[:, 3:, 5:] are taken as they are), a fixed number of launches -> [B, *histSize],
+    float32 or int32.  mask: None, [H,W] shared by all frames, or [B,H,W].  device=True: the result stays on the frames' device and nothing is read back; otherwise it
+    is a CPU tensor."""
+    n, s0 = _batch_geom(frames)
+    ch, dims, hs, rg, uni = _hist_binning("calcHistBatch", channels, histSize, ranges, uniform)
+    mask = _minmax_mask("calcHistBatch", mask, frames, ((s0.h, s0.w), (n, s0.h, s0.w)))
+    mptr, mstep, mframe = None, 0, 0
+    if mask is not None:
+        m0 = Img(mask if mask.dim() == 2 else mask[0])
+        mptr, mstep, mframe = _vp(m0.ptr), m0.step, (int(mask.stride(0)) if mask.dim() == 3 else 0)
+    if device and not frames.is_cuda:
+        raise ValueError("calcHistBatch: device=True needs frames in device memory")
+    depth = _hist_depth("calcHistBatch", dtype)
+    hist = torch.empty((n,) + tuple(int(v) for v in histSize), dtype=torch.float32 if depth == CV_32F else torch.int32, device=frames.device if device else "cpu")
+    bind_stream(s0)
+    rc = L.mi355cv_calcHistBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, s0.depth, s0.cn, n, ch, dims, hs, _vp(rg.ctypes.data), uni, mptr, mstep,
+                                 mframe, _vp(hist.data_ptr()), depth, 0)
+    _lib.check(rc, "calcHistBatch")
+    return hist
+
+
+def _dense_hist(name, hist):
+    if _is_tensor(hist):
+        if hist.dtype != torch.float32:
+            raise ValueError(name + ": hist must be float32")
+        return hist.contiguous()
+    hist = np.asarray(hist)
+    if hist.dtype != np.float32:
+        raise ValueError(name + ": hist must be float32")
+    return np.ascontiguousarray(hist)
+
+
+def calcBackProject(images, channels, hist, ranges, scale, uniform=True, dst=None):
+    """cv::calcBackProject -> mi355cv_calcBackProject: [image], hist float32 of shape histSize (numpy, or a tensor) -> one channel of the image's depth and kind: 0
+    where some dimension does not count the pixel, otherwise hist[bin] * scale (8- and 16-bit: cvRound, ties to even, saturated)."""
+    src = _one_image("calcBackProject", images)
+    s = Img(src)
+    hist = _dense_hist("calcBackProject", hist)
+    if hist.ndim != len(channels):
+        raise ValueError("calcBackProject: hist must have one axis per channel index")
+    ch, dims, hs, rg, uni = _hist_binning("calcBackProject", channels, hist.shape, ranges, uniform)
+    out = dst if dst is not None else empty_like_kind(s.obj if s.obj.ndim == 2 else s.obj[..., 0], s.h, s.w, 1, s.depth)
+    d = Img(out)
+    if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, 1, s.depth):
+        raise ValueError("dst geometry mismatch")
+    bind_stream(s, d)
+    rc = L.mi355cv_calcBackProject(_vp(s.ptr), s.step, s.w, s.h, s.depth, s.cn, ch, dims, hs, _vp(rg.ctypes.data), uni, _vp(_ptr(hist)), float(scale), _vp(d.ptr), d.step)
+    _lib.check(rc, "calcBackProject")
+    return out
+
+
+def calcBackProjectBatch(frames, channels, hist, ranges, scale, uniform=True, dst=None):
+    """cv::calcBackProject over [B,H,W] or [B,H,W,C] frames -> [B,H,W] of the frames' type, where the frames live.  hist: of shape histSize, shared by all frames, or
+    [B, *histSize], one per frame."""
+    n, s0 = _batch_geom(frames)
+    hist = _dense_hist("calcBackProjectBatch", hist)
+    per_frame = hist.ndim == len(channels) + 1
+    if not per_frame and hist.ndim != len(channels) or per_frame and hist.shape[0] != n:
+        raise ValueError("calcBackProjectBatch: hist is of shape histSize, or [B, *histSize]")
+    shape = tuple(hist.shape[1:] if per_frame else hist.shape)
+    ch, dims, hs, rg, uni = _hist_binning("calcBackProjectBatch", channels, shape, ranges, uniform)
+    out = _batch_out(frames, dst, (n, s0.h, s0.w), frames.dtype)
+    d0 = Img(out[0])
+    bind_stream(s0, d0)
+    rc = L.mi355cv_calcBackProjectBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, s0.depth, s0.cn, n, ch, dims, hs, _vp(rg.ctypes.data), uni,
+                                        _vp(_ptr(hist)), int(np.prod(shape)) * 4 if per_frame else 0, float(scale), _vp(d0.ptr), d0.step, int(out.stride(0)) * d0.esz)
+    _lib.check(rc, "calcBackProjectBatch")
+    return out
 
 
 def buildPyramid(src, maxlevel, borderType=BORDER_DEFAULT):
