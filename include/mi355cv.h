@@ -474,6 +474,30 @@ MI355CV_API int mi355cv_calcBackProject(const mi355cv_uchar* src_data, size_t sr
 MI355CV_API int mi355cv_calcBackProjectBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, int depth, int cn, int nframes,
         const int* channels, int dims, const int* histSize, const float* ranges, int uniform, const float* hist, size_t hist_frame_stride, double scale,
         mi355cv_uchar* dst_data, size_t dst_step, size_t dst_frame_stride);
+/* cv::BackgroundSubtractorMOG2 (csrc/mog2.hip; modules/video, no HAL hook).  A handle owns the per-pixel mixture model in HBM (planes of weights, variances and means,
+ * allocated by the first apply on the calling thread's device); frames of `type` CV_8UC1 (0), CV_8UC3 (16), CV_32FC1 (5) or CV_32FC3 (21) in HBM or host memory, the mask
+ * CV_8UC1 (0 background, shadowValue, 255 foreground) where the frame lives.  The reference was not available: the definition is the project's restatement
+ * (tests/mog2_restate.py) and the kernels are held against it bit for bit.  Parameter names of Set / GetParam: "history", "nmixtures", "varThreshold", "backgroundRatio",
+ * "varThresholdGen", "varInit", "varMin", "varMax", "complexityReductionThreshold", "detectShadows", "shadowValue", "shadowThreshold"; real values are kept as float.
+ * apply re-initialises the model when it has seen no frame, learningRate >= 1, the size or type differ from the model's, or "nmixtures" was set since the last apply;
+ * learningRate < 0: the automatic rate 1 / min(2 nframes, history).
+ * Declined (MI355CV_NOT_IMPLEMENTED, the model left untouched): other types; "nmixtures" outside 1 .. mi355cv_limit("mog2_max_mixtures") = 5; history < 1; an unknown
+ * parameter name; width or height < 1 or above mi355cv_limit("mog2_max_dim") = 16384; a pitch below the row; a mask that overlaps the source in HBM;
+ * GetBackgroundImage / GetModel before any apply or with a geometry other than the model's. */
+MI355CV_API int mi355cv_mog2Create(void** ctx, int history, double varThreshold, int detectShadows);
+MI355CV_API int mi355cv_mog2Free(void* ctx);
+MI355CV_API int mi355cv_mog2SetParam(void* ctx, const char* name, double v);
+MI355CV_API int mi355cv_mog2GetParam(void* ctx, const char* name, double* v);
+MI355CV_API int mi355cv_mog2Apply(void* ctx, const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* mask, size_t mask_step, int width, int height, int type,
+        double learningRate);
+/* `nframes` consecutive frames of one camera in time order, one mask per frame, in ONE launch per 64 frames: the model is read and written once.  learningRate < 0: each
+ * frame gets its own automatic rate; learningRate >= 1 or a changed geometry re-initialises before the first frame only.  Both ends in HBM, or both in host memory. */
+MI355CV_API int mi355cv_mog2ApplyBatch(void* ctx, const mi355cv_uchar* src, size_t src_step, size_t src_frame_stride, mi355cv_uchar* mask, size_t mask_step,
+        size_t mask_frame_stride, int nframes, int width, int height, int type, double learningRate);
+/* the weighted mean of the modes that make up backgroundRatio of the weight, in the model's type (CV_8U: rounded to nearest even, saturated) */
+MI355CV_API int mi355cv_mog2GetBackgroundImage(void* ctx, mi355cv_uchar* dst, size_t dst_step, int width, int height, int type);
+/* the model in the reference's order, dense: modesUsed h x w bytes; gmm h x w x nmixtures x {weight, variance}; mean h x w x nmixtures x cn; unused slots are zero */
+MI355CV_API int mi355cv_mog2GetModel(void* ctx, mi355cv_uchar* modesUsed, float* gmm, float* mean);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

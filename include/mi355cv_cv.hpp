@@ -642,6 +642,91 @@ inline void calcOpticalFlowPyrLK(cv::InputArray _prevImg, cv::InputArray _nextIm
 }
 #endif
 
+#ifdef OPENCV_BACKGROUND_SEGM_HPP   // cv::BackgroundSubtractorMOG2 lives in opencv2/video/background_segm.hpp; include it before this header to get the wrapper
+// cv::BackgroundSubtractorMOG2 (video/background_segm.hpp; bgfg_gaussmix2.cpp).  The reference has no HAL hook for it.  mi355cv::createBackgroundSubtractorMOG2
+// returns a cv::BackgroundSubtractorMOG2 that wraps the stock object and a mi355cv_mog2* handle: parameters live in the stock object and every setter forwards to the
+// handle; apply sends a 2-D CV_8UC1 / CV_8UC3 / CV_32FC1 / CV_32FC3 cv::Mat through mi355cv_mog2Apply, the model staying in HBM.  When the entry declines the VERY FIRST
+// frame (another type, UMat, no device, the host policy) the stock object takes over for good, with its own model; a decline after frames were served is an error,
+// since the two models cannot be merged.
+class BackgroundSubtractorMOG2 CV_FINAL : public cv::BackgroundSubtractorMOG2
+{
+public:
+    explicit BackgroundSubtractorMOG2(const cv::Ptr<cv::BackgroundSubtractorMOG2>& stock) : stock_(stock)
+    {
+        if (mi355cv_mog2Create(&ctx_, stock_->getHistory(), stock_->getVarThreshold(), stock_->getDetectShadows() ? 1 : 0) != MI355CV_OK) ctx_ = nullptr;
+        // the stock object's other defaults, kept in step from the start
+        static const char* const names[] = {"nmixtures", "backgroundRatio", "varThresholdGen", "varInit", "varMin", "varMax", "complexityReductionThreshold", "shadowValue",
+                                            "shadowThreshold"};
+        const double values[] = {(double)stock_->getNMixtures(), stock_->getBackgroundRatio(), stock_->getVarThresholdGen(), stock_->getVarInit(), stock_->getVarMin(),
+                                 stock_->getVarMax(), stock_->getComplexityReductionThreshold(), (double)stock_->getShadowValue(), stock_->getShadowThreshold()};
+        for (int i = 0; ctx_ && i < 9; i++) forward(names[i], values[i]);
+    }
+    ~BackgroundSubtractorMOG2() CV_OVERRIDE { if (ctx_) mi355cv_mog2Free(ctx_); }
+    BackgroundSubtractorMOG2(const BackgroundSubtractorMOG2&) = delete;
+    BackgroundSubtractorMOG2& operator=(const BackgroundSubtractorMOG2&) = delete;
+
+    int getHistory() const CV_OVERRIDE { return stock_->getHistory(); }                           void setHistory(int v) CV_OVERRIDE { stock_->setHistory(v); forward("history", v); }
+    int getNMixtures() const CV_OVERRIDE { return stock_->getNMixtures(); }                       void setNMixtures(int v) CV_OVERRIDE { stock_->setNMixtures(v); forward("nmixtures", v); }
+    double getBackgroundRatio() const CV_OVERRIDE { return stock_->getBackgroundRatio(); }        void setBackgroundRatio(double v) CV_OVERRIDE { stock_->setBackgroundRatio(v); forward("backgroundRatio", v); }
+    double getVarThreshold() const CV_OVERRIDE { return stock_->getVarThreshold(); }              void setVarThreshold(double v) CV_OVERRIDE { stock_->setVarThreshold(v); forward("varThreshold", v); }
+    double getVarThresholdGen() const CV_OVERRIDE { return stock_->getVarThresholdGen(); }        void setVarThresholdGen(double v) CV_OVERRIDE { stock_->setVarThresholdGen(v); forward("varThresholdGen", v); }
+    double getVarInit() const CV_OVERRIDE { return stock_->getVarInit(); }                        void setVarInit(double v) CV_OVERRIDE { stock_->setVarInit(v); forward("varInit", v); }
+    double getVarMin() const CV_OVERRIDE { return stock_->getVarMin(); }                          void setVarMin(double v) CV_OVERRIDE { stock_->setVarMin(v); forward("varMin", v); }
+    double getVarMax() const CV_OVERRIDE { return stock_->getVarMax(); }                          void setVarMax(double v) CV_OVERRIDE { stock_->setVarMax(v); forward("varMax", v); }
+    double getComplexityReductionThreshold() const CV_OVERRIDE { return stock_->getComplexityReductionThreshold(); }
+    void setComplexityReductionThreshold(double v) CV_OVERRIDE { stock_->setComplexityReductionThreshold(v); forward("complexityReductionThreshold", v); }
+    bool getDetectShadows() const CV_OVERRIDE { return stock_->getDetectShadows(); }              void setDetectShadows(bool v) CV_OVERRIDE { stock_->setDetectShadows(v); forward("detectShadows", v ? 1 : 0); }
+    int getShadowValue() const CV_OVERRIDE { return stock_->getShadowValue(); }                   void setShadowValue(int v) CV_OVERRIDE { stock_->setShadowValue(v); forward("shadowValue", v); }
+    double getShadowThreshold() const CV_OVERRIDE { return stock_->getShadowThreshold(); }        void setShadowThreshold(double v) CV_OVERRIDE { stock_->setShadowThreshold(v); forward("shadowThreshold", v); }
+    void clear() CV_OVERRIDE { stock_->clear(); }
+    bool empty() const CV_OVERRIDE { return stock_->empty(); }
+    void write(cv::FileStorage& fs) const CV_OVERRIDE { stock_->write(fs); }
+    void read(const cv::FileNode& fn) CV_OVERRIDE { stock_->read(fn); }
+    cv::String getDefaultName() const CV_OVERRIDE { return stock_->getDefaultName(); }
+
+    void apply(cv::InputArray _image, cv::OutputArray _fgmask, double learningRate = -1) CV_OVERRIDE
+    {
+        if (ctx_ && !forwardFailed_ && _image.kind() == cv::_InputArray::MAT && !_fgmask.isUMat()) {
+            cv::Mat image = _image.getMat();
+            const int t = image.type();
+            if (image.dims <= 2 && !image.empty() && (t == CV_8UC1 || t == CV_8UC3 || t == CV_32FC1 || t == CV_32FC3)) {
+                _fgmask.create(image.size(), CV_8U);
+                cv::Mat mask = _fgmask.getMat();
+                if (mi355cv_mog2Apply(ctx_, image.data, image.step, mask.data, mask.step, image.cols, image.rows, t, learningRate) == MI355CV_OK) {
+                    served_ = true; size_ = image.size(); type_ = t;
+                    return;
+                }
+            }
+        }
+        if (served_) CV_Error(cv::Error::StsNotImplemented, cv::String("mi355cv::BackgroundSubtractorMOG2: the model lives on the device and this frame was declined: ") + mi355cv_lastError());
+        if (ctx_) { mi355cv_mog2Free(ctx_); ctx_ = nullptr; }                   // declined on the very first frame: the stock object from here on
+        stock_->apply(_image, _fgmask, learningRate);
+    }
+
+    void getBackgroundImage(cv::OutputArray _dst) const CV_OVERRIDE
+    {
+        if (!served_) { stock_->getBackgroundImage(_dst); return; }
+        _dst.create(size_, type_);
+        cv::Mat dst = _dst.getMat();
+        if (mi355cv_mog2GetBackgroundImage(ctx_, dst.data, dst.step, dst.cols, dst.rows, type_) != MI355CV_OK)
+            CV_Error(cv::Error::StsNotImplemented, cv::String("mi355cv::BackgroundSubtractorMOG2::getBackgroundImage: ") + mi355cv_lastError());
+    }
+private:
+    // a value the handle declines (nmixtures above mi355cv_limit("mog2_max_mixtures"), say) before any frame was served sends the object to the stock path
+    void forward(const char* name, double v) { if (ctx_ && mi355cv_mog2SetParam(ctx_, name, v) != MI355CV_OK) forwardFailed_ = true; }
+    cv::Ptr<cv::BackgroundSubtractorMOG2> stock_;
+    void* ctx_ = nullptr;
+    bool served_ = false, forwardFailed_ = false;
+    cv::Size size_;
+    int type_ = -1;
+};
+
+inline cv::Ptr<cv::BackgroundSubtractorMOG2> createBackgroundSubtractorMOG2(int history = 500, double varThreshold = 16, bool detectShadows = true)
+{
+    return cv::makePtr<mi355cv::BackgroundSubtractorMOG2>(cv::createBackgroundSubtractorMOG2(history, varThreshold, detectShadows));
+}
+#endif
+
 // Batches across the GPUs of one node from C++: forEachShard({0,1,...,7}, nframes, [&](int slot, int device, int first, int count) { ... return 0; })
 // runs the callable once per device on its own host thread bound to that device (mi355cv_runSharded, csrc/shard.hip), frames [first, first + count) being that
 // device's share; inside, call cv:: functions of a HAL-enabled build or mi355cv:: / mi355cv_*Batch entry points on Mats whose storage lives on `device`

@@ -189,6 +189,14 @@ def _load():
                                             c_sz]),
         "mi355cv_calcBackProjectBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
                                                  ctypes.c_void_p, c_sz, c_dbl, c_u8p, c_sz, c_sz]),
+        "mi355cv_mog2Create": (c_int, [ctypes.POINTER(ctypes.c_void_p), c_int, c_dbl, c_int]),
+        "mi355cv_mog2Free": (c_int, [ctypes.c_void_p]),
+        "mi355cv_mog2SetParam": (c_int, [ctypes.c_void_p, ctypes.c_char_p, c_dbl]),
+        "mi355cv_mog2GetParam": (c_int, [ctypes.c_void_p, ctypes.c_char_p, ctypes.POINTER(c_dbl)]),
+        "mi355cv_mog2Apply": (c_int, [ctypes.c_void_p, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_dbl]),
+        "mi355cv_mog2ApplyBatch": (c_int, [ctypes.c_void_p, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_dbl]),
+        "mi355cv_mog2GetBackgroundImage": (c_int, [ctypes.c_void_p, c_u8p, c_sz, c_int, c_int, c_int]),
+        "mi355cv_mog2GetModel": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
         "mi355cv_buildPyramid": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_sz), c_int, c_int]),
         "mi355cv_cornerHarris": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int]),
         "mi355cv_cornerMinEigenVal": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),

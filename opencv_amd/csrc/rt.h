@@ -40,6 +40,8 @@ constexpr int MINMAX_MAX_DIM = 16384;      // mi355cv_minMaxLoc*: width and heig
 constexpr int DEMOSAIC_MAX_DIM = 16384;    // mi355cv_demosaic*: width and height (the neighbours' bound; a destination row offset of 8 bytes per pixel stays far below 2^31)
 constexpr int CALCHIST_MAX_DIM = 16384;    // mi355cv_calcHist* / mi355cv_calcBackProject*: width and height (the neighbours' bound; a frame has at most 2^28 pixels, so no count of one call passes int32; calchist_math.h)
 constexpr int CALCHIST_MAX_BINS = 1 << 20; // ... and the cells of the dense histogram, the product of histSize (each histSize also <= 65536): 4 MiB of counters per frame, a cell offset far from the table's SKIP mark
+constexpr int MOG2_MAX_DIM = 16384;        // mi355cv_mog2*: width and height (the neighbours' bound; a pixel index and a plane of the model stay below 2^28 elements; mog2_math.h)
+constexpr int MOG2_MAX_MIXTURES = 5;       // ... and the modes per pixel, held in registers with compile-time indices (the reference's default nmixtures)
 }
 
 struct ThreadCtx;

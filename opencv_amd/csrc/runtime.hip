@@ -572,7 +572,8 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"median8u_max_ksize", MEDIAN8U_MAX_KSIZE}, {"bilateral_max_d", 2 * BILATERAL_MAX_RADIUS + 1}, {"orb_max_levels", ORB_MAX_LEVELS}, {"filter2d_dft_taps", FILTER2D_DFT_TAPS},
         {"disttransform_max_dim", DISTTRANSFORM_MAX_DIM}, {"ccl_max_dim", CCL_MAX_DIM},
         {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"minmax_max_dim", MINMAX_MAX_DIM},
-        {"demosaic_max_dim", DEMOSAIC_MAX_DIM}, {"calchist_max_dim", CALCHIST_MAX_DIM}, {"calchist_max_bins", CALCHIST_MAX_BINS}};
+        {"demosaic_max_dim", DEMOSAIC_MAX_DIM}, {"calchist_max_dim", CALCHIST_MAX_DIM}, {"calchist_max_bins", CALCHIST_MAX_BINS},
+        {"mog2_max_dim", MOG2_MAX_DIM}, {"mog2_max_mixtures", MOG2_MAX_MIXTURES}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;

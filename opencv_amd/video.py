@@ -10,11 +10,11 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from .core import Img, bind_stream, torch, CV_8U, BORDER_CONSTANT, BORDER_REFLECT_101, BORDER_ISOLATED
+from .core import Img, bind_stream, torch, CV_8U, CV_32F, BORDER_CONSTANT, BORDER_REFLECT_101, BORDER_ISOLATED
 from .imgproc import pyrDown
 
 __all__ = ["ScharrDeriv", "copyMakeBorder", "buildOpticalFlowPyramid", "LKOpticalFlowLevel", "calcOpticalFlowPyrLK", "calcOpticalFlowPyrLK_hooks",
-           "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_LK_GET_MIN_EIGENVALS", "TERM_COUNT", "TERM_EPS"]
+           "createBackgroundSubtractorMOG2", "BackgroundSubtractorMOG2", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_LK_GET_MIN_EIGENVALS", "TERM_COUNT", "TERM_EPS"]
 
 L = _lib.lib
 OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS = 4, 8
@@ -212,3 +212,107 @@ def calcOpticalFlowPyrLK_hooks(prevImg, nextImg, prevPts, nextPts=None, winSize=
         LKOpticalFlowLevel(I, dI, J, prevScaled.contiguous() if dev else np.ascontiguousarray(prevScaled), out, status if level == 0 else None, err,
                            (winW, winH), maxCount, eps, bool(flags & OPTFLOW_LK_GET_MIN_EIGENVALS), minEigThreshold)
     return out, status, err
+
+
+class BackgroundSubtractorMOG2:
+    """cv::BackgroundSubtractorMOG2 (modules/video; no HAL hook) through the mi355cv_mog2* entries: the handle owns the per-pixel mixture model in HBM, frames are
+    CV_8UC1 / CV_8UC3 / CV_32FC1 / CV_32FC3 torch device tensors or numpy arrays, masks CV_8UC1 of the same kind.  Create it with createBackgroundSubtractorMOG2."""
+    _PARAMS = {"History": "history", "NMixtures": "nmixtures", "BackgroundRatio": "backgroundRatio", "VarThreshold": "varThreshold", "VarThresholdGen": "varThresholdGen",
+               "VarInit": "varInit", "VarMin": "varMin", "VarMax": "varMax", "ComplexityReductionThreshold": "complexityReductionThreshold",
+               "DetectShadows": "detectShadows", "ShadowValue": "shadowValue", "ShadowThreshold": "shadowThreshold"}
+    _INT = {"history": int, "nmixtures": int, "shadowValue": int, "detectShadows": bool}
+
+    def __init__(self, history=500, varThreshold=16, detectShadows=True):
+        self._h = None
+        h = ctypes.c_void_p()
+        _lib.check(L.mi355cv_mog2Create(ctypes.byref(h), int(history), float(varThreshold), 1 if detectShadows else 0), "mog2Create")
+        self._h = h
+        self._last = None                                                                     # (array of the last frame's kind, h, w, cn, depth, the model's nmixtures)
+
+    def __del__(self):
+        h, self._h = getattr(self, "_h", None), None
+        if h is not None and L is not None:
+            L.mi355cv_mog2Free(h)
+
+    def _get(self, name):
+        v = ctypes.c_double()
+        _lib.check(L.mi355cv_mog2GetParam(self._h, name.encode(), ctypes.byref(v)), "mog2GetParam")
+        return self._INT.get(name, float)(v.value)
+
+    def _set(self, name, v):
+        _lib.check(L.mi355cv_mog2SetParam(self._h, name.encode(), float(v)), "mog2SetParam")
+
+    def __getattr__(self, attr):                                                              # getHistory ... setShadowThreshold, the reference's names
+        name = self._PARAMS.get(attr[3:]) if attr[:3] in ("get", "set") else None
+        if name is None:
+            raise AttributeError(attr)
+        return (lambda: self._get(name)) if attr[:3] == "get" else (lambda v: self._set(name, v))
+
+    @staticmethod
+    def _frame(s):
+        if s.depth not in (CV_8U, CV_32F) or s.cn not in (1, 3):
+            raise ValueError("BackgroundSubtractorMOG2: CV_8UC1, CV_8UC3, CV_32FC1 or CV_32FC3 frames")
+
+    def apply(self, image, fgmask=None, learningRate=-1):
+        """one frame into the model; returns the CV_8UC1 mask (0 background, shadowValue, 255 foreground)"""
+        s = Img(image)
+        self._frame(s)
+        out = fgmask if fgmask is not None else _empty(image, (s.h, s.w), np.uint8)
+        d = Img(out)
+        if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, 1, CV_8U):
+            raise ValueError("BackgroundSubtractorMOG2.apply: fgmask must be CV_8UC1 of the frame's size")
+        bind_stream(s, d)
+        _lib.check(L.mi355cv_mog2Apply(self._h, _vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, s.type, float(learningRate)), "mog2Apply")
+        self._last = (image, s.h, s.w, s.cn, s.depth, self._get("nmixtures"))
+        return out
+
+    def applyBatch(self, frames, fgmask=None, learningRate=-1):
+        """T consecutive frames of the camera in time order, stacked as T x H x W (one channel) or T x H x W x C, in one launch per 64 frames: the model crosses HBM
+        once.  learningRate < 0 gives every frame its own automatic rate; learningRate >= 1 re-initialises before the first frame only.  Returns T x H x W masks."""
+        if isinstance(frames, (list, tuple)):
+            frames = torch.stack(list(frames)) if _is_dev(frames[0]) else np.stack([np.asarray(f) for f in frames])
+        if frames.ndim not in (3, 4) or int(frames.shape[0]) < 1:
+            raise ValueError("BackgroundSubtractorMOG2.applyBatch: frames stacked as T x H x W or T x H x W x C")
+        n = int(frames.shape[0])
+        s = Img(frames[0])
+        self._frame(s)
+        out = fgmask if fgmask is not None else _empty(frames, (n, s.h, s.w), np.uint8)
+        if out.ndim != 3 or int(out.shape[0]) != n:
+            raise ValueError("BackgroundSubtractorMOG2.applyBatch: fgmask must be T x H x W, CV_8U")
+        d = Img(out[0])
+        if (d.h, d.w, d.cn, d.depth) != (s.h, s.w, 1, CV_8U):
+            raise ValueError("BackgroundSubtractorMOG2.applyBatch: fgmask must be T x H x W, CV_8U")
+        fstride = lambda a, esz: int(a.stride(0)) * esz if torch is not None and isinstance(a, torch.Tensor) else int(a.strides[0])
+        bind_stream(s, d)
+        _lib.check(L.mi355cv_mog2ApplyBatch(self._h, _vp(s.ptr), s.step, fstride(frames, s.esz), _vp(d.ptr), d.step, fstride(out, 1), n, s.w, s.h, s.type,
+                                            float(learningRate)), "mog2ApplyBatch")
+        self._last = (frames, s.h, s.w, s.cn, s.depth, self._get("nmixtures"))
+        return out
+
+    def _need_model(self, what):
+        if self._last is None:
+            raise NotImplementedError("BackgroundSubtractorMOG2.%s: no frame has been applied yet" % what)
+        return self._last
+
+    def getBackgroundImage(self, dst=None):
+        ref, h, w, cn, depth, _ = self._need_model("getBackgroundImage")
+        out = dst if dst is not None else _empty(ref, (h, w) if cn == 1 else (h, w, cn), np.uint8 if depth == CV_8U else np.float32)
+        d = Img(out)
+        bind_stream(d)
+        _lib.check(L.mi355cv_mog2GetBackgroundImage(self._h, _vp(d.ptr), d.step, d.w, d.h, d.type), "mog2GetBackgroundImage")
+        return out
+
+    def getModel(self):
+        """the model in the reference's order, of the last frame's kind: (modesUsed h x w uint8, gmm h x w x nmixtures x 2 = {weight, variance},
+        mean h x w x nmixtures x cn); slots at and above a pixel's count are zero.  Enough to checkpoint a camera."""
+        ref, h, w, cn, _, m = self._need_model("getModel")
+        modes, gmm, mean = _empty(ref, (h, w), np.uint8), _empty(ref, (h, w, m, 2), np.float32), _empty(ref, (h, w, m, cn), np.float32)
+        ptr = lambda a: _vp(a.data_ptr() if torch is not None and isinstance(a, torch.Tensor) else a.ctypes.data)
+        bind_stream(Img(modes))
+        _lib.check(L.mi355cv_mog2GetModel(self._h, ptr(modes), ptr(gmm), ptr(mean)), "mog2GetModel")
+        return modes, gmm, mean
+
+
+def createBackgroundSubtractorMOG2(history=500, varThreshold=16, detectShadows=True):
+    """cv::createBackgroundSubtractorMOG2"""
+    return BackgroundSubtractorMOG2(history, varThreshold, detectShadows)
