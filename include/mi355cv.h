@@ -498,6 +498,31 @@ MI355CV_API int mi355cv_mog2ApplyBatch(void* ctx, const mi355cv_uchar* src, size
 MI355CV_API int mi355cv_mog2GetBackgroundImage(void* ctx, mi355cv_uchar* dst, size_t dst_step, int width, int height, int type);
 /* the model in the reference's order, dense: modesUsed h x w bytes; gmm h x w x nmixtures x {weight, variance}; mean h x w x nmixtures x cn; unused slots are zero */
 MI355CV_API int mi355cv_mog2GetModel(void* ctx, mi355cv_uchar* modesUsed, float* gmm, float* mean);
+/* cv::calcOpticalFlowFarneback (csrc/farneback.hip; modules/video, no HAL hook): dense optical flow between two CV_8UC1 frames of width x height, the flow CV_32FC2
+ * (x, y displacement per pixel), all in HBM or all in host memory (staged).  The reference was not available: the definition is the project's restatement
+ * (tests/farneback_restate.py, float32 arithmetic in a fixed order) and the kernels are held against it bit for bit.  flags: OPTFLOW_USE_INITIAL_FLOW (4), then `flow`
+ * holds the initial flow, and OPTFLOW_FARNEBACK_GAUSSIAN (256).  The pyramid has the levels k = 0 .. levels - 1 of scale pyr_scale^k, cut at the first k >= 1 whose
+ * scaled width or height falls below 32.
+ * Declined (MI355CV_NOT_IMPLEMENTED, flow left untouched): width or height < 1 or above mi355cv_limit("farneback_max_dim") = 16384; winsize < 1 or above
+ * mi355cv_limit("farneback_max_winsize") = 25; poly_n < 1 or above mi355cv_limit("farneback_max_poly_n") = 7; a pyramid level whose Gaussian needs more than
+ * mi355cv_limit("farneback_max_smooth_taps") = 255 taps; iterations < 0; levels < 1 or > 32; pyr_scale outside (0, 1); poly_sigma < 0; other flags;
+ * OPTFLOW_USE_INITIAL_FLOW with more than one effective level; a pitch below the row; a flow pointer or pitch that is no multiple of 4; a flow that overlaps a frame
+ * (or another flow) in HBM. */
+MI355CV_API int mi355cv_calcOpticalFlowFarneback(const mi355cv_uchar* prev, size_t prev_step, const mi355cv_uchar* next, size_t next_step, mi355cv_uchar* flow,
+        size_t flow_step, int width, int height, double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags);
+/* `nframes` consecutive frames -> nframes - 1 flows, flow i from frame i to frame i + 1, each equal to the single call bit for bit; the level images and polynomial
+ * expansions of every shared frame are computed once.  OPTFLOW_USE_INITIAL_FLOW is declined.  Host-resident batches are staged whole (not pipelined). */
+MI355CV_API int mi355cv_calcOpticalFlowFarnebackBatch(const mi355cv_uchar* frames, size_t step, size_t frame_stride, int nframes, mi355cv_uchar* flows, size_t flow_step,
+        size_t flow_frame_stride, int width, int height, double pyr_scale, int levels, int winsize, int iterations, int poly_n, double poly_sigma, int flags);
+/* The stages, one kernel each, so that a mismatch can be pinned at a tiny size.  Images are CV_32F: src one float per pixel, R0 / R1 / M five (interleaved), flow two.
+ * PolyExp: R (y-linear, x-linear, yy, xx, xy) of src.  UpdateMatrices: M (G11, G12, G22, h1, h2) from R0, R1 and the flow.  UpdateFlow: the flow from the window sums of
+ * M (flags: 0 or OPTFLOW_FARNEBACK_GAUSSIAN); with R0, R1 and M_next all given (else all NULL), M_next is the update matrix of the new flow, as every iteration but the
+ * last computes it. */
+MI355CV_API int mi355cv_farnebackPolyExp(const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* dst, size_t dst_step, int width, int height, int poly_n, double poly_sigma);
+MI355CV_API int mi355cv_farnebackUpdateMatrices(const mi355cv_uchar* R0, size_t r0_step, const mi355cv_uchar* R1, size_t r1_step, const mi355cv_uchar* flow, size_t flow_step,
+        mi355cv_uchar* M, size_t m_step, int width, int height);
+MI355CV_API int mi355cv_farnebackUpdateFlow(const mi355cv_uchar* M, size_t m_step, mi355cv_uchar* flow, size_t flow_step, const mi355cv_uchar* R0, size_t r0_step,
+        const mi355cv_uchar* R1, size_t r1_step, mi355cv_uchar* M_next, size_t m_next_step, int width, int height, int winsize, int flags);
 /* cv::buildPyramid (pyramids.cpp:1616-1643) has no HAL hook: dst_data[i] / dst_step[i] receive level i+1. */
 MI355CV_API int mi355cv_buildPyramid(const mi355cv_uchar* src_data, size_t src_step, int width, int height, int depth, int cn,
         mi355cv_uchar** dst_data, const size_t* dst_step, int maxlevel, int border_type);

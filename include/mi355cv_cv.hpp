@@ -640,6 +640,28 @@ inline void calcOpticalFlowPyrLK(cv::InputArray _prevImg, cv::InputArray _nextIm
     }
     cv::calcOpticalFlowPyrLK(_prevImg, _nextImg, _prevPts, _nextPts, _status, _err, winSize, maxLevel, criteria, flags, minEigThreshold);
 }
+
+// cv::calcOpticalFlowFarneback (video/tracking.hpp; optflowgf.cpp).  The reference has no HAL hook for it.  Two CV_8UC1 Mats go through mi355cv_calcOpticalFlowFarneback
+// (csrc/farneback.hip): the frames and the flow live where the Mats live.  The entry computes the project's float32 restatement of the algorithm, which is not
+// bit-identical to cv::; everything it declines (other types, sizes and windows over the limits, OPTFLOW_USE_INITIAL_FLOW with more than one pyramid level, UMat, no
+// device) is handed to the stock function.
+inline void calcOpticalFlowFarneback(cv::InputArray _prev, cv::InputArray _next, cv::InputOutputArray _flow, double pyr_scale, int levels, int winsize, int iterations,
+                                     int poly_n, double poly_sigma, int flags)
+{
+    if (_prev.kind() == cv::_InputArray::MAT && _next.kind() == cv::_InputArray::MAT && _flow.kind() == cv::_InputArray::MAT) {
+        cv::Mat prev = _prev.getMat(), next = _next.getMat();
+        if (prev.dims <= 2 && prev.type() == CV_8UC1 && next.type() == CV_8UC1 && prev.size() == next.size() && !prev.empty()) {
+            // the stock function creates the flow itself unless it carries the initial flow; the entry writes it only when it succeeds
+            if (!(flags & cv::OPTFLOW_USE_INITIAL_FLOW)) _flow.create(prev.size(), CV_32FC2);
+            cv::Mat flow = _flow.getMat();
+            if (flow.size() == prev.size() && flow.type() == CV_32FC2 &&
+                mi355cv_calcOpticalFlowFarneback(prev.data, prev.step, next.data, next.step, flow.data, flow.step, prev.cols, prev.rows, pyr_scale, levels, winsize,
+                                                 iterations, poly_n, poly_sigma, flags) == MI355CV_OK)
+                return;
+        }
+    }
+    cv::calcOpticalFlowFarneback(_prev, _next, _flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags);
+}
 #endif
 
 #ifdef OPENCV_BACKGROUND_SEGM_HPP   // cv::BackgroundSubtractorMOG2 lives in opencv2/video/background_segm.hpp; include it before this header to get the wrapper

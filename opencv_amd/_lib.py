@@ -197,6 +197,11 @@ def _load():
         "mi355cv_mog2ApplyBatch": (c_int, [ctypes.c_void_p, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_dbl]),
         "mi355cv_mog2GetBackgroundImage": (c_int, [ctypes.c_void_p, c_u8p, c_sz, c_int, c_int, c_int]),
         "mi355cv_mog2GetModel": (c_int, [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p]),
+        "mi355cv_calcOpticalFlowFarneback": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_dbl, c_int, c_int, c_int, c_int, c_dbl, c_int]),
+        "mi355cv_calcOpticalFlowFarnebackBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_dbl, c_int, c_int, c_int, c_int, c_dbl, c_int]),
+        "mi355cv_farnebackPolyExp": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_dbl]),
+        "mi355cv_farnebackUpdateMatrices": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int]),
+        "mi355cv_farnebackUpdateFlow": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int]),
         "mi355cv_buildPyramid": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.POINTER(ctypes.c_void_p), ctypes.POINTER(c_sz), c_int, c_int]),
         "mi355cv_cornerHarris": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_dbl, c_int]),
         "mi355cv_cornerMinEigenVal": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),

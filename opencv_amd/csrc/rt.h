@@ -42,6 +42,10 @@ constexpr int CALCHIST_MAX_DIM = 16384;    // mi355cv_calcHist* / mi355cv_calcBa
 constexpr int CALCHIST_MAX_BINS = 1 << 20; // ... and the cells of the dense histogram, the product of histSize (each histSize also <= 65536): 4 MiB of counters per frame, a cell offset far from the table's SKIP mark
 constexpr int MOG2_MAX_DIM = 16384;        // mi355cv_mog2*: width and height (the neighbours' bound; a pixel index and a plane of the model stay below 2^28 elements; mog2_math.h)
 constexpr int MOG2_MAX_MIXTURES = 5;       // ... and the modes per pixel, held in registers with compile-time indices (the reference's default nmixtures)
+constexpr int FARNEBACK_MAX_DIM = 16384;   // mi355cv_calcOpticalFlowFarneback* and its stages: width and height (the neighbours' bound; farneback_math.h)
+constexpr int FARNEBACK_MAX_WINSIZE = 25;  // ... the averaging window: the M tile with its halo and the vertical sums of k_fb_update_flow fit 64 KiB of LDS
+constexpr int FARNEBACK_MAX_POLY_N = 7;    // ... the half-width of the polynomial expansion: taps in the kernel arguments, LDS tiles sized for it
+constexpr int FARNEBACK_MAX_SMOOTH_TAPS = 255; // ... the taps of a pyramid level's Gaussian, max(cvRound(5 sigma) | 1, 3) with sigma = (1 / scale - 1) / 2
 }
 
 struct ThreadCtx;

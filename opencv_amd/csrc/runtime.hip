@@ -573,7 +573,9 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"disttransform_max_dim", DISTTRANSFORM_MAX_DIM}, {"ccl_max_dim", CCL_MAX_DIM},
         {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"minmax_max_dim", MINMAX_MAX_DIM},
         {"demosaic_max_dim", DEMOSAIC_MAX_DIM}, {"calchist_max_dim", CALCHIST_MAX_DIM}, {"calchist_max_bins", CALCHIST_MAX_BINS},
-        {"mog2_max_dim", MOG2_MAX_DIM}, {"mog2_max_mixtures", MOG2_MAX_MIXTURES}};
+        {"mog2_max_dim", MOG2_MAX_DIM}, {"mog2_max_mixtures", MOG2_MAX_MIXTURES},
+        {"farneback_max_dim", FARNEBACK_MAX_DIM}, {"farneback_max_winsize", FARNEBACK_MAX_WINSIZE}, {"farneback_max_poly_n", FARNEBACK_MAX_POLY_N},
+        {"farneback_max_smooth_taps", FARNEBACK_MAX_SMOOTH_TAPS}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;

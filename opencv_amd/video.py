@@ -14,10 +14,13 @@ from .core import Img, bind_stream, torch, CV_8U, CV_32F, BORDER_CONSTANT, BORDE
 from .imgproc import pyrDown
 
 __all__ = ["ScharrDeriv", "copyMakeBorder", "buildOpticalFlowPyramid", "LKOpticalFlowLevel", "calcOpticalFlowPyrLK", "calcOpticalFlowPyrLK_hooks",
-           "createBackgroundSubtractorMOG2", "BackgroundSubtractorMOG2", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_LK_GET_MIN_EIGENVALS", "TERM_COUNT", "TERM_EPS"]
+           "createBackgroundSubtractorMOG2", "BackgroundSubtractorMOG2", "OPTFLOW_USE_INITIAL_FLOW", "OPTFLOW_LK_GET_MIN_EIGENVALS", "TERM_COUNT", "TERM_EPS",
+           "calcOpticalFlowFarneback", "calcOpticalFlowFarnebackBatch", "farnebackPolyExp", "farnebackUpdateMatrices", "farnebackUpdateFlow",
+           "OPTFLOW_FARNEBACK_GAUSSIAN"]
 
 L = _lib.lib
 OPTFLOW_USE_INITIAL_FLOW, OPTFLOW_LK_GET_MIN_EIGENVALS = 4, 8
+OPTFLOW_FARNEBACK_GAUSSIAN = 256
 TERM_COUNT, TERM_EPS = 1, 2
 
 
@@ -316,3 +319,109 @@ class BackgroundSubtractorMOG2:
 def createBackgroundSubtractorMOG2(history=500, varThreshold=16, detectShadows=True):
     """cv::createBackgroundSubtractorMOG2"""
     return BackgroundSubtractorMOG2(history, varThreshold, detectShadows)
+
+
+# ---- cv::calcOpticalFlowFarneback (modules/video/src/optflowgf.cpp; no HAL hook): mi355cv_calcOpticalFlowFarneback* and its stages
+def _decline(entry, why):
+    """a refusal the C ABI cannot see (it takes no type argument): counted in the decline ledger like the library's own"""
+    L.mi355cv_noteDecline(entry.encode())
+    raise NotImplementedError("mi355cv_%s: NOT_IMPLEMENTED for these arguments (%s); no CPU fallback in opencv_amd" % (entry, why))
+
+
+def _f32(a, cn, entry, what):
+    i = Img(a)
+    if i.depth != CV_32F or i.cn != cn:
+        _decline(entry, "%s must be CV_32FC%d" % (what, cn))
+    return i
+
+
+def calcOpticalFlowFarneback(prev, next, flow, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
+    """cv::calcOpticalFlowFarneback: dense flow between two CV_8UC1 frames, H x W x 2 float32 of the frames' kind (torch device tensors stay in HBM, numpy arrays are
+    staged).  `flow` may be None (allocated) unless flags has OPTFLOW_USE_INITIAL_FLOW, which is served for one effective pyramid level only."""
+    entry = "calcOpticalFlowFarneback"
+    p, n = Img(prev), Img(next)
+    if (p.depth, p.cn) != (CV_8U, 1) or (n.depth, n.cn) != (CV_8U, 1):
+        _decline(entry, "frames must be CV_8UC1")
+    if (p.w, p.h) != (n.w, n.h):
+        raise ValueError("calcOpticalFlowFarneback: two frames of the same size")
+    if flow is None:
+        if flags & OPTFLOW_USE_INITIAL_FLOW:
+            raise ValueError("calcOpticalFlowFarneback: OPTFLOW_USE_INITIAL_FLOW needs a flow")
+        flow = _empty(prev, (p.h, p.w, 2), np.float32)
+    f = _f32(flow, 2, entry, "flow")
+    if (f.w, f.h) != (p.w, p.h):
+        raise ValueError("calcOpticalFlowFarneback: flow must be H x W x 2 of the frames' size")
+    bind_stream(p, n, f)
+    _lib.check(L.mi355cv_calcOpticalFlowFarneback(_vp(p.ptr), p.step, _vp(n.ptr), n.step, _vp(f.ptr), f.step, p.w, p.h, float(pyr_scale), int(levels), int(winsize),
+                                                  int(iterations), int(poly_n), float(poly_sigma), int(flags)), entry)
+    return flow
+
+
+def calcOpticalFlowFarnebackBatch(frames, flows, pyr_scale, levels, winsize, iterations, poly_n, poly_sigma, flags):
+    """T consecutive CV_8UC1 frames stacked as T x H x W -> T - 1 flows (T - 1) x H x W x 2, flow i from frame i to frame i + 1, each bit for bit the single call's;
+    every shared frame's level images and polynomial expansions are computed once."""
+    entry = "calcOpticalFlowFarnebackBatch"
+    if isinstance(frames, (list, tuple)):
+        frames = torch.stack(list(frames)) if _is_dev(frames[0]) else np.stack([np.asarray(f) for f in frames])
+    if frames.ndim != 3 or int(frames.shape[0]) < 2:
+        raise ValueError("calcOpticalFlowFarnebackBatch: at least two frames stacked as T x H x W")
+    t = int(frames.shape[0])
+    s = Img(frames[0])
+    if (s.depth, s.cn) != (CV_8U, 1):
+        _decline(entry, "frames must be CV_8UC1")
+    if flows is None:
+        flows = _empty(frames, (t - 1, s.h, s.w, 2), np.float32)
+    if flows.ndim != 4 or int(flows.shape[0]) != t - 1:
+        raise ValueError("calcOpticalFlowFarnebackBatch: flows must be (T - 1) x H x W x 2")
+    d = _f32(flows[0], 2, entry, "flows")
+    if (d.w, d.h) != (s.w, s.h):
+        raise ValueError("calcOpticalFlowFarnebackBatch: flows must be (T - 1) x H x W x 2")
+    fstride = lambda a, esz: int(a.stride(0)) * esz if torch is not None and isinstance(a, torch.Tensor) else int(a.strides[0])
+    bind_stream(s, d)
+    _lib.check(L.mi355cv_calcOpticalFlowFarnebackBatch(_vp(s.ptr), s.step, fstride(frames, 1), t, _vp(d.ptr), d.step, fstride(flows, 4), s.w, s.h, float(pyr_scale), int(levels),
+                                                       int(winsize), int(iterations), int(poly_n), float(poly_sigma), int(flags)), entry)
+    return flows
+
+
+def farnebackPolyExp(src, poly_n, poly_sigma, dst=None):
+    """the polynomial expansion of a CV_32FC1 image: H x W x 5 float32 (y-linear, x-linear, yy, xx, xy)"""
+    s = _f32(src, 1, "farnebackPolyExp", "src")
+    out = dst if dst is not None else _empty(src, (s.h, s.w, 5), np.float32)
+    d = _f32(out, 5, "farnebackPolyExp", "dst")
+    bind_stream(s, d)
+    _lib.check(L.mi355cv_farnebackPolyExp(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, int(poly_n), float(poly_sigma)), "farnebackPolyExp")
+    return out
+
+
+def farnebackUpdateMatrices(R0, R1, flow, M=None):
+    """M (G11, G12, G22, h1, h2; H x W x 5) from the two expansions and the flow"""
+    e = "farnebackUpdateMatrices"
+    a, b, f = _f32(R0, 5, e, "R0"), _f32(R1, 5, e, "R1"), _f32(flow, 2, e, "flow")
+    out = M if M is not None else _empty(R0, (a.h, a.w, 5), np.float32)
+    m = _f32(out, 5, e, "M")
+    if len({(i.w, i.h) for i in (a, b, f, m)}) != 1:
+        raise ValueError("farnebackUpdateMatrices: R0, R1, flow and M of one size")
+    bind_stream(a, b, f, m)
+    _lib.check(L.mi355cv_farnebackUpdateMatrices(_vp(a.ptr), a.step, _vp(b.ptr), b.step, _vp(f.ptr), f.step, _vp(m.ptr), m.step, a.w, a.h), e)
+    return out
+
+
+def farnebackUpdateFlow(M, winsize, flags=0, flow=None, R0=None, R1=None, M_next=None):
+    """one iteration: the flow (H x W x 2) from the window sums of M.  With R0 and R1 the update matrix of the new flow is computed too, as every iteration but the
+    last does: returns (flow, M_next) then, else the flow."""
+    e = "farnebackUpdateFlow"
+    m = _f32(M, 5, e, "M")
+    out = flow if flow is not None else _empty(M, (m.h, m.w, 2), np.float32)
+    f = _f32(out, 2, e, "flow")
+    update = R0 is not None or R1 is not None
+    if update:
+        a, b = _f32(R0, 5, e, "R0"), _f32(R1, 5, e, "R1")
+        nxt = M_next if M_next is not None else _empty(M, (m.h, m.w, 5), np.float32)
+        n = _f32(nxt, 5, e, "M_next")
+        bind_stream(m, f, a, b, n)
+        rc = L.mi355cv_farnebackUpdateFlow(_vp(m.ptr), m.step, _vp(f.ptr), f.step, _vp(a.ptr), a.step, _vp(b.ptr), b.step, _vp(n.ptr), n.step, m.w, m.h, int(winsize), int(flags))
+    else:
+        bind_stream(m, f)
+        rc = L.mi355cv_farnebackUpdateFlow(_vp(m.ptr), m.step, _vp(f.ptr), f.step, None, 0, None, 0, None, 0, m.w, m.h, int(winsize), int(flags))
+    _lib.check(rc, e)
+    return (out, nxt) if update else out
