@@ -794,6 +794,37 @@ MI355CV_API int mi355cv_ORB_detectAndCompute(const mi355cv_uchar* image, size_t 
         const mi355cv_OrbParams* params, int use_provided_keypoints, mi355cv_KeyPoint* keypoints, int nkeypoints_in, int capacity,
         mi355cv_uchar* descriptors, size_t descriptors_step);
 
+/* --------------------------------------------------- f3: features2d BFMatcher (csrc/bfmatch.hip) */
+/* cv::DMatch (core/types.hpp): 16 bytes.  A list shorter than its plane is padded with cv::DMatch's default, {-1, -1, -1, FLT_MAX} */
+typedef struct mi355cv_DMatch { int queryIdx, trainIdx, imgIdx; float distance; } mi355cv_DMatch;
+/* cv::BFMatcher::knnMatch (modules/features2d, no HAL hook; the definition served is written down in DESIGN 6.16 and tests/bfmatch_restate.py).  `query`: nq rows of `len`
+ * elements of `type` (MI355CV_8U or MI355CV_32F, one channel) at pitch query_step; the train collection: nimg matrices train[i] of train_rows[i] rows at train_step[i],
+ * imgIdx = i; masks: NULL, or nimg pointers, each NULL or a CV_8UC1 nq x train_rows[i] matrix at mask_step[i] (0 excludes the pair).  normType: 6 NORM_HAMMING /
+ * 7 NORM_HAMMING2 on CV_8U, 2 NORM_L1 / 4 NORM_L2 / 5 NORM_L2SQR on CV_32F (every float operation rounded on its own, elements ascending; L2 the correctly rounded
+ * root).  A pair whose distance is NaN is not a candidate.  Candidates of a query are ordered by (distance, imgIdx, trainIdx); `matches` is the nq x k plane of the first
+ * k of them per query, counts[q] = how many there are.  crossCheck != 0 (k = 1 only, anything else is an error): (q, t) stays iff q is also the best query of t by
+ * (distance, queryIdx).  Every matrix may live in host memory (staged through HBM, host-cost class HOST_HEAVY) or in this thread's device memory, at any pitch and, for
+ * CV_8U, any byte address; with device outputs nothing is downloaded.  nq = 0 and train_rows[i] = 0 are legal.
+ * Declined (MI355CV_NOT_IMPLEMENTED): other (type, normType) pairs; nq or the collection's rows above mi355cv_limit("bfmatch_max_rows") = 2^24; k outside
+ * 1 .. mi355cv_limit("bfmatch_max_k") = 8; rows above mi355cv_limit("bfmatch_max_row_bytes") = 2048 bytes; nimg outside 1 .. mi355cv_limit("bfmatch_max_images") = 64; a
+ * pitch below the row; CV_32F rows, matches or counts off a 4-byte boundary; crossCheck with a mask or with nimg > 1. */
+MI355CV_API int mi355cv_bfKnnMatch(const void* query, size_t query_step, int nq, int len, int type, const void* const* train, const size_t* train_step,
+        const int* train_rows, const void* const* masks, const size_t* mask_step, int nimg, int normType, int k, int crossCheck, mi355cv_DMatch* matches, int* counts);
+/* npairs independent (query[b], train[b]) pairs with their own row counts in ONE sequence of launches; exactly the results of npairs single calls (one train matrix,
+ * no mask).  matches[b]: the nq[b] x k plane of pair b, counts[b]: its nq[b] counts.  npairs <= 65535. */
+MI355CV_API int mi355cv_bfKnnMatchBatch(const void* const* query, const size_t* query_step, const int* nq, const void* const* train, const size_t* train_step,
+        const int* train_rows, int npairs, int len, int type, int normType, int k, int crossCheck, mi355cv_DMatch* const* matches, int* const* counts);
+/* cv::BFMatcher::radiusMatch: every candidate with distance <= maxDistance, per query in (distance, imgIdx, trainIdx) order; the lists of queries 0 .. nq - 1 follow one
+ * another in `matches`, counts[q] their lengths.  The capacity convention of mi355cv_FAST: returns the total (>= 0; at most `capacity` records were written: call again
+ * with a larger array if it exceeds capacity), -1 arguments not served, -2 device failure.  Declined as well: a query with more than
+ * mi355cv_limit("bfmatch_max_radius_row") = 4096 matches (its list is sorted in LDS). */
+MI355CV_API int mi355cv_bfRadiusMatch(const void* query, size_t query_step, int nq, int len, int type, const void* const* train, const size_t* train_step,
+        const int* train_rows, const void* const* masks, const size_t* mask_step, int nimg, int normType, float maxDistance, mi355cv_DMatch* matches, int capacity,
+        int* counts);
+/* A/B switch of the split of the train rows over workgroups (tools/bfmatch_bench.py --ab): 0 one pass over all train rows per query, -1 or 1 the built-in rule
+ * (parts of mi355cv_limit("bfmatch_split_rows") rows merged by key).  Results do not depend on it. */
+MI355CV_API int mi355cv_bfSetSplitMode(int mode);
+
 #ifdef __cplusplus
 }
 #endif

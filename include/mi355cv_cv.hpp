@@ -604,6 +604,92 @@ inline cv::Ptr<cv::ORB> ORB_create(int nfeatures = 500, float scaleFactor = 1.2f
 {
     return cv::makePtr<mi355cv::ORB>(cv::ORB::create(nfeatures, scaleFactor, nlevels, edgeThreshold, firstLevel, WTA_K, scoreType, patchSize, fastThreshold));
 }
+
+// cv::BFMatcher (features2d.hpp; matchers.cpp).  The reference has no HAL hook for matching.  mi355cv::BFMatcher is a cv::BFMatcher whose knnMatchImpl / radiusMatchImpl
+// (what match / knnMatch / radiusMatch of DescriptorMatcher end in, with an explicit train matrix or the add()-ed collection) send cv::Mat descriptors through
+// mi355cv_bfKnnMatch / mi355cv_bfRadiusMatch and hand everything the library declines (UMat, other types or norms, crossCheck with masks or several train matrices, no
+// device) to the stock implementation.  The order the library serves -- (distance, imgIdx, trainIdx), DESIGN 6.16 -- fully determines every list; where the stock
+// implementation orders equal distances otherwise the two differ in exactly those places.  Written against the reference's declarations as recollected: the reference's
+// headers are not in this tree, so this class has not been compiled here.
+class BFMatcher CV_FINAL : public cv::BFMatcher
+{
+public:
+    explicit BFMatcher(int normType_ = cv::NORM_L2, bool crossCheck_ = false) : cv::BFMatcher(normType_, crossCheck_) {}
+    static cv::Ptr<mi355cv::BFMatcher> create(int normType_ = cv::NORM_L2, bool crossCheck_ = false) { return cv::makePtr<mi355cv::BFMatcher>(normType_, crossCheck_); }
+
+protected:
+    struct Lists { std::vector<const void*> t, m; std::vector<size_t> tstep, mstep; std::vector<int> rows; bool ok = true; bool anyMask = false; };
+    Lists gather(const cv::Mat& query, cv::InputArrayOfArrays _masks) const
+    {
+        Lists l;
+        std::vector<cv::Mat> masks;
+        if (!_masks.empty()) _masks.getMatVector(masks);
+        if (!masks.empty() && masks.size() != trainDescCollection.size()) { l.ok = false; return l; }
+        for (size_t i = 0; i < trainDescCollection.size(); i++) {
+            const cv::Mat& t = trainDescCollection[i];
+            if (t.dims > 2 || (!t.empty() && (t.type() != query.type() || t.cols != query.cols))) { l.ok = false; return l; }
+            l.t.push_back(t.data); l.tstep.push_back(t.empty() ? 0 : (size_t)t.step); l.rows.push_back(t.rows);
+            const bool has = !masks.empty() && !masks[i].empty();
+            if (has && (masks[i].type() != CV_8UC1 || masks[i].rows != query.rows || masks[i].cols != t.rows)) { l.ok = false; return l; }
+            l.m.push_back(has ? masks[i].data : nullptr); l.mstep.push_back(has ? (size_t)masks[i].step : 0);
+            l.anyMask = l.anyMask || has;
+        }
+        if (!utrainDescCollection.empty() || trainDescCollection.empty()) l.ok = false;
+        return l;
+    }
+
+    void knnMatchImpl(cv::InputArray _query, std::vector<std::vector<cv::DMatch> >& matches, int k, cv::InputArrayOfArrays _masks = cv::noArray(),
+                      bool compactResult = false) CV_OVERRIDE
+    {
+        static_assert(sizeof(cv::DMatch) == sizeof(mi355cv_DMatch), "cv::DMatch is the 16-byte record mi355cv_DMatch declares");
+        if (_query.kind() == cv::_InputArray::MAT && k >= 1) {
+            const cv::Mat query = _query.getMat();
+            const Lists l = gather(query, _masks);
+            if (l.ok && query.dims <= 2 && !query.empty() && query.channels() == 1) {
+                std::vector<cv::DMatch> plane((size_t)query.rows * k);
+                std::vector<int> counts(query.rows);
+                if (mi355cv_bfKnnMatch(query.data, query.step, query.rows, query.cols, query.type(), l.t.data(), l.tstep.data(), l.rows.data(), l.anyMask ? l.m.data() : nullptr,
+                                       l.mstep.data(), (int)l.t.size(), normType, k, crossCheck ? 1 : 0, reinterpret_cast<mi355cv_DMatch*>(plane.data()), counts.data()) == MI355CV_OK) {
+                    matches.clear();
+                    for (int q = 0; q < query.rows; q++) {
+                        if (compactResult && !counts[q]) continue;
+                        matches.emplace_back(plane.begin() + (size_t)q * k, plane.begin() + (size_t)q * k + counts[q]);
+                    }
+                    return;
+                }
+            }
+        }
+        cv::BFMatcher::knnMatchImpl(_query, matches, k, _masks, compactResult);
+    }
+
+    void radiusMatchImpl(cv::InputArray _query, std::vector<std::vector<cv::DMatch> >& matches, float maxDistance, cv::InputArrayOfArrays _masks = cv::noArray(),
+                         bool compactResult = false) CV_OVERRIDE
+    {
+        if (_query.kind() == cv::_InputArray::MAT && !crossCheck) {
+            const cv::Mat query = _query.getMat();
+            const Lists l = gather(query, _masks);
+            if (l.ok && query.dims <= 2 && !query.empty() && query.channels() == 1) {
+                std::vector<cv::DMatch> flat(std::max<size_t>(1024, 4 * (size_t)query.rows));
+                std::vector<int> counts(query.rows);
+                for (;;) {
+                    const int n = mi355cv_bfRadiusMatch(query.data, query.step, query.rows, query.cols, query.type(), l.t.data(), l.tstep.data(), l.rows.data(),
+                                                        l.anyMask ? l.m.data() : nullptr, l.mstep.data(), (int)l.t.size(), normType, maxDistance,
+                                                        reinterpret_cast<mi355cv_DMatch*>(flat.data()), (int)flat.size(), counts.data());
+                    if (n < 0) break;                                             // declined or failed: the stock implementation below
+                    if ((size_t)n > flat.size()) { flat.resize((size_t)n); continue; }
+                    matches.clear();
+                    size_t at = 0;
+                    for (int q = 0; q < query.rows; q++) {
+                        if (!compactResult || counts[q]) matches.emplace_back(flat.begin() + at, flat.begin() + at + counts[q]);
+                        at += (size_t)counts[q];
+                    }
+                    return;
+                }
+            }
+        }
+        cv::BFMatcher::radiusMatchImpl(_query, matches, maxDistance, _masks, compactResult);
+    }
+};
 #endif
 
 #ifdef OPENCV_TRACKING_HPP      // cv::calcOpticalFlowPyrLK lives in opencv2/video/tracking.hpp; include it before this header to get the wrapper

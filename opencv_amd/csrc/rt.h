@@ -46,6 +46,13 @@ constexpr int FARNEBACK_MAX_DIM = 16384;   // mi355cv_calcOpticalFlowFarneback* 
 constexpr int FARNEBACK_MAX_WINSIZE = 25;  // ... the averaging window: the M tile with its halo and the vertical sums of k_fb_update_flow fit 64 KiB of LDS
 constexpr int FARNEBACK_MAX_POLY_N = 7;    // ... the half-width of the polynomial expansion: taps in the kernel arguments, LDS tiles sized for it
 constexpr int FARNEBACK_MAX_SMOOTH_TAPS = 255; // ... the taps of a pyramid level's Gaussian, max(cvRound(5 sigma) | 1, 3) with sigma = (1 / scale - 1) / 2
+constexpr int BFMATCH_MAX_ROWS = 1 << 24;      // mi355cv_bf*: rows per matrix and per train collection (the global train row is the low word of the 64-bit key; bfmatch_math.h)
+constexpr int BFMATCH_MAX_K = 8;               // ... k of knnMatch: the list lives in registers with compile-time indices
+constexpr int BFMATCH_MAX_ROW_BYTES = 2048;    // ... bytes per descriptor row (512 floats)
+constexpr int BFMATCH_MAX_IMAGES = 64;         // ... train matrices per collection
+constexpr int BFMATCH_MAX_RADIUS_ROW = 4096;   // ... matches of one query in radiusMatch: its keys are sorted in 32 KiB of LDS
+constexpr int BFMATCH_TILE_ROWS = 256;         // ... geometry, reported for the tests' shapes: train rows per LDS tile of k_bf_hamming
+constexpr int BFMATCH_SPLIT_ROWS = 512;        // ... and train rows per workgroup when the train set is split
 }
 
 struct ThreadCtx;

@@ -575,7 +575,9 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"demosaic_max_dim", DEMOSAIC_MAX_DIM}, {"calchist_max_dim", CALCHIST_MAX_DIM}, {"calchist_max_bins", CALCHIST_MAX_BINS},
         {"mog2_max_dim", MOG2_MAX_DIM}, {"mog2_max_mixtures", MOG2_MAX_MIXTURES},
         {"farneback_max_dim", FARNEBACK_MAX_DIM}, {"farneback_max_winsize", FARNEBACK_MAX_WINSIZE}, {"farneback_max_poly_n", FARNEBACK_MAX_POLY_N},
-        {"farneback_max_smooth_taps", FARNEBACK_MAX_SMOOTH_TAPS}};
+        {"farneback_max_smooth_taps", FARNEBACK_MAX_SMOOTH_TAPS},
+        {"bfmatch_max_rows", BFMATCH_MAX_ROWS}, {"bfmatch_max_k", BFMATCH_MAX_K}, {"bfmatch_max_row_bytes", BFMATCH_MAX_ROW_BYTES}, {"bfmatch_max_images", BFMATCH_MAX_IMAGES},
+        {"bfmatch_max_radius_row", BFMATCH_MAX_RADIUS_ROW}, {"bfmatch_tile_rows", BFMATCH_TILE_ROWS}, {"bfmatch_split_rows", BFMATCH_SPLIT_ROWS}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
