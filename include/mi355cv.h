@@ -825,6 +825,38 @@ MI355CV_API int mi355cv_bfRadiusMatch(const void* query, size_t query_step, int 
  * (parts of mi355cv_limit("bfmatch_split_rows") rows merged by key).  Results do not depend on it. */
 MI355CV_API int mi355cv_bfSetSplitMode(int mode);
 
+/* --------------------------------------------------- f3: calib3d StereoBM (csrc/stereobm.hip) */
+/* The parameters of cv::StereoBM (calib3d.hpp).  numDisparities <= 0 means 64; preFilterType: 0 PREFILTER_NORMALIZED_RESPONSE, 1 PREFILTER_XSOBEL; roi1 / roi2 are
+ * (x, y, width, height), all zero when unset.  mi355cv_stereoBMDefaults fills the values of StereoBM::create(0, 21). */
+typedef struct mi355cv_StereoBMParams {
+    int minDisparity, numDisparities, blockSize, preFilterType, preFilterSize, preFilterCap, textureThreshold, uniquenessRatio, speckleWindowSize, speckleRange, disp12MaxDiff;
+    int roi1[4], roi2[4];
+} mi355cv_StereoBMParams;
+MI355CV_API void mi355cv_stereoBMDefaults(mi355cv_StereoBMParams* params);
+/* cv::StereoBM::compute (modules/calib3d, no HAL hook; the definition served is written down in DESIGN 6.17 and tests/stereobm_restate.py) on two rectified CV_8UC1
+ * images of width x height: the CV_16SC1 map of disparities times 16 (disp_depth = MI355CV_16S) or the CV_32FC1 map of disparities (MI355CV_32F, the former divided by
+ * 16, exact).  A pixel without a disparity holds (minDisparity - 1) * 16, respectively minDisparity - 1.  All arithmetic is integer: the map is determined bit for bit.
+ * Every image may live in host memory (staged through HBM, host-cost class HOST_HEAVY) or in this thread's device memory, at any pitch and byte address; device
+ * pointers run on the current stream.
+ * Declined (MI355CV_NOT_IMPLEMENTED, disp left untouched): PREFILTER_NORMALIZED_RESPONSE; speckleWindowSize > 0; roi1 / roi2 set; other disparity depths; numDisparities
+ * not a positive multiple of 16 or above mi355cv_limit("stereobm_max_disparities") = 256; blockSize even, below 5, above min(width, height) or above
+ * mi355cv_limit("stereobm_max_block") = 51; preFilterCap outside 1 .. 63; a negative textureThreshold or uniquenessRatio; width or height above
+ * mi355cv_limit("stereobm_max_dim") = 16384; disparities that leave the CV_16S map's range (minDisparity < -2047 or minDisparity + numDisparities - 1 > 2046); a pitch below
+ * the row; disparity rows off their element's boundary; a disparity map that overlaps an input. */
+MI355CV_API int mi355cv_stereoBM(const mi355cv_uchar* left, size_t left_step, const mi355cv_uchar* right, size_t right_step, mi355cv_uchar* disp, size_t disp_step,
+        int width, int height, int disp_depth, const mi355cv_StereoBMParams* params);
+/* nframes pairs at left + f * left_frame_stride, right + f * right_frame_stride into disp + f * disp_frame_stride in ONE sequence of launches; exactly the results of
+ * nframes single calls.  Declined as well: nframes < 1 or > 65535, a frame stride below the frame. */
+MI355CV_API int mi355cv_stereoBMBatch(const mi355cv_uchar* left, size_t left_step, size_t left_frame_stride, const mi355cv_uchar* right, size_t right_step,
+        size_t right_frame_stride, mi355cv_uchar* disp, size_t disp_step, size_t disp_frame_stride, int nframes, int width, int height, int disp_depth,
+        const mi355cv_StereoBMParams* params);
+/* The stage entry: the XSOBEL prefilter of one CV_8UC1 image, dst = clip(cap + the 3 x 3 x-Sobel, 0, 2 cap), rows under BORDER_REFLECT_101, the first and last column = cap.
+ * cap in 1 .. 63. */
+MI355CV_API int mi355cv_stereoPrefilterXSobel(const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* dst, size_t dst_step, int width, int height, int cap);
+/* A/B switch of the cost kernel (tools/stereobm_bench.py): -1 the built-in rule (blockSize <= mi355cv_limit("stereobm_roll_max_block") = 21: the rolling kernel), 0 always
+ * the generic kernel.  Results do not depend on it. */
+MI355CV_API int mi355cv_stereoBMSetKernel(int mode);
+
 #ifdef __cplusplus
 }
 #endif

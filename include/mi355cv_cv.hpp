@@ -835,6 +835,67 @@ inline cv::Ptr<cv::BackgroundSubtractorMOG2> createBackgroundSubtractorMOG2(int 
 }
 #endif
 
+#ifdef OPENCV_CALIB3D_HPP       // cv::StereoBM lives in opencv2/calib3d.hpp; include it before this header to get the wrapper
+// cv::StereoBM (calib3d.hpp; stereobm.cpp).  The reference has no HAL hook for it.  mi355cv::StereoBM::create returns a cv::StereoBM that wraps the stock object, where
+// the parameters live; compute sends two 2-D CV_8UC1 cv::Mat images through mi355cv_stereoBM (csrc/stereobm.hip), the images and the CV_16SC1 map staying where the Mats
+// live.  The map is the project's restatement of the algorithm (tests/stereobm_restate.py), all integer and determined bit for bit; where recollection of
+// the reference differs it is listed there.  Everything the entry declines (PREFILTER_NORMALIZED_RESPONSE, speckle filtering, ROIs, sizes over the limits, UMat, no
+// device) goes to the stock object, which finds the map untouched.  Not compiled here: the reference's headers are absent.
+class StereoBM CV_FINAL : public cv::StereoBM
+{
+public:
+    explicit StereoBM(const cv::Ptr<cv::StereoBM>& stock) : stock_(stock) {}
+    static cv::Ptr<cv::StereoBM> create(int numDisparities = 0, int blockSize = 21) { return cv::makePtr<mi355cv::StereoBM>(cv::StereoBM::create(numDisparities, blockSize)); }
+
+    int getMinDisparity() const CV_OVERRIDE { return stock_->getMinDisparity(); }              void setMinDisparity(int v) CV_OVERRIDE { stock_->setMinDisparity(v); }
+    int getNumDisparities() const CV_OVERRIDE { return stock_->getNumDisparities(); }          void setNumDisparities(int v) CV_OVERRIDE { stock_->setNumDisparities(v); }
+    int getBlockSize() const CV_OVERRIDE { return stock_->getBlockSize(); }                    void setBlockSize(int v) CV_OVERRIDE { stock_->setBlockSize(v); }
+    int getSpeckleWindowSize() const CV_OVERRIDE { return stock_->getSpeckleWindowSize(); }    void setSpeckleWindowSize(int v) CV_OVERRIDE { stock_->setSpeckleWindowSize(v); }
+    int getSpeckleRange() const CV_OVERRIDE { return stock_->getSpeckleRange(); }              void setSpeckleRange(int v) CV_OVERRIDE { stock_->setSpeckleRange(v); }
+    int getDisp12MaxDiff() const CV_OVERRIDE { return stock_->getDisp12MaxDiff(); }            void setDisp12MaxDiff(int v) CV_OVERRIDE { stock_->setDisp12MaxDiff(v); }
+    int getPreFilterType() const CV_OVERRIDE { return stock_->getPreFilterType(); }            void setPreFilterType(int v) CV_OVERRIDE { stock_->setPreFilterType(v); }
+    int getPreFilterSize() const CV_OVERRIDE { return stock_->getPreFilterSize(); }            void setPreFilterSize(int v) CV_OVERRIDE { stock_->setPreFilterSize(v); }
+    int getPreFilterCap() const CV_OVERRIDE { return stock_->getPreFilterCap(); }              void setPreFilterCap(int v) CV_OVERRIDE { stock_->setPreFilterCap(v); }
+    int getTextureThreshold() const CV_OVERRIDE { return stock_->getTextureThreshold(); }      void setTextureThreshold(int v) CV_OVERRIDE { stock_->setTextureThreshold(v); }
+    int getUniquenessRatio() const CV_OVERRIDE { return stock_->getUniquenessRatio(); }        void setUniquenessRatio(int v) CV_OVERRIDE { stock_->setUniquenessRatio(v); }
+    int getSmallerBlockSize() const CV_OVERRIDE { return stock_->getSmallerBlockSize(); }      void setSmallerBlockSize(int v) CV_OVERRIDE { stock_->setSmallerBlockSize(v); }
+    cv::Rect getROI1() const CV_OVERRIDE { return stock_->getROI1(); }                         void setROI1(cv::Rect r) CV_OVERRIDE { stock_->setROI1(r); }
+    cv::Rect getROI2() const CV_OVERRIDE { return stock_->getROI2(); }                         void setROI2(cv::Rect r) CV_OVERRIDE { stock_->setROI2(r); }
+    void clear() CV_OVERRIDE { stock_->clear(); }
+    bool empty() const CV_OVERRIDE { return stock_->empty(); }
+    void write(cv::FileStorage& fs) const CV_OVERRIDE { stock_->write(fs); }
+    void read(const cv::FileNode& fn) CV_OVERRIDE { stock_->read(fn); }
+    cv::String getDefaultName() const CV_OVERRIDE { return stock_->getDefaultName(); }
+
+    void compute(cv::InputArray _left, cv::InputArray _right, cv::OutputArray _disp) CV_OVERRIDE
+    {
+        if (_left.kind() == cv::_InputArray::MAT && _right.kind() == cv::_InputArray::MAT && !_disp.isUMat()) {
+            cv::Mat left = _left.getMat(), right = _right.getMat();
+            // the reference writes CV_16S unless the destination was fixed to CV_32F by the caller
+            const int dtype = _disp.fixedType() && _disp.type() == CV_32FC1 ? CV_32FC1 : CV_16SC1;
+            if (left.dims <= 2 && !left.empty() && left.type() == CV_8UC1 && right.type() == CV_8UC1 && left.size() == right.size()) {
+                mi355cv_StereoBMParams p;
+                mi355cv_stereoBMDefaults(&p);
+                p.minDisparity = getMinDisparity(); p.numDisparities = getNumDisparities(); p.blockSize = getBlockSize(); p.preFilterType = getPreFilterType();
+                p.preFilterSize = getPreFilterSize(); p.preFilterCap = getPreFilterCap(); p.textureThreshold = getTextureThreshold(); p.uniquenessRatio = getUniquenessRatio();
+                p.speckleWindowSize = getSpeckleWindowSize(); p.speckleRange = getSpeckleRange(); p.disp12MaxDiff = getDisp12MaxDiff();
+                const cv::Rect r1 = getROI1(), r2 = getROI2();
+                p.roi1[0] = r1.x; p.roi1[1] = r1.y; p.roi1[2] = r1.width; p.roi1[3] = r1.height;
+                p.roi2[0] = r2.x; p.roi2[1] = r2.y; p.roi2[2] = r2.width; p.roi2[3] = r2.height;
+                // an overlapping destination is declined by the entry and the stock object then allocates as it always does
+                cv::Mat disp = _disp.getMat();
+                if (disp.size() != left.size() || disp.type() != dtype) { _disp.create(left.size(), dtype); disp = _disp.getMat(); }
+                if (mi355cv_stereoBM(left.data, left.step, right.data, right.step, disp.data, disp.step, left.cols, left.rows, dtype == CV_32FC1 ? MI355CV_32F : MI355CV_16S, &p) == MI355CV_OK)
+                    return;
+            }
+        }
+        stock_->compute(_left, _right, _disp);
+    }
+private:
+    cv::Ptr<cv::StereoBM> stock_;
+};
+#endif
+
 // Batches across the GPUs of one node from C++: forEachShard({0,1,...,7}, nframes, [&](int slot, int device, int first, int count) { ... return 0; })
 // runs the callable once per device on its own host thread bound to that device (mi355cv_runSharded, csrc/shard.hip), frames [first, first + count) being that
 // device's share; inside, call cv:: functions of a HAL-enabled build or mi355cv:: / mi355cv_*Batch entry points on Mats whose storage lives on `device`

@@ -16,5 +16,6 @@ from .core import *  # noqa: F401,F403
 from .imgproc import *  # noqa: F401,F403
 from .video import *  # noqa: F401,F403
 from .features2d import *  # noqa: F401,F403
+from .calib3d import *  # noqa: F401,F403
 
 __version__ = "0.1"

@@ -73,6 +73,11 @@ def _load():
         "mi355cv_bfRadiusMatch": (c_int, [ctypes.c_void_p, c_sz, c_int, c_int, c_int, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p, c_int,
                                           c_int, ctypes.c_float, ctypes.c_void_p, c_int, ctypes.c_void_p]),
         "mi355cv_bfSetSplitMode": (c_int, [c_int]),
+        "mi355cv_stereoBMDefaults": (None, [ctypes.c_void_p]),
+        "mi355cv_stereoBM": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_stereoBMBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_stereoPrefilterXSobel": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int]),
+        "mi355cv_stereoBMSetKernel": (c_int, [c_int]),
         "mi355cv_remap": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int,
                                   c_int, c_int, ctypes.c_void_p]),
         "mi355cv_convertMaps": (c_int, [ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz,

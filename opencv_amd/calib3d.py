@@ -1,0 +1,139 @@
+"""Host-side mirror of cv::StereoBM (modules/calib3d; the reference has no HAL hook for it): the parameters with the reference's getters and setters, compute on one
+rectified pair and computeBatch on N x H x W stacks.  The maps are made by mi355cv_stereoBM / mi355cv_stereoBMBatch (opencv_amd/csrc/stereobm.hip); torch device
+tensors stay in HBM, numpy arrays are staged, the result has the kind of the input.  The definition served is the project's restatement."""
+import ctypes
+
+import numpy as np
+
+from . import _lib
+from .core import Img, bind_stream, torch, CV_8U, CV_16S, CV_32F
+
+__all__ = ["StereoBM", "StereoBM_create", "stereoPrefilterXSobel", "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "StereoBM_PREFILTER_NORMALIZED_RESPONSE",
+           "StereoBM_PREFILTER_XSOBEL", "StereoBM_DISP_SHIFT", "StereoBM_DISP_SCALE"]
+
+L = _lib.lib
+PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1
+StereoBM_PREFILTER_NORMALIZED_RESPONSE, StereoBM_PREFILTER_XSOBEL = 0, 1
+StereoBM_DISP_SHIFT = 4
+StereoBM_DISP_SCALE = 1 << StereoBM_DISP_SHIFT
+
+_FIELDS = ("minDisparity", "numDisparities", "blockSize", "preFilterType", "preFilterSize", "preFilterCap", "textureThreshold", "uniquenessRatio", "speckleWindowSize",
+           "speckleRange", "disp12MaxDiff")
+
+
+class StereoBMParams(ctypes.Structure):
+    """mi355cv_StereoBMParams"""
+    _fields_ = [(f, ctypes.c_int) for f in _FIELDS] + [("roi1", ctypes.c_int * 4), ("roi2", ctypes.c_int * 4)]
+
+
+def _vp(p):
+    return ctypes.c_void_p(p)
+
+
+def _decline(entry, why):
+    """a refusal the C ABI cannot see (it takes no type argument for the inputs): counted in the decline ledger like the library's own"""
+    L.mi355cv_noteDecline(entry.encode())
+    raise NotImplementedError("mi355cv_%s: NOT_IMPLEMENTED for these arguments (%s); no CPU fallback in opencv_amd" % (entry, why))
+
+
+def _empty(ref, shape, depth):
+    if torch is not None and isinstance(ref, torch.Tensor):
+        return torch.empty(shape, dtype=torch.int16 if depth == CV_16S else torch.float32, device=ref.device)
+    return np.empty(shape, np.int16 if depth == CV_16S else np.float32)
+
+
+def _frame_stride(a):
+    return int(a.stride(0)) * a.element_size() if torch is not None and isinstance(a, torch.Tensor) else int(a.strides[0])
+
+
+class StereoBM:
+    """cv::StereoBM.  compute(left, right) -> the CV_16S map of disparities x 16 (pass disp= a float32 array / tensor, or disptype=CV_32F, for the CV_32F map of
+    disparities); a pixel without a disparity holds (minDisparity - 1) * 16, respectively minDisparity - 1."""
+    PREFILTER_NORMALIZED_RESPONSE, PREFILTER_XSOBEL = 0, 1
+    DISP_SHIFT, DISP_SCALE = StereoBM_DISP_SHIFT, StereoBM_DISP_SCALE
+
+    def __init__(self, numDisparities=0, blockSize=21):
+        self._p = StereoBMParams()
+        L.mi355cv_stereoBMDefaults(ctypes.byref(self._p))
+        self._p.numDisparities = int(numDisparities)
+        self._p.blockSize = int(blockSize)
+
+    def getROI1(self): return tuple(self._p.roi1)
+    def getROI2(self): return tuple(self._p.roi2)
+    def setROI1(self, roi): self._p.roi1 = (ctypes.c_int * 4)(*[int(v) for v in roi])
+    def setROI2(self, roi): self._p.roi2 = (ctypes.c_int * 4)(*[int(v) for v in roi])
+    def getDefaultName(self): return "StereoMatcher.BM"
+
+    def _disp(self, ref, shape, disp, disptype, entry):
+        if disp is None:
+            if disptype not in (CV_16S, CV_32F):
+                _decline(entry, "the disparity map is neither CV_16SC1 nor CV_32FC1")
+            disp = _empty(ref, shape, disptype)
+        if tuple(int(v) for v in disp.shape) != tuple(shape):
+            raise ValueError("%s: disp must have the shape of the inputs" % entry)
+        return disp
+
+    def compute(self, left, right, disp=None, disptype=CV_16S):
+        entry = "stereoBM"
+        a, b = Img(left), Img(right)
+        if (a.depth, a.cn) != (CV_8U, 1) or (b.depth, b.cn) != (CV_8U, 1):
+            _decline(entry, "inputs must be CV_8UC1")
+        if (a.w, a.h) != (b.w, b.h):
+            raise ValueError("stereoBM: two images of the same size")
+        disp = self._disp(left, (a.h, a.w), disp, disptype, entry)
+        d = Img(disp)
+        if d.cn != 1 or d.depth not in (CV_16S, CV_32F):
+            _decline(entry, "the disparity map is neither CV_16SC1 nor CV_32FC1")
+        bind_stream(a, b, d)
+        _lib.check(L.mi355cv_stereoBM(_vp(a.ptr), a.step, _vp(b.ptr), b.step, _vp(d.ptr), d.step, a.w, a.h, d.depth, ctypes.byref(self._p)), entry)
+        return disp
+
+    def computeBatch(self, lefts, rights, disp=None, disptype=CV_16S):
+        """N pairs stacked as N x H x W -> N x H x W maps, each bit for bit the single call's, in one sequence of launches"""
+        entry = "stereoBMBatch"
+        stack = lambda v: (torch.stack(list(v)) if torch is not None and isinstance(v[0], torch.Tensor) else np.stack([np.asarray(f) for f in v])) if isinstance(v, (list, tuple)) else v
+        lefts, rights = stack(lefts), stack(rights)
+        if lefts.ndim != 3 or tuple(lefts.shape) != tuple(rights.shape) or int(lefts.shape[0]) < 1:
+            raise ValueError("stereoBMBatch: two stacks N x H x W of the same shape")
+        n = int(lefts.shape[0])
+        a, b = Img(lefts[0]), Img(rights[0])
+        if (a.depth, a.cn) != (CV_8U, 1) or (b.depth, b.cn) != (CV_8U, 1):
+            _decline(entry, "inputs must be CV_8UC1")
+        disp = self._disp(lefts, (n, a.h, a.w), disp, disptype, entry)
+        d = Img(disp[0])
+        if d.depth not in (CV_16S, CV_32F):
+            _decline(entry, "the disparity map is neither CV_16SC1 nor CV_32FC1")
+        bind_stream(a, b, d)
+        _lib.check(L.mi355cv_stereoBMBatch(_vp(a.ptr), a.step, _frame_stride(lefts), _vp(b.ptr), b.step, _frame_stride(rights), _vp(d.ptr), d.step, _frame_stride(disp), n,
+                                           a.w, a.h, d.depth, ctypes.byref(self._p)), entry)
+        return disp
+
+
+def _accessors(name):
+    cap = name[0].upper() + name[1:]
+    setattr(StereoBM, "get" + cap, lambda self: int(getattr(self._p, name)))
+    setattr(StereoBM, "set" + cap, lambda self, v: setattr(self._p, name, int(v)))
+
+
+for _f in _FIELDS:
+    _accessors(_f)
+
+
+def StereoBM_create(numDisparities=0, blockSize=21):
+    """cv::StereoBM::create"""
+    return StereoBM(numDisparities, blockSize)
+
+
+def stereoPrefilterXSobel(src, cap, dst=None):
+    """the XSOBEL prefilter of StereoBM on one CV_8UC1 image (the stage entry)"""
+    s = Img(src)
+    if (s.depth, s.cn) != (CV_8U, 1):
+        _decline("stereoPrefilterXSobel", "src must be CV_8UC1")
+    if dst is None:
+        dst = torch.empty((s.h, s.w), dtype=torch.uint8, device=src.device) if torch is not None and isinstance(src, torch.Tensor) else np.empty((s.h, s.w), np.uint8)
+    d = Img(dst)
+    if (d.depth, d.cn, d.w, d.h) != (CV_8U, 1, s.w, s.h):
+        raise ValueError("stereoPrefilterXSobel: dst must be CV_8UC1 of the size of src")
+    bind_stream(s, d)
+    _lib.check(L.mi355cv_stereoPrefilterXSobel(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, int(cap)), "stereoPrefilterXSobel")
+    return dst

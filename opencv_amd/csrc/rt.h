@@ -53,6 +53,14 @@ constexpr int BFMATCH_MAX_IMAGES = 64;         // ... train matrices per collect
 constexpr int BFMATCH_MAX_RADIUS_ROW = 4096;   // ... matches of one query in radiusMatch: its keys are sorted in 32 KiB of LDS
 constexpr int BFMATCH_TILE_ROWS = 256;         // ... geometry, reported for the tests' shapes: train rows per LDS tile of k_bf_hamming
 constexpr int BFMATCH_SPLIT_ROWS = 512;        // ... and train rows per workgroup when the train set is split
+constexpr int STEREOBM_MAX_DIM = 16384;        // mi355cv_stereoBM*: width and height (the neighbours' bound; a column fits the 16 bits the left-right key gives it; stereobm_math.h)
+constexpr int STEREOBM_MAX_DISPARITIES = 256;  // ... numDisparities: a workgroup of the fast kernel is a wave per 16 disparities, 1024 lanes at most
+constexpr int STEREOBM_MAX_BLOCK = 51;         // ... blockSize: the generic kernel's two tiles of blockSize rows and its SADs fit 64 KiB of LDS at 256 disparities
+constexpr int STEREOBM_ROLL_MAX_BLOCK = 21;    // ... geometry, reported for the tests' shapes: the largest blockSize of the fast kernel (its SADs fit 16 bits)
+constexpr int STEREOBM_CHUNK = 16;             // ... disparities per lane of the fast kernel
+constexpr int STEREOBM_TILE_COLS = 64;         // ... window columns per workgroup of the fast kernel: 64 - (blockSize - 1) pixels of a row
+constexpr int STEREOBM_STRIP_ROWS = 32;        // ... rows a workgroup of the fast kernel walks down
+constexpr int STEREOBM_GENERIC_TILE_COLS = 32; // ... pixels of a row per workgroup of the generic kernel
 }
 
 struct ThreadCtx;

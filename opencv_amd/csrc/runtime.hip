@@ -577,7 +577,10 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"farneback_max_dim", FARNEBACK_MAX_DIM}, {"farneback_max_winsize", FARNEBACK_MAX_WINSIZE}, {"farneback_max_poly_n", FARNEBACK_MAX_POLY_N},
         {"farneback_max_smooth_taps", FARNEBACK_MAX_SMOOTH_TAPS},
         {"bfmatch_max_rows", BFMATCH_MAX_ROWS}, {"bfmatch_max_k", BFMATCH_MAX_K}, {"bfmatch_max_row_bytes", BFMATCH_MAX_ROW_BYTES}, {"bfmatch_max_images", BFMATCH_MAX_IMAGES},
-        {"bfmatch_max_radius_row", BFMATCH_MAX_RADIUS_ROW}, {"bfmatch_tile_rows", BFMATCH_TILE_ROWS}, {"bfmatch_split_rows", BFMATCH_SPLIT_ROWS}};
+        {"bfmatch_max_radius_row", BFMATCH_MAX_RADIUS_ROW}, {"bfmatch_tile_rows", BFMATCH_TILE_ROWS}, {"bfmatch_split_rows", BFMATCH_SPLIT_ROWS},
+        {"stereobm_max_dim", STEREOBM_MAX_DIM}, {"stereobm_max_disparities", STEREOBM_MAX_DISPARITIES}, {"stereobm_max_block", STEREOBM_MAX_BLOCK},
+        {"stereobm_roll_max_block", STEREOBM_ROLL_MAX_BLOCK}, {"stereobm_chunk", STEREOBM_CHUNK}, {"stereobm_tile_cols", STEREOBM_TILE_COLS},
+        {"stereobm_strip_rows", STEREOBM_STRIP_ROWS}, {"stereobm_generic_tile_cols", STEREOBM_GENERIC_TILE_COLS}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
