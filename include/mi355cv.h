@@ -857,6 +857,24 @@ MI355CV_API int mi355cv_stereoPrefilterXSobel(const mi355cv_uchar* src, size_t s
  * the generic kernel.  Results do not depend on it. */
 MI355CV_API int mi355cv_stereoBMSetKernel(int mode);
 
+/* --------------------------------------------------- f3: calib3d filterSpeckles (csrc/speckle.hip) */
+/* cv::filterSpeckles (modules/calib3d, no HAL hook; the definition served is written down in DESIGN 6.18 and tests/speckle_restate.py) on one channel of CV_8U or
+ * CV_16S (depth = MI355CV_8U / MI355CV_16S), IN PLACE: a pixel is live iff its value != newVal; two live 4-neighbours are linked iff |a - b| <= maxDiff (in int);
+ * every pixel of a connected component of at most maxSpeckleSize pixels becomes newVal, every other byte keeps its value.  maxSpeckleSize <= 0 erases nothing;
+ * maxDiff < 0 links nothing.  The image depends on component sizes only: it is determined bit for bit.  The image may live in host memory (staged through HBM,
+ * host-cost class HOST_HEAVY) or in this thread's device memory, at any pitch and any byte address a CV_8U / CV_16S row may have; device pointers run on the
+ * current stream.
+ * Declined (MI355CV_NOT_IMPLEMENTED, the image left untouched): other depths; a null pointer; width or height < 1 or above mi355cv_limit("speckle_max_dim") = 16384;
+ * a pitch below the row; CV_16S rows off a 2-byte boundary; newVal outside the depth's range (the reference would store it truncated). */
+MI355CV_API int mi355cv_filterSpeckles(mi355cv_uchar* img, size_t step, int width, int height, int depth, int newVal, int maxSpeckleSize, int maxDiff);
+/* nframes maps at img + f * frame_stride in ONE sequence of launches, the frame in the grid's z; every frame is bit for bit the single call's.  Declined as well:
+ * nframes < 1 or > 65535, frames that overlap (a frame stride below the frame). */
+MI355CV_API int mi355cv_filterSpecklesBatch(mi355cv_uchar* img, size_t step, size_t frame_stride, int nframes, int width, int height, int depth, int newVal,
+        int maxSpeckleSize, int maxDiff);
+/* A/B switch (tools/speckle_bench.py): -1 the built-in rule (the tile kernel, tiles of mi355cv_limit("speckle_tile_cols") x mi355cv_limit("speckle_tile_rows") merged
+ * in LDS), 0 always the plain per-pixel kernels.  Results do not depend on it. */
+MI355CV_API int mi355cv_filterSpecklesSetKernel(int mode);
+
 #ifdef __cplusplus
 }
 #endif

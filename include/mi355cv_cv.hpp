@@ -894,6 +894,23 @@ public:
 private:
     cv::Ptr<cv::StereoBM> stock_;
 };
+
+// cv::filterSpeckles (calib3d.hpp; stereosgbm.cpp).  The reference has no HAL hook for it.  A 2-D CV_8UC1 or CV_16SC1 cv::Mat goes through mi355cv_filterSpeckles
+// (csrc/speckle.hip) in place, where the Mat lives: the step to take on the map mi355cv::StereoBM::compute left in HBM.  The image is the project's restatement of the
+// algorithm (tests/speckle_restate.py): it depends on component sizes only and is determined bit for bit.  newVal and maxDiff are truncated to int as the
+// reference does; buf is the reference's scratch and is not used.  Everything the entry declines (other types, a newVal outside the depth's range, sizes over the
+// limit, UMat, no device) goes to the stock function, which finds the image untouched.  Not compiled here: the reference's headers are absent.
+inline void filterSpeckles(cv::InputOutputArray _img, double newVal, int maxSpeckleSize, double maxDiff, cv::InputOutputArray _buf = cv::noArray())
+{
+    if (_img.kind() == cv::_InputArray::MAT) {
+        cv::Mat img = _img.getMat();
+        const bool ints = newVal >= -2147483648.0 && newVal <= 2147483647.0 && maxDiff >= -2147483648.0 && maxDiff <= 2147483647.0;
+        if (ints && img.dims <= 2 && !img.empty() && (img.type() == CV_8UC1 || img.type() == CV_16SC1) &&
+            mi355cv_filterSpeckles(img.data, img.step, img.cols, img.rows, img.type() == CV_8UC1 ? MI355CV_8U : MI355CV_16S, (int)newVal, maxSpeckleSize, (int)maxDiff) == MI355CV_OK)
+            return;
+    }
+    cv::filterSpeckles(_img, newVal, maxSpeckleSize, maxDiff, _buf);
+}
 #endif
 
 // Batches across the GPUs of one node from C++: forEachShard({0,1,...,7}, nframes, [&](int slot, int device, int first, int count) { ... return 0; })

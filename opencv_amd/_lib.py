@@ -78,6 +78,9 @@ def _load():
         "mi355cv_stereoBMBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p]),
         "mi355cv_stereoPrefilterXSobel": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int]),
         "mi355cv_stereoBMSetKernel": (c_int, [c_int]),
+        "mi355cv_filterSpeckles": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
+        "mi355cv_filterSpecklesBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
+        "mi355cv_filterSpecklesSetKernel": (c_int, [c_int]),
         "mi355cv_remap": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int,
                                   c_int, c_int, ctypes.c_void_p]),
         "mi355cv_convertMaps": (c_int, [ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz,

@@ -1,6 +1,7 @@
 """Host-side mirror of cv::StereoBM (modules/calib3d; the reference has no HAL hook for it): the parameters with the reference's getters and setters, compute on one
 rectified pair and computeBatch on N x H x W stacks.  The maps are made by mi355cv_stereoBM / mi355cv_stereoBMBatch (opencv_amd/csrc/stereobm.hip); torch device
-tensors stay in HBM, numpy arrays are staged, the result has the kind of the input.  The definition served is the project's restatement."""
+tensors stay in HBM, numpy arrays are staged, the result has the kind of the input.  The definition served is the project's restatement.
+cv::filterSpeckles (mi355cv_filterSpeckles / mi355cv_filterSpecklesBatch, opencv_amd/csrc/speckle.hip) works in place on the map where it lives."""
 import ctypes
 
 import numpy as np
@@ -8,7 +9,7 @@ import numpy as np
 from . import _lib
 from .core import Img, bind_stream, torch, CV_8U, CV_16S, CV_32F
 
-__all__ = ["StereoBM", "StereoBM_create", "stereoPrefilterXSobel", "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "StereoBM_PREFILTER_NORMALIZED_RESPONSE",
+__all__ = ["StereoBM", "StereoBM_create", "stereoPrefilterXSobel", "filterSpeckles", "filterSpecklesBatch", "PREFILTER_NORMALIZED_RESPONSE", "PREFILTER_XSOBEL", "StereoBM_PREFILTER_NORMALIZED_RESPONSE",
            "StereoBM_PREFILTER_XSOBEL", "StereoBM_DISP_SHIFT", "StereoBM_DISP_SCALE"]
 
 L = _lib.lib
@@ -137,3 +138,46 @@ def stereoPrefilterXSobel(src, cap, dst=None):
     bind_stream(s, d)
     _lib.check(L.mi355cv_stereoPrefilterXSobel(_vp(s.ptr), s.step, _vp(d.ptr), d.step, s.w, s.h, int(cap)), "stereoPrefilterXSobel")
     return dst
+
+
+def _speckle_args(entry, newVal, maxSpeckleSize, maxDiff):
+    # the reference takes newVal and maxDiff as double and truncates them to int
+    try:
+        return int(newVal), int(maxSpeckleSize), int(maxDiff)
+    except (TypeError, ValueError, OverflowError):
+        raise ValueError("%s: newVal, maxSpeckleSize and maxDiff must be finite numbers" % entry)
+
+
+def _clamp_int(v):
+    return max(-2 ** 31, min(2 ** 31 - 1, v))
+
+
+def filterSpeckles(img, newVal, maxSpeckleSize, maxDiff, buf=None):
+    """cv::filterSpeckles on one CV_8UC1 or CV_16SC1 map, IN PLACE: every connected component (4-neighbours with |a - b| <= maxDiff among the pixels != newVal) of at
+    most maxSpeckleSize pixels becomes newVal.  Returns img: a device tensor stays in HBM, a numpy array is staged and written back into the same array.  buf is the
+    reference's scratch argument: accepted and ignored."""
+    entry = "filterSpeckles"
+    if getattr(img, "ndim", 0) != 2:
+        raise ValueError("filterSpeckles: img must be H x W")
+    a = Img(img)
+    newVal, maxSpeckleSize, maxDiff = _speckle_args(entry, newVal, maxSpeckleSize, maxDiff)
+    if a.cn != 1 or a.depth not in (CV_8U, CV_16S):
+        _decline(entry, "the image is neither CV_8UC1 nor CV_16SC1")
+    bind_stream(a)
+    _lib.check(L.mi355cv_filterSpeckles(_vp(a.ptr), a.step, a.w, a.h, a.depth, _clamp_int(newVal), _clamp_int(maxSpeckleSize), _clamp_int(maxDiff)), entry)
+    return img
+
+
+def filterSpecklesBatch(imgs, newVal, maxSpeckleSize, maxDiff, buf=None):
+    """N maps stacked as N x H x W, each filtered in place bit for bit as the single call does, in one sequence of launches; the frame stride may exceed the frame"""
+    entry = "filterSpecklesBatch"
+    if getattr(imgs, "ndim", 0) != 3 or int(imgs.shape[0]) < 1:
+        raise ValueError("filterSpecklesBatch: a stack N x H x W")
+    a = Img(imgs[0])
+    newVal, maxSpeckleSize, maxDiff = _speckle_args(entry, newVal, maxSpeckleSize, maxDiff)
+    if a.cn != 1 or a.depth not in (CV_8U, CV_16S):
+        _decline(entry, "the image is neither CV_8UC1 nor CV_16SC1")
+    bind_stream(a)
+    _lib.check(L.mi355cv_filterSpecklesBatch(_vp(a.ptr), a.step, _frame_stride(imgs), int(imgs.shape[0]), a.w, a.h, a.depth, _clamp_int(newVal), _clamp_int(maxSpeckleSize),
+                                             _clamp_int(maxDiff)), entry)
+    return imgs

@@ -61,6 +61,9 @@ constexpr int STEREOBM_CHUNK = 16;             // ... disparities per lane of th
 constexpr int STEREOBM_TILE_COLS = 64;         // ... window columns per workgroup of the fast kernel: 64 - (blockSize - 1) pixels of a row
 constexpr int STEREOBM_STRIP_ROWS = 32;        // ... rows a workgroup of the fast kernel walks down
 constexpr int STEREOBM_GENERIC_TILE_COLS = 32; // ... pixels of a row per workgroup of the generic kernel
+constexpr int SPECKLE_MAX_DIM = 16384;         // mi355cv_filterSpeckles*: width and height (the neighbours' bound; a pixel index and a component size stay below 2^28; speckle_math.h)
+constexpr int SPECKLE_TILE_COLS = 256;         // ... geometry, reported for the tests' shapes: columns of a tile of the fast kernel (64 lanes x 4 pixels)
+constexpr int SPECKLE_TILE_ROWS = 16;          // ... and its rows, merged in LDS
 }
 
 struct ThreadCtx;

@@ -580,7 +580,8 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"bfmatch_max_radius_row", BFMATCH_MAX_RADIUS_ROW}, {"bfmatch_tile_rows", BFMATCH_TILE_ROWS}, {"bfmatch_split_rows", BFMATCH_SPLIT_ROWS},
         {"stereobm_max_dim", STEREOBM_MAX_DIM}, {"stereobm_max_disparities", STEREOBM_MAX_DISPARITIES}, {"stereobm_max_block", STEREOBM_MAX_BLOCK},
         {"stereobm_roll_max_block", STEREOBM_ROLL_MAX_BLOCK}, {"stereobm_chunk", STEREOBM_CHUNK}, {"stereobm_tile_cols", STEREOBM_TILE_COLS},
-        {"stereobm_strip_rows", STEREOBM_STRIP_ROWS}, {"stereobm_generic_tile_cols", STEREOBM_GENERIC_TILE_COLS}};
+        {"stereobm_strip_rows", STEREOBM_STRIP_ROWS}, {"stereobm_generic_tile_cols", STEREOBM_GENERIC_TILE_COLS},
+        {"speckle_max_dim", SPECKLE_MAX_DIM}, {"speckle_tile_cols", SPECKLE_TILE_COLS}, {"speckle_tile_rows", SPECKLE_TILE_ROWS}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
