@@ -13,15 +13,8 @@
 #include <string.h>
 #if !defined(__HIPCC__)
 #include <math.h>
-#ifndef __host__
-#define __host__
 #endif
-#ifndef __device__
-#define __device__
-#endif
-#endif
-
-#define BFMATCH_HD __host__ __device__ inline
+#include "hd.h"
 
 namespace bfm {
 
@@ -39,21 +32,14 @@ constexpr int MAX_SPLITS = 256;           // ... and the most parts; beyond it a
 typedef unsigned long long Key;
 constexpr Key NO_KEY = ~0ull;
 
-BFMATCH_HD uint32_t popc32(uint32_t x)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return (uint32_t)__popc(x);
-#else
-    return (uint32_t)__builtin_popcount(x);
-#endif
-}
+using mi355::popc32;
 // NORM_HAMMING2 on a word of xor-ed bytes: one bit per non-zero 2-bit group
-BFMATCH_HD uint32_t pairs32(uint32_t x) { return (x | (x >> 1)) & 0x55555555u; }
+MI355_HD_PLAIN uint32_t pairs32(uint32_t x) { return (x | (x >> 1)) & 0x55555555u; }
 
-template <bool H2> BFMATCH_HD uint32_t hammingWord(uint32_t q, uint32_t t) { return popc32(H2 ? pairs32(q ^ t) : (q ^ t)); }
+template <bool H2> MI355_HD_PLAIN uint32_t hammingWord(uint32_t q, uint32_t t) { return popc32(H2 ? pairs32(q ^ t) : (q ^ t)); }
 
 // rows of n bytes at any address
-BFMATCH_HD uint32_t hammingBytes(const uint8_t* q, const uint8_t* t, int n, bool h2)
+MI355_HD_PLAIN uint32_t hammingBytes(const uint8_t* q, const uint8_t* t, int n, bool h2)
 {
     uint32_t s = 0;
     for (int i = 0; i < n; i++) { const uint32_t x = (uint32_t)(q[i] ^ t[i]); s += popc32(h2 ? pairs32(x) : x); }
@@ -62,10 +48,10 @@ BFMATCH_HD uint32_t hammingBytes(const uint8_t* q, const uint8_t* t, int n, bool
 
 // the correctly rounded float32 square root: the double root is correctly rounded and 53 >= 2 * 24 + 2 bits make the second rounding harmless.  (The device's
 // __fsqrt_rn was measured one ulp off on gfx950: sqrt(6) came back as 0x401CC470, the nearest float is 0x401CC471.)
-BFMATCH_HD float sqrtRn(float v) { return (float)sqrt((double)v); }
+MI355_HD_PLAIN float sqrtRn(float v) { return (float)sqrt((double)v); }
 
 // NORM_L1 / NORM_L2SQR / NORM_L2 of two rows of n floats
-BFMATCH_HD float floatDistance(const float* q, const float* t, int n, int norm)
+MI355_HD_PLAIN float floatDistance(const float* q, const float* t, int n, int norm)
 {
     float s = 0.f;
     if (norm == NORM_L1) for (int i = 0; i < n; i++) { const float x = q[i] - t[i]; s = s + (x < 0.f ? -x : x); }
@@ -73,25 +59,25 @@ BFMATCH_HD float floatDistance(const float* q, const float* t, int n, int norm)
     return norm == NORM_L2 ? sqrtRn(s) : s;
 }
 
-BFMATCH_HD uint32_t floatBits(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
-BFMATCH_HD float bitsFloat(uint32_t u) { float v; memcpy(&v, &u, 4); return v; }
+MI355_HD_PLAIN uint32_t floatBits(float v) { uint32_t u; memcpy(&u, &v, 4); return u; }
+MI355_HD_PLAIN float bitsFloat(uint32_t u) { float v; memcpy(&v, &u, 4); return v; }
 
-BFMATCH_HD Key keyOf(uint32_t dist, uint32_t row) { return ((Key)dist << 32) | row; }
+MI355_HD_PLAIN Key keyOf(uint32_t dist, uint32_t row) { return ((Key)dist << 32) | row; }
 // a float distance: NaN has no key.  -x of a NaN, |x| and x * x never give -0, so the sign bit is clear and the pattern is monotone
-BFMATCH_HD Key keyOfFloat(float d, uint32_t row) { return d != d ? NO_KEY : keyOf(floatBits(d), row); }
-BFMATCH_HD uint32_t keyRow(Key k) { return (uint32_t)k; }
-BFMATCH_HD float keyDistance(Key k, bool isFloat) { const uint32_t h = (uint32_t)(k >> 32); return isFloat ? bitsFloat(h) : (float)h; }
+MI355_HD_PLAIN Key keyOfFloat(float d, uint32_t row) { return d != d ? NO_KEY : keyOf(floatBits(d), row); }
+MI355_HD_PLAIN uint32_t keyRow(Key k) { return (uint32_t)k; }
+MI355_HD_PLAIN float keyDistance(Key k, bool isFloat) { const uint32_t h = (uint32_t)(k >> 32); return isFloat ? bitsFloat(h) : (float)h; }
 
 template <int K> struct KList { Key v[K]; };
 
-template <int K> BFMATCH_HD void clear(KList<K>& l)
+template <int K> MI355_HD_PLAIN void clear(KList<K>& l)
 {
 #pragma unroll
     for (int i = 0; i < K; i++) l.v[i] = NO_KEY;
 }
 
 // keeps the K smallest keys in ascending order; keys are unique, NO_KEY is never inserted (it is not below the last element)
-template <int K> BFMATCH_HD void insert(KList<K>& l, Key key)
+template <int K> MI355_HD_PLAIN void insert(KList<K>& l, Key key)
 {
     if (!(key < l.v[K - 1])) return;
     l.v[K - 1] = key;

@@ -280,7 +280,6 @@ __global__ __launch_bounds__(256) void k_backproject(const uchar* __restrict__ s
 }
 
 // ---- host side
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
 const char* depthName(int depth) { return depth == 0 ? "8u" : depth == 2 ? "16u" : "32f"; }
 constexpr int LDS_SHARED_BLOCKS = 40 * 1024;     // up to here four workgroups share a CU's 160 KiB: private copies are added while they fit
 constexpr int LDS_MAX_COPIES = 8;                // private copies of k_calchist_lds, chosen by lane (DESIGN 6.13 has the measurements behind the number)

@@ -12,12 +12,7 @@
 #pragma once
 #include <math.h>
 #include <stdint.h>
-
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#define CALCHIST_HD __host__ __device__ inline
+#include "hd.h"
 
 namespace calchist {
 
@@ -29,7 +24,7 @@ constexpr int MAX_FRAMES = 65535;
 constexpr int32_t SKIP = -(1 << 28);           // 3 * SKIP > INT32_MIN and SKIP + 2 * MAX_BINS < 0
 
 // v * a + b, two roundings
-CALCHIST_HD double mulThenAdd(double v, double a, double b)
+MI355_HD_PLAIN double mulThenAdd(double v, double a, double b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __dadd_rn(__dmul_rn(v, a), b);
@@ -40,7 +35,7 @@ CALCHIST_HD double mulThenAdd(double v, double a, double b)
 }
 
 struct Uniform { double a, b; };
-CALCHIST_HD Uniform uniformCoef(int n, float lo, float hi)
+MI355_HD_PLAIN Uniform uniformCoef(int n, float lo, float hi)
 {
     Uniform u;
     u.a = (double)n / ((double)hi - (double)lo);
@@ -49,7 +44,7 @@ CALCHIST_HD Uniform uniformCoef(int n, float lo, float hi)
 }
 
 // the bin of an 8- or 16-bit value under uniform ranges, -1: not counted
-CALCHIST_HD int binUniformInt(int v, int n, float lo, float hi, Uniform u)
+MI355_HD_PLAIN int binUniformInt(int v, int n, float lo, float hi, Uniform u)
 {
     if (!((double)v >= (double)lo && (double)v < (double)hi)) return -1;
     const double f = floor(mulThenAdd((double)v, u.a, u.b));
@@ -57,7 +52,7 @@ CALCHIST_HD int binUniformInt(int v, int n, float lo, float hi, Uniform u)
 }
 
 // the bin of a CV_32F value under uniform ranges, -1: not counted
-CALCHIST_HD int binUniformF32(float v, int n, Uniform u)
+MI355_HD_PLAIN int binUniformF32(float v, int n, Uniform u)
 {
     const double t = mulThenAdd((double)v, u.a, u.b);
     if (!(t >= 0.0 && t < (double)n)) return -1;
@@ -65,7 +60,7 @@ CALCHIST_HD int binUniformF32(float v, int n, Uniform u)
 }
 
 // the k with r[k] <= v < r[k + 1] among n + 1 ascending boundaries, -1 outside [r[0], r[n]); v is exact as a float (8- and 16-bit values)
-CALCHIST_HD int binNonUniform(float v, const float* r, int n)
+MI355_HD_PLAIN int binNonUniform(float v, const float* r, int n)
 {
     if (!(v >= r[0] && v < r[n])) return -1;
     int lo = 0, hi = n;                        // r[lo] <= v < r[hi]
@@ -87,23 +82,23 @@ inline void buildTable(int levels, int n, bool uniform, const float* ranges, int
 }
 
 // cvRound(p) saturated to [0, top] (top = 255 / 65535); NaN -> 0
-CALCHIST_HD uint32_t roundSat(double p, uint32_t top)
+MI355_HD_PLAIN uint32_t roundSat(double p, uint32_t top)
 {
     const double r = rint(p);
     return !(r > 0.0) ? 0u : r >= (double)top ? top : (uint32_t)r;
 }
 
 // accumulate: a CV_32F cell as the starting count, cvRound saturated to int32; NaN -> 0
-CALCHIST_HD int32_t countOfFloat(float f)
+MI355_HD_PLAIN int32_t countOfFloat(float f)
 {
     const double r = rint((double)f);
     return r != r ? 0 : r <= -2147483648.0 ? INT32_MIN : r >= 2147483647.0 ? INT32_MAX : (int32_t)r;
 }
 // ... and a count as a CV_32F cell: round to nearest even
-CALCHIST_HD float floatOfCount(int32_t c) { return (float)c; }
+MI355_HD_PLAIN float floatOfCount(int32_t c) { return (float)c; }
 
 // one back-projected value: hist[bin] * scale in double, then the destination's rounding
-CALCHIST_HD uint32_t backProjectInt(float h, double scale, uint32_t top) { return roundSat((double)h * scale, top); }
-CALCHIST_HD float backProjectF32(float h, double scale) { return (float)((double)h * scale); }
+MI355_HD_PLAIN uint32_t backProjectInt(float h, double scale, uint32_t top) { return roundSat((double)h * scale, top); }
+MI355_HD_PLAIN float backProjectF32(float h, double scale) { return (float)((double)h * scale); }
 
 } // namespace calchist

@@ -1,6 +1,7 @@
 // ccl.hip -- cv::connectedComponents / cv::connectedComponentsWithStats (imgproc/src/connectedcomponents.cpp; the reference has no HAL hook for them) on
-// CV_8UC1, 4- and 8-connected, labels CV_32S or CV_16U.  Every line of arithmetic is in ccl_math.h.  A union-find over pixels whose root is the SMALLEST linear
-// pixel index of the set (parents only ever decrease), so the root of a component is its first raster pixel whatever order the merges land in.
+// CV_8UC1, 4- and 8-connected, labels CV_32S or CV_16U.  Every line of arithmetic is in ccl_math.h, and the find / unite loops are unionfind.h's (over its LDS
+// and HBM memory policies); tests/hostemu/ccl_emu.cpp compiles both for the host.  A union-find over pixels whose root is the SMALLEST linear pixel index of the set
+// (parents only ever decrease), so the root of a component is its first raster pixel whatever order the merges land in.
 //
 //   k_ccl_strip      a wave per tile of 256 columns x 16 rows.  A lane loads one dword (4 pixels), four 64-bit ballots become the four row words of the tile;
 //                    runs and the links to the row above are bit scans of those words (no per-pixel work); the runs of the tile are merged in LDS (atomicMin
@@ -19,6 +20,7 @@
 // Everything else is ordered by kernel boundaries; there is no grid-wide wait.
 #include "rt.h"
 #include "ccl_math.h"
+#include "unionfind.h"
 #include <algorithm>
 
 using namespace mi355;
@@ -29,6 +31,8 @@ using ccl::BG;
 using ccl::STRIP_H;
 using ccl::TILE_W;
 using ccl::WORDS;
+using uf::GlobalMem;
+using uf::LdsMem;
 
 // the scratch of a group of frames: parents, flag bitmap, the two levels of its scan, the block-key table, the totals
 struct Scr {
@@ -36,41 +40,6 @@ struct Scr {
     size_t pf, bf, wf, cf, kf;             // frame strides in elements
     uint32_t nW, nchunk, npos;
 };
-
-__device__ __forceinline__ uint32_t ldAgent(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-
-// x is a foreground pixel: parents are smaller than their children, a root is its own parent
-__device__ __forceinline__ uint32_t findG(const uint32_t* P, uint32_t x)
-{
-    for (;;) { const uint32_t p = ldAgent(P + x); if (p >= x) return x; x = p; }
-}
-__device__ __forceinline__ void uniteG(uint32_t* P, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = findG(P, a); b = findG(P, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(P + a, b);              // a was a root when read: old == a unless another union got there first
-        if (old == a) return;
-        a = old;                                                // the set a pointed to still has to meet b
-    }
-}
-
-__device__ __forceinline__ uint32_t findL(volatile uint32_t* par, uint32_t x)
-{
-    for (;;) { const uint32_t p = par[x]; if (p >= x) return x; x = p; }
-}
-__device__ __forceinline__ void uniteL(uint32_t* par, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = findL(par, a); b = findL(par, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = atomicMin(par + a, b);
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // bytes x .. x + 3 of a row w wide as a dword, 0 for the ones past its end
 __device__ __forceinline__ uint32_t loadPix4(const uchar* row, int x, int w)
@@ -100,6 +69,7 @@ __global__ __launch_bounds__(64) void k_ccl_strip(const uchar* __restrict__ src,
             if ((W[j] >> lane) & 1) { const int c = 64 * j + lane; if (ccl::tileRunStart(W, j, lane) == c) par[r * TILE_W + c] = r * TILE_W + c; }
     }
     __syncthreads();
+    LdsMem m{par};
     for (int r = 1; r < rows; r++) {                                         // the pairs (run, run of the row above) that touch
         const uint64_t* W = wd[r]; const uint64_t* U = wd[r - 1];
         for (int j = 0; j < WORDS; j++) {
@@ -108,9 +78,9 @@ __global__ __launch_bounds__(64) void k_ccl_strip(const uchar* __restrict__ src,
             const uint64_t left = conn8 ? ccl::linkLeft(W[j], U[j], Wl, Ul) : 0, right = conn8 ? ccl::linkRight(W[j], U[j], Wr, Ur) : 0;
             if (!(((direct | left | right) >> lane) & 1)) continue;
             const uint32_t a = r * TILE_W + ccl::tileRunStart(W, j, lane);
-            if ((direct >> lane) & 1) uniteL(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, j, lane));
-            if ((left >> lane) & 1) { const int c = 64 * j + lane - 1; uniteL(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
-            if ((right >> lane) & 1) { const int c = 64 * j + lane + 1; uniteL(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
+            if ((direct >> lane) & 1) uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, j, lane));
+            if ((left >> lane) & 1) { const int c = 64 * j + lane - 1; uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
+            if ((right >> lane) & 1) { const int c = 64 * j + lane + 1; uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
         }
     }
     __syncthreads();
@@ -121,7 +91,7 @@ __global__ __launch_bounds__(64) void k_ccl_strip(const uchar* __restrict__ src,
             if (x >= w) continue;
             uint32_t p = BG;
             if ((W[j] >> lane) & 1) {
-                const uint32_t root = findL(par, r * TILE_W + ccl::tileRunStart(W, j, lane));
+                const uint32_t root = uf::find(m, r * TILE_W + ccl::tileRunStart(W, j, lane));
                 p = (uint32_t)(y0 + (int)(root / TILE_W)) * (uint32_t)w + (uint32_t)(x0 + (int)(root % TILE_W));
             }
             P[(size_t)(y0 + r) * w + x] = p;
@@ -134,13 +104,13 @@ __global__ __launch_bounds__(64) void k_ccl_vseam(uint32_t* __restrict__ P, size
 {
     const int y = blockIdx.x * 64 + threadIdx.x, x = (blockIdx.y + 1) * TILE_W;
     if (y >= h) return;
-    P += (size_t)blockIdx.z * pframe;
+    GlobalMem m{P + (size_t)blockIdx.z * pframe};
     const uint32_t b = (uint32_t)y * w + x, a = b - 1;
-    const bool fa = ldAgent(P + a) != BG, fb = ldAgent(P + b) != BG;
-    if (fa && fb) uniteG(P, a, b);
+    const bool fa = m.load(a) != BG, fb = m.load(b) != BG;
+    if (fa && fb) uf::unite(m, a, b);
     if (conn8 && y > 0) {
-        if (fa && ldAgent(P + b - w) != BG) uniteG(P, a, b - w);
-        if (fb && ldAgent(P + a - w) != BG) uniteG(P, b, a - w);
+        if (fa && m.at(m.P + b - w) != BG) uf::unite(m, a, b - w);
+        if (fb && m.at(m.P + a - w) != BG) uf::unite(m, b, a - w);
     }
 }
 
@@ -148,16 +118,16 @@ __global__ __launch_bounds__(64) void k_ccl_vseam(uint32_t* __restrict__ P, size
 __global__ __launch_bounds__(64) void k_ccl_hseam(uint32_t* __restrict__ P, size_t pframe, int w, int conn8)
 {
     const int lane = threadIdx.x, x0 = blockIdx.x * TILE_W, y = (blockIdx.y + 1) * STRIP_H;
-    P += (size_t)blockIdx.z * pframe;
-    const uint32_t* cur = P + (size_t)y * w; const uint32_t* up = cur - w;
+    GlobalMem m{P + (size_t)blockIdx.z * pframe};
+    const uint32_t* cur = m.P + (size_t)y * w; const uint32_t* up = cur - w;
     uint64_t W[WORDS + 2], U[WORDS + 2];                                     // [0] and [WORDS + 1]: the carries
-    W[0] = x0 > 0 && ldAgent(cur + x0 - 1) != BG ? ~uint64_t(0) : 0; U[0] = x0 > 0 && ldAgent(up + x0 - 1) != BG ? ~uint64_t(0) : 0;
-    W[WORDS + 1] = x0 + TILE_W < w && ldAgent(cur + x0 + TILE_W) != BG; U[WORDS + 1] = x0 + TILE_W < w && ldAgent(up + x0 + TILE_W) != BG;
+    W[0] = x0 > 0 && m.at(cur + x0 - 1) != BG ? ~uint64_t(0) : 0; U[0] = x0 > 0 && m.at(up + x0 - 1) != BG ? ~uint64_t(0) : 0;
+    W[WORDS + 1] = x0 + TILE_W < w && m.at(cur + x0 + TILE_W) != BG; U[WORDS + 1] = x0 + TILE_W < w && m.at(up + x0 + TILE_W) != BG;
 #pragma unroll
     for (int j = 0; j < WORDS; j++) {
         const int x = x0 + 64 * j + lane;
-        W[j + 1] = __ballot(x < w && ldAgent(cur + x) != BG);
-        U[j + 1] = __ballot(x < w && ldAgent(up + x) != BG);
+        W[j + 1] = __ballot(x < w && m.at(cur + x) != BG);
+        U[j + 1] = __ballot(x < w && m.at(up + x) != BG);
     }
 #pragma unroll
     for (int j = 1; j <= WORDS; j++) {
@@ -165,9 +135,9 @@ __global__ __launch_bounds__(64) void k_ccl_hseam(uint32_t* __restrict__ P, size
         const uint64_t direct = ccl::linkDirect(W[j], U[j], Wl, Ul);
         const uint64_t left = conn8 ? ccl::linkLeft(W[j], U[j], Wl, Ul) : 0, right = conn8 ? ccl::linkRight(W[j], U[j], Wr, Ur) : 0;
         const uint32_t a = (uint32_t)y * w + x0 + 64 * (j - 1) + lane;
-        if ((direct >> lane) & 1) uniteG(P, a, a - w);
-        if ((left >> lane) & 1) uniteG(P, a, a - w - 1);
-        if ((right >> lane) & 1) uniteG(P, a, a - w + 1);
+        if ((direct >> lane) & 1) uf::unite(m, a, a - w);
+        if ((left >> lane) & 1) uf::unite(m, a, a - w - 1);
+        if ((right >> lane) & 1) uf::unite(m, a, a - w + 1);
     }
 }
 
@@ -177,17 +147,17 @@ __global__ __launch_bounds__(256) void k_ccl_flatten(Scr s, int w, int h)
 {
     const int lane = threadIdx.x & 63, x0 = blockIdx.x * TILE_W, y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (y >= h) return;
-    uint32_t* P = s.P + (size_t)blockIdx.z * s.pf;
+    GlobalMem m{s.P + (size_t)blockIdx.z * s.pf};
 #pragma unroll
     for (int j = 0; j < WORDS; j++) {
         const int x = x0 + 64 * j + lane;
         const uint32_t g = (uint32_t)y * w + x;
-        const uint32_t p = x < w ? ldAgent(P + g) : BG;
+        const uint32_t p = x < w ? m.load(g) : BG;
         const bool fg = p != BG;
         uint32_t r = BG;
         if (fg) {
-            r = findG(P, p);
-            if (r != p) __hip_atomic_store(P + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+            r = uf::find(m, p);
+            if (r != p) __hip_atomic_store(m.P + g, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
         }
         if (ORDER == ccl::ORDER_PIXEL) {
             const uint64_t m = __ballot(fg && r == g);
@@ -331,7 +301,6 @@ __global__ __launch_bounds__(256) void k_ccl_stats_finish(const ccl::Acc* __rest
 
 // ---- host side
 struct Geom { uint32_t npos, nW, nchunk, nblocks; size_t pBytes, bBytes, wBytes, cBytes, kBytes, bytes; };
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
 Geom geometry(int w, int h, int order)
 {
     Geom q;

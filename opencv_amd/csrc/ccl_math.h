@@ -10,24 +10,21 @@
 //             widened by one bit each way with the carry bits of the neighbouring words (link8) -- cut into the direct pairs plus the purely diagonal ones
 //             (linkLeft / linkRight), which names every touching pair at least once and few of them twice.
 //   roots     the union-find keeps the SMALLEST linear pixel index as the root and parents only ever decrease, so the root of a component is its first raster
-//             pixel whatever the interleaving of the unions.
+//             pixel whatever the interleaving of the unions.  Its find / unite loops are not here: they are unionfind.h's, which the kernels and the host build
+//             both include.
 //   order     components are numbered by a key of the component: its first pixel (ORDER_PIXEL), or its first 2 x 2 block, blockKey (ORDER_BLOCK).  The keys are
 //             flags in a bitmap over key space; a label is 1 + the number of flags below the component's key (rank).
 //   stats     per row, runs of equal label; a run [x, x + len) adds len to the area, runSumX to the sum of x and y * len to the sum of y.
 // Bounds: width and height <= MAX_DIM = 16384, so a pixel index and an area fit 2^28 and a coordinate sum stays below 2^42 < 2^53: the centroid's double
 // division sees two exactly represented integers.
 #pragma once
-#include <stdint.h>
-
-#ifndef MI355_HD
-#  if defined(__HIPCC__)
-#    define MI355_HD __host__ __device__ __forceinline__
-#  else
-#    define MI355_HD inline
-#  endif
-#endif
+#include "hd.h"
 
 namespace ccl {
+
+using mi355::clz64;
+using mi355::ctz64;
+using mi355::popc64;
 
 enum { ORDER_PIXEL = 0, ORDER_BLOCK = 1 };
 constexpr int TILE_W = 256;                       // columns of a tile = 64 lanes x 4 pixels
@@ -44,31 +41,6 @@ MI355_HD int orderOf(int connectivity, int ccltype)
     if (ccltype < -1 || ccltype > 5) return -1;
     if (connectivity == 4 || ccltype == 0 || ccltype == 3) return ORDER_PIXEL;
     return ORDER_BLOCK;
-}
-
-MI355_HD int clz64(uint64_t v)                    // v != 0
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __clzll((long long)v);
-#else
-    return __builtin_clzll(v);
-#endif
-}
-MI355_HD int ctz64(uint64_t v)                    // v != 0
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __ffsll((unsigned long long)v) - 1;
-#else
-    return __builtin_ctzll(v);
-#endif
-}
-MI355_HD int popc64(uint64_t v)
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __popcll(v);
-#else
-    return __builtin_popcountll(v);
-#endif
 }
 
 MI355_HD uint64_t below(int lane) { return (uint64_t(1) << lane) - 1; }             // the bits under `lane`, 0 <= lane < 64

@@ -22,13 +22,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef MI355_HD
-#  if defined(__HIPCC__)
-#    define MI355_HD __host__ __device__ __forceinline__
-#  else
-#    define MI355_HD inline
-#  endif
-#endif
+#include "hd.h"
 
 namespace demosaic {
 

@@ -18,13 +18,7 @@
 #include <stdint.h>
 #include <math.h>
 
-#ifndef MI355_HD
-#  if defined(__HIPCC__)
-#    define MI355_HD __host__ __device__ __forceinline__
-#  else
-#    define MI355_HD inline
-#  endif
-#endif
+#include "hd.h"
 
 namespace disttransform {
 
@@ -35,22 +29,8 @@ constexpr uint32_t CAP = 32768;                   // g of a column without a sit
 constexpr float NO_SITE_32F = 31622776.0f;        // sqrtf(1e15f): every pixel of a frame without a site (CV_32F)
 constexpr int NO_SITE_8U = 255;
 
-MI355_HD int clz64(uint64_t v)                    // v != 0
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __clzll((long long)v);
-#else
-    return __builtin_clzll(v);
-#endif
-}
-MI355_HD int ctz64(uint64_t v)                    // v != 0
-{
-#if defined(__HIP_DEVICE_COMPILE__)
-    return __ffsll((unsigned long long)v) - 1;
-#else
-    return __builtin_ctzll(v);
-#endif
-}
+using mi355::clz64;
+using mi355::ctz64;
 
 // words[k * stride]: the site word of segment k of one column.  Distance from the FIRST row of segment s up to the nearest site above the segment, CAP if none
 MI355_HD uint32_t carryUp(const uint64_t* words, size_t stride, int s)

@@ -5,11 +5,7 @@
 #include <math.h>
 #include <stdint.h>
 
-#if defined(__HIPCC__)
-#define FB_HD __host__ __device__ __forceinline__
-#else
-#define FB_HD inline
-#endif
+#include "hd.h"
 
 namespace fb {
 
@@ -34,9 +30,9 @@ struct WinTaps {                         // the window of the flow update: 2 m +
     int m;
 };
 
-FB_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+MI355_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
 
-FB_HD int reflect101(int p, int len)
+MI355_HD int reflect101(int p, int len)
 {
     if ((unsigned)p < (unsigned)len) return p;
     if (len == 1) return 0;
@@ -48,7 +44,7 @@ FB_HD int reflect101(int p, int len)
 }
 
 // ---- bilinear resize: source coordinate (float)((d + 0.5) * scale - 0.5) with scale = src / dst in double, floor, zero fraction where it clamps
-FB_HD void resizeCoord(int d, double scale, int srcLen, int& i0, int& i1, float& f)
+MI355_HD void resizeCoord(int d, double scale, int srcLen, int& i0, int& i1, float& f)
 {
     const float c = (float)((d + 0.5) * scale - 0.5);
     const float fl = floorf(c);
@@ -59,11 +55,11 @@ FB_HD void resizeCoord(int d, double scale, int srcLen, int& i0, int& i1, float&
     i0 = s;
     i1 = s + 1 < srcLen ? s + 1 : srcLen - 1;
 }
-FB_HD float lerp(float a, float b, float f) { return a * (1.f - f) + b * f; }
+MI355_HD float lerp(float a, float b, float f) { return a * (1.f - f) + b * f; }
 
 // ---- polynomial expansion.  col(k): the source at row offset k (replicated rows); three sums in the order centre, k = 1 .. n
 template <typename Col>
-FB_HD void polyVertical(const PolyTaps& T, Col col, float (&v)[3])
+MI355_HD void polyVertical(const PolyTaps& T, Col col, float (&v)[3])
 {
     v[0] = col(0) * T.g[0]; v[1] = 0.f; v[2] = 0.f;
     for (int k = 1; k <= T.n; k++) {
@@ -76,7 +72,7 @@ FB_HD void polyVertical(const PolyTaps& T, Col col, float (&v)[3])
 }
 // row(k, c): vertical sum c at column offset k (replicated columns); the five channels: y-linear, x-linear, yy, xx, xy
 template <typename Row>
-FB_HD void polyHorizontal(const PolyTaps& T, Row row, float (&r)[5])
+MI355_HD void polyHorizontal(const PolyTaps& T, Row row, float (&r)[5])
 {
     const float g0 = T.g[0];
     float b1 = row(0, 0) * g0, b2 = 0.f, b3 = row(0, 1) * g0, b4 = 0.f, b5 = row(0, 2) * g0, b6 = 0.f;
@@ -98,17 +94,17 @@ FB_HD void polyHorizontal(const PolyTaps& T, Row row, float (&r)[5])
 }
 
 // ---- update matrices
-FB_HD float borderWeight1(int p, int len)
+MI355_HD float borderWeight1(int p, int len)
 {
     const float B[BORDER] = {0.14f, 0.14f, 0.4472f, 0.4472f, 0.4472f};
     const float a = p < BORDER ? B[p] : 1.f;
     const float b = p >= len - BORDER ? B[len - p - 1] : 1.f;
     return a * b;
 }
-FB_HD float borderWeight(int x, int y, int w, int h) { return borderWeight1(x, w) * borderWeight1(y, h); }
+MI355_HD float borderWeight(int x, int y, int w, int h) { return borderWeight1(x, w) * borderWeight1(y, h); }
 
 // r0: the five floats of R0 at (x, y); R1: the second expansion, `pitch1` floats per row; d: the flow at (x, y); M: five floats out
-FB_HD void updateMatrix(const float* r0, const float* R1, size_t pitch1, int x, int y, int w, int h, float dx, float dy, float (&M)[5])
+MI355_HD void updateMatrix(const float* r0, const float* R1, size_t pitch1, int x, int y, int w, int h, float dx, float dy, float (&M)[5])
 {
     const float fx = (float)x + dx, fy = (float)y + dy;
     const float x1f = floorf(fx), y1f = floorf(fy);
@@ -147,13 +143,13 @@ FB_HD void updateMatrix(const float* r0, const float* R1, size_t pitch1, int x, 
 
 // ---- update flow.  at(i): the i-th value under the window; taps in ascending order
 template <typename At>
-FB_HD float tapSum(const float* t, int n, At at)
+MI355_HD float tapSum(const float* t, int n, At at)
 {
     float s = t[0] * at(0);
     for (int i = 1; i < n; i++) s = s + t[i] * at(i);
     return s;
 }
-FB_HD void solveFlow(const float (&s)[5], float scale, float& fx, float& fy)
+MI355_HD void solveFlow(const float (&s)[5], float scale, float& fx, float& fy)
 {
     const float g11 = s[0] * scale, g12 = s[1] * scale, g22 = s[2] * scale, h1 = s[3] * scale, h2 = s[4] * scale;
     const float idet = 1.f / (g11 * g22 - g12 * g12 + 1e-3f);

@@ -124,8 +124,6 @@ __global__ __launch_bounds__(256) void k_hough_emit(const unsigned long long* __
 }
 
 // ---- host side
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-
 // the refusals that need no device; 0 when the arguments are served
 int houghArgs(const void* src, int w, int h, double rho, double theta, double srn, double stn, double minTheta, double maxTheta, int useEdgeval, Geom* g)
 {

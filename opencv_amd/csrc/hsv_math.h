@@ -5,13 +5,7 @@
 #pragma once
 #include <math.h>
 
-#ifndef MI355_HD
-#  if defined(__HIPCC__)
-#    define MI355_HD __host__ __device__ __forceinline__
-#  else
-#    define MI355_HD inline
-#  endif
-#endif
+#include "hd.h"
 
 MI355_HD void mi355_hsv2bgr_px(int h8, int s8, int v8, bool inBody, float hscale, int& bo, int& go, int& ro)
 {

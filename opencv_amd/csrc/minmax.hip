@@ -182,8 +182,6 @@ __global__ __launch_bounds__(256) void k_minmax_final(const typename Depth<D>::K
 }
 
 // ---- host side
-inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }
-
 const char* const DEPTH_NAME[7] = {"8u", "8s", "16u", "16s", "32s", "32f", "64f"};
 
 struct Launch {

@@ -15,12 +15,7 @@
 #pragma once
 #include <stdint.h>
 #include <string.h>
-
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#define MINMAX_HD __host__ __device__ inline
+#include "hd.h"
 
 namespace minmax {
 
@@ -28,58 +23,58 @@ constexpr int MAX_DIM = 16384;                 // width and height: a raster ind
 constexpr uint32_t NONE = 0xFFFFFFFFu;         // the index of "no candidate"
 constexpr int MAX_FRAMES = 65535;
 
-template <class K> MINMAX_HD K least(K a, K b) { return b < a ? b : a; }
-template <class K> MINMAX_HD K greatest(K a, K b) { return a < b ? b : a; }
+template <class K> MI355_HD_PLAIN K least(K a, K b) { return b < a ? b : a; }
+template <class K> MI355_HD_PLAIN K greatest(K a, K b) { return a < b ? b : a; }
 
 template <class K> struct Best { K key; uint32_t idx; };
 
-template <class K> MINMAX_HD Best<K> identity() { Best<K> b; b.key = (K)~(K)0; b.idx = NONE; return b; }
+template <class K> MI355_HD_PLAIN Best<K> identity() { Best<K> b; b.key = (K)~(K)0; b.idx = NONE; return b; }
 // a comes before b in the total order
-template <class K> MINMAX_HD bool before(const Best<K>& a, const Best<K>& b) { return a.key < b.key || (a.key == b.key && a.idx < b.idx); }
-template <class K> MINMAX_HD Best<K> combine(const Best<K>& a, const Best<K>& b) { return before(b, a) ? b : a; }
+template <class K> MI355_HD_PLAIN bool before(const Best<K>& a, const Best<K>& b) { return a.key < b.key || (a.key == b.key && a.idx < b.idx); }
+template <class K> MI355_HD_PLAIN Best<K> combine(const Best<K>& a, const Best<K>& b) { return before(b, a) ? b : a; }
 
 // Depth<d>: U the element as raw bits, K the key; valid(bits) -- a candidate value; key(bits); value(key) -- exactly (double)element
 template <int DEPTH> struct Depth;
 
 template <> struct Depth<0> {                  // CV_8U
     typedef uint8_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U) { return true; }
-    static MINMAX_HD K key(U v) { return v; }
-    static MINMAX_HD double value(K k) { return (double)k; }
+    static MI355_HD_PLAIN bool valid(U) { return true; }
+    static MI355_HD_PLAIN K key(U v) { return v; }
+    static MI355_HD_PLAIN double value(K k) { return (double)k; }
 };
 template <> struct Depth<1> {                  // CV_8S
     typedef uint8_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U) { return true; }
-    static MINMAX_HD K key(U v) { return (K)(v ^ 0x80u); }
-    static MINMAX_HD double value(K k) { return (double)((int32_t)k - 128); }
+    static MI355_HD_PLAIN bool valid(U) { return true; }
+    static MI355_HD_PLAIN K key(U v) { return (K)(v ^ 0x80u); }
+    static MI355_HD_PLAIN double value(K k) { return (double)((int32_t)k - 128); }
 };
 template <> struct Depth<2> {                  // CV_16U
     typedef uint16_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U) { return true; }
-    static MINMAX_HD K key(U v) { return v; }
-    static MINMAX_HD double value(K k) { return (double)k; }
+    static MI355_HD_PLAIN bool valid(U) { return true; }
+    static MI355_HD_PLAIN K key(U v) { return v; }
+    static MI355_HD_PLAIN double value(K k) { return (double)k; }
 };
 template <> struct Depth<3> {                  // CV_16S
     typedef uint16_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U) { return true; }
-    static MINMAX_HD K key(U v) { return (K)(v ^ 0x8000u); }
-    static MINMAX_HD double value(K k) { return (double)((int32_t)k - 32768); }
+    static MI355_HD_PLAIN bool valid(U) { return true; }
+    static MI355_HD_PLAIN K key(U v) { return (K)(v ^ 0x8000u); }
+    static MI355_HD_PLAIN double value(K k) { return (double)((int32_t)k - 32768); }
 };
 template <> struct Depth<4> {                  // CV_32S
     typedef uint32_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U) { return true; }
-    static MINMAX_HD K key(U v) { return v ^ 0x80000000u; }
-    static MINMAX_HD double value(K k) { return (double)(int32_t)(k ^ 0x80000000u); }
+    static MI355_HD_PLAIN bool valid(U) { return true; }
+    static MI355_HD_PLAIN K key(U v) { return v ^ 0x80000000u; }
+    static MI355_HD_PLAIN double value(K k) { return (double)(int32_t)(k ^ 0x80000000u); }
 };
 template <> struct Depth<5> {                  // CV_32F
     typedef uint32_t U; typedef uint32_t K;
-    static MINMAX_HD bool valid(U v) { return (v & 0x7FFFFFFFu) <= 0x7F800000u; }
-    static MINMAX_HD K key(U v)
+    static MI355_HD_PLAIN bool valid(U v) { return (v & 0x7FFFFFFFu) <= 0x7F800000u; }
+    static MI355_HD_PLAIN K key(U v)
     {
         if (v == 0x80000000u) v = 0;                                         // -0 == +0
         return (v & 0x80000000u) ? ~v : (v | 0x80000000u);
     }
-    static MINMAX_HD double value(K k)
+    static MI355_HD_PLAIN double value(K k)
     {
         const uint32_t v = (k & 0x80000000u) ? (k & 0x7FFFFFFFu) : ~k;
         float f;
@@ -89,13 +84,13 @@ template <> struct Depth<5> {                  // CV_32F
 };
 template <> struct Depth<6> {                  // CV_64F
     typedef uint64_t U; typedef uint64_t K;
-    static MINMAX_HD bool valid(U v) { return (v & 0x7FFFFFFFFFFFFFFFull) <= 0x7FF0000000000000ull; }
-    static MINMAX_HD K key(U v)
+    static MI355_HD_PLAIN bool valid(U v) { return (v & 0x7FFFFFFFFFFFFFFFull) <= 0x7FF0000000000000ull; }
+    static MI355_HD_PLAIN K key(U v)
     {
         if (v == 0x8000000000000000ull) v = 0;
         return (v & 0x8000000000000000ull) ? ~v : (v | 0x8000000000000000ull);
     }
-    static MINMAX_HD double value(K k)
+    static MI355_HD_PLAIN double value(K k)
     {
         const uint64_t v = (k & 0x8000000000000000ull) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k;
         double d;
@@ -106,7 +101,7 @@ template <> struct Depth<6> {                  // CV_64F
 
 // what a frame's two winning pairs become: vals = {min, max}, locs = {minX, minY, maxX, maxY}; an empty candidate set gives 0, 0 and (-1, -1) twice.
 // mx carries the COMPLEMENTED key.
-template <int DEPTH> MINMAX_HD void emit(const Best<typename Depth<DEPTH>::K>& mn, const Best<typename Depth<DEPTH>::K>& mx, int width, double* vals, int* locs)
+template <int DEPTH> MI355_HD_PLAIN void emit(const Best<typename Depth<DEPTH>::K>& mn, const Best<typename Depth<DEPTH>::K>& mx, int width, double* vals, int* locs)
 {
     typedef typename Depth<DEPTH>::K K;
     if (mn.idx == NONE || mx.idx == NONE) {                                  // both or neither: they range over the same set

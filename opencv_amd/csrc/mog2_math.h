@@ -7,12 +7,7 @@
 #pragma once
 #include <math.h>
 #include <float.h>
-
-#ifndef __host__
-#define __host__
-#define __device__
-#endif
-#define MOG2_HD __host__ __device__ inline
+#include "hd.h"
 
 namespace mog2 {
 
@@ -31,7 +26,7 @@ struct Pixel {
 };
 
 template <int CN>
-MOG2_HD void clear(Pixel<CN>& p)
+MI355_HD_PLAIN void clear(Pixel<CN>& p)
 {
 #pragma unroll
     for (int m = 0; m < MAX_MIXTURES; m++) {
@@ -44,7 +39,7 @@ MOG2_HD void clear(Pixel<CN>& p)
 
 // modes a and b change places (a, b compile-time constants at every call site)
 template <int CN>
-MOG2_HD void swapModes(Pixel<CN>& p, int a, int b)
+MI355_HD_PLAIN void swapModes(Pixel<CN>& p, int a, int b)
 {
     float t = p.w[a]; p.w[a] = p.w[b]; p.w[b] = t;
     t = p.var[a]; p.var[a] = p.var[b]; p.var[b] = t;
@@ -56,7 +51,7 @@ MOG2_HD void swapModes(Pixel<CN>& p, int a, int b)
 // The reference writes the updated weight to weight[mode - swaps] after the bubble; here the value is stored in slot `mode` BEFORE the bubble and travels with the
 // swaps (the comparisons of the bubble only look at slots below the travelling one), which needs no computed index.
 template <int CN>
-MOG2_HD bool update(Pixel<CN>& p, const float (&x)[CN], const Params& P, float alphaT)
+MI355_HD_PLAIN bool update(Pixel<CN>& p, const float (&x)[CN], const Params& P, float alphaT)
 {
     const float alpha1 = 1.f - alphaT, prune = -alphaT * P.CT;
     bool background = false, fits = false;
@@ -131,7 +126,7 @@ MOG2_HD bool update(Pixel<CN>& p, const float (&x)[CN], const Params& P, float a
 
 // detectShadowGMM on the updated model
 template <int CN>
-MOG2_HD bool shadow(const Pixel<CN>& p, const float (&x)[CN], const Params& P)
+MI355_HD_PLAIN bool shadow(const Pixel<CN>& p, const float (&x)[CN], const Params& P)
 {
     float t = 0.f;
     bool done = false, res = false;
@@ -159,7 +154,7 @@ MOG2_HD bool shadow(const Pixel<CN>& p, const float (&x)[CN], const Params& P)
 
 // the mask value of a pixel after update()
 template <int CN>
-MOG2_HD unsigned maskValue(bool background, const Pixel<CN>& p, const float (&x)[CN], const Params& P)
+MI355_HD_PLAIN unsigned maskValue(bool background, const Pixel<CN>& p, const float (&x)[CN], const Params& P)
 {
     if (background) return 0u;
     return (P.detectShadows && shadow(p, x, P)) ? (unsigned)P.shadowValue : 255u;
@@ -167,7 +162,7 @@ MOG2_HD unsigned maskValue(bool background, const Pixel<CN>& p, const float (&x)
 
 // getBackgroundImage_intern: the weighted mean of the modes up to the one that carries the sum of weights past TB
 template <int CN>
-MOG2_HD void backgroundMean(const Pixel<CN>& p, const Params& P, float (&out)[CN])
+MI355_HD_PLAIN void backgroundMean(const Pixel<CN>& p, const Params& P, float (&out)[CN])
 {
     float m[CN], t = 0.f;
 #pragma unroll
@@ -188,7 +183,7 @@ MOG2_HD void backgroundMean(const Pixel<CN>& p, const Params& P, float (&out)[CN
 }
 
 // CV_8U result: round to nearest even, saturate
-MOG2_HD unsigned roundSat8(float v)
+MI355_HD_PLAIN unsigned roundSat8(float v)
 {
     const float r = rintf(v);
     return r <= 0.f ? 0u : r >= 255.f ? 255u : (unsigned)r;

@@ -17,13 +17,7 @@
 #pragma once
 #include <stdint.h>
 
-#ifndef MI355_HD
-#  if defined(__HIPCC__)
-#    define MI355_HD __host__ __device__ __forceinline__
-#  else
-#    define MI355_HD inline
-#  endif
-#endif
+#include "hd.h"
 
 // (a << n) + b: pyrup.hip maps it to one v_lshl_add_u32 in device code (rt.h lshlAdd); the value is the same
 #ifndef PYRUP_LSHL_ADD

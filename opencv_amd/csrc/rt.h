@@ -178,6 +178,8 @@ int runHostBatchN(const char* entry, const HostBatchN& hb, const HostBatchNFn& r
 
 inline int depthBytes(int depth) { return depth <= 1 ? 1 : depth <= 3 ? 2 : depth <= 5 ? 4 : 8; }     // CV_8U .. CV_64F
 inline int divUp(int a, int b) { return (a + b - 1) / b; }
+inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }                                                  // b bytes rounded up to 256: the start of the next array in a scratch block, a staged row's pitch
+inline size_t span(size_t step, int rows, size_t rowBytes) { return (size_t)(rows - 1) * step + rowBytes; }          // bytes from the first byte of an image to one past its last
 
 #if defined(__HIPCC__)
 // Workgroups of a 1-D grid go to the 8 XCDs round-robin (id % 8), each XCD behind its own L2.  A kernel whose neighbouring workgroups write the two halves of

@@ -21,11 +21,7 @@
 #include <stddef.h>
 #include <math.h>
 
-#if defined(__HIPCC__)
-#define SL_HD __host__ __device__ __forceinline__
-#else
-#define SL_HD inline
-#endif
+#include "hd.h"
 
 namespace seplong {
 
@@ -44,13 +40,13 @@ struct Geom {
 
 template <int CN> struct StripOf { static constexpr int TP = CN == 1 ? 128 : CN == 2 ? 64 : CN == 3 ? 40 : 32; };
 
-SL_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
-SL_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
-SL_HD int imin(int a, int b) { return a < b ? a : b; }
-SL_HD int imax(int a, int b) { return a > b ? a : b; }
+MI355_HD uint32_t f2u(float f) { return __builtin_bit_cast(uint32_t, f); }
+MI355_HD float u2f(uint32_t u) { return __builtin_bit_cast(float, u); }
+MI355_HD int imin(int a, int b) { return a < b ? a : b; }
+MI355_HD int imax(int a, int b) { return a > b ? a : b; }
 
 // borderInterpolate (core/src/copy.cpp:748-793); -1 for BORDER_CONSTANT.  Border codes: 0 constant, 1 replicate, 2 reflect, 3 wrap, 4 reflect_101.
-SL_HD int border(int p, int len, int type)
+MI355_HD int border(int p, int len, int type)
 {
     if ((unsigned)p < (unsigned)len) return p;
     if (type == 1) return p < 0 ? 0 : len - 1;
@@ -68,7 +64,7 @@ SL_HD int border(int p, int len, int type)
     return -1;
 }
 
-SL_HD float ldSrcF(const unsigned char* row, int idx, int depth)
+MI355_HD float ldSrcF(const unsigned char* row, int idx, int depth)
 {
     switch (depth) {
     case SL_8U:  return (float)row[idx];
@@ -79,7 +75,7 @@ SL_HD float ldSrcF(const unsigned char* row, int idx, int depth)
 }
 
 // saturate_cast<DT>(float): cvRound (round-half-even) then clamp (core/saturate.hpp:103-142)
-SL_HD void stDstF(unsigned char* row, int idx, int depth, float s)
+MI355_HD void stDstF(unsigned char* row, int idx, int depth, float s)
 {
     switch (depth) {
     case SL_8U:  { float r = rintf(s); r = fminf(fmaxf(r, 0.f), 255.f); row[idx] = (unsigned char)(int)r; break; }
@@ -90,7 +86,7 @@ SL_HD void stDstF(unsigned char* row, int idx, int depth, float s)
 }
 
 // integer multiply-add on the values of each mode: Q8.8 operands fit 24 bits (full-rate v_mad_u32_u24), the integer kernels of cv::sepFilter2D need all 32
-template <int MODE> SL_HD uint32_t imad(uint32_t k, uint32_t v, uint32_t acc)
+template <int MODE> MI355_HD uint32_t imad(uint32_t k, uint32_t v, uint32_t acc)
 {
     if constexpr (MODE == 4) { (void)k; return v < acc ? v : acc; }               // erode: the "multiply-add" of a flat rectangle is a minimum
     else if constexpr (MODE == 5) { (void)k; return v > acc ? v : acc; }          // dilate
@@ -105,13 +101,13 @@ template <int MODE> SL_HD uint32_t imad(uint32_t k, uint32_t v, uint32_t acc)
 
 struct V2 { uint32_t x, y; };
 struct V4 { uint32_t x, y, z, w; };
-SL_HD V2 ld2(const uint32_t* p) { V2 v; __builtin_memcpy(&v, p, 8); return v; }           // 8-byte aligned by construction: one ds_read_b64
-SL_HD V4 ld4(const uint32_t* p) { V4 v; __builtin_memcpy(&v, p, 16); return v; }          // 16-byte aligned: one ds_read_b128
+MI355_HD V2 ld2(const uint32_t* p) { V2 v; __builtin_memcpy(&v, p, 8); return v; }           // 8-byte aligned by construction: one ds_read_b64
+MI355_HD V4 ld4(const uint32_t* p) { V4 v; __builtin_memcpy(&v, p, 16); return v; }          // 16-byte aligned: one ds_read_b128
 
 // the per-segment constants every phase uses
 template <int CN> struct Seg {
     int px0, y0, rows, nsrc, nsteps, spn, fx0; bool xin;
-    SL_HD void init(const Geom& g, int strip, int segIdx)
+    MI355_HD void init(const Geom& g, int strip, int segIdx)
     {
         constexpr int TP = StripOf<CN>::TP;
         px0 = strip * TP; y0 = segIdx * g.seg;
@@ -133,7 +129,7 @@ constexpr int RPW = RB / 4;                                       // rows per wa
 template <int CN, bool LONG> struct StageOf { static constexpr int NXMAX = LONG ? 129 : 33, MMAX = ((StripOf<CN>::TP + NXMAX - 1) * CN + 63) / 64; };
 
 template <int MODE, int CN, int MMAX>
-SL_HD void stageLoad(const Geom& g, const Seg<CN>& sg, int step, const unsigned char* src, size_t sstep, int tid, uint32_t (&v)[RPW * MMAX])
+MI355_HD void stageLoad(const Geom& g, const Seg<CN>& sg, int step, const unsigned char* src, size_t sstep, int tid, uint32_t (&v)[RPW * MMAX])
 {
     const int wv = tid >> 6, ln = tid & 63;
     const int n0 = step * RB, rlim = imin(RB, sg.nsrc - n0);
@@ -162,7 +158,7 @@ SL_HD void stageLoad(const Geom& g, const Seg<CN>& sg, int step, const unsigned 
 }
 
 template <int CN, int MMAX>
-SL_HD void stageStore(const Geom& g, const Seg<CN>& sg, int step, uint32_t* S, int tid, const uint32_t (&v)[RPW * MMAX])
+MI355_HD void stageStore(const Geom& g, const Seg<CN>& sg, int step, uint32_t* S, int tid, const uint32_t (&v)[RPW * MMAX])
 {
     const int wv = tid >> 6, ln = tid & 63;
     const int n0 = step * RB, rlim = imin(RB, sg.nsrc - n0);
@@ -181,7 +177,7 @@ SL_HD void stageStore(const Geom& g, const Seg<CN>& sg, int step, uint32_t* S, i
 
 // ---- 2. row pass: 4 consecutive pixels of one plane of one row per lane; taps = kx (float bits or ints)
 template <int MODE, int CN>
-SL_HD void rowPass(const Geom& g, const Seg<CN>& sg, int step, const uint32_t* S, uint32_t* ring, const uint32_t* kx, int tid)
+MI355_HD void rowPass(const Geom& g, const Seg<CN>& sg, int step, const uint32_t* S, uint32_t* ring, const uint32_t* kx, int tid)
 {
     constexpr int Q4 = StripOf<CN>::TP / 4;
     const int n0 = step * RB, rlim = imin(RB, sg.nsrc - n0);
@@ -223,7 +219,7 @@ SL_HD void rowPass(const Geom& g, const Seg<CN>& sg, int step, const uint32_t* S
 }
 
 // output rows complete after `step`: those whose ny source rows are all in the ring
-template <int CN> SL_HD int doneAfter(const Geom& g, const Seg<CN>& sg, int step)
+template <int CN> MI355_HD int doneAfter(const Geom& g, const Seg<CN>& sg, int step)
 {
     const int staged = imin((step + 1) * RB, sg.nsrc);
     return imin(sg.rows, imax(0, staged - g.ny + 1));
@@ -231,7 +227,7 @@ template <int CN> SL_HD int doneAfter(const Geom& g, const Seg<CN>& sg, int step
 
 // ---- 3. column pass: output rows [done, newDone); ky = float bits or ints, kyS = mode 1's float(ky) * 2^-16
 template <int MODE, int CN>
-SL_HD void colPass(const Geom& g, const Seg<CN>& sg, int done, int newDone, const uint32_t* ring, const uint32_t* ky, const uint32_t* kyS,
+MI355_HD void colPass(const Geom& g, const Seg<CN>& sg, int done, int newDone, const uint32_t* ring, const uint32_t* ky, const uint32_t* kyS,
                    unsigned char* dst, size_t dstep, int tid)
 {
     constexpr int TP = StripOf<CN>::TP, PP = TP / 2, NPAIR = CN * PP;

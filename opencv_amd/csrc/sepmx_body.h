@@ -6,11 +6,7 @@
 #include <stddef.h>
 #include <string.h>
 
-#if defined(__HIPCC__)
-#define MX_HD __host__ __device__ __forceinline__
-#else
-#define MX_HD inline
-#endif
+#include "hd.h"
 
 namespace sepmx {
 
@@ -20,8 +16,8 @@ constexpr int TR = 32;           // rows per step (one matrix tile)
 constexpr int MAXKS = 9;         // 32-byte K steps of the column pass: 32 + ny - 1 <= 32 KSY (255 taps: the largest box filter); the kernel exists for KSY in {2, 3, 4, 5, 7, 9}
 constexpr int MAXKSX = 13;       // ... of the row pass: 32 + delta + (nx - 1) cn <= 32 KSX -- channels are interleaved elements, so three channels x 129 taps need 13;
                                  // the kernel exists for KSX in {2, 3, 4, 5, 7, 9, 13}, a count in between runs on the next one (the extra steps carry zero weights)
-MX_HD int ksxClass(int k) { return k <= 5 ? (k < 2 ? 2 : k) : k <= 7 ? 7 : k <= 9 ? 9 : 13; }
-MX_HD int ksyClass(int k) { return k <= 5 ? (k < 2 ? 2 : k) : k <= 7 ? 7 : 9; }
+MI355_HD int ksxClass(int k) { return k <= 5 ? (k < 2 ? 2 : k) : k <= 7 ? 7 : k <= 9 ? 9 : 13; }
+MI355_HD int ksyClass(int k) { return k <= 5 ? (k < 2 ? 2 : k) : k <= 7 ? 7 : 9; }
 
 struct Geom {
     int W, H, cn, WE;                          // the ROI; WE = W * cn elements per row
@@ -43,9 +39,9 @@ struct Geom {
 
 // v_mfma_i32_32x32x32_i8 operand maps (checked against the hardware by k_ccorr_ring_i8, templmatch.hip): lane (idx = lane & 31, h = lane >> 5), byte i of the 16-byte
 // operand <-> k = 16 h + i for A (idx = m) and B (idx = n) alike; result register i of lane (n, h) <-> row regRow(h, i), column n.
-MX_HD int regRow(int h, int i) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
+MI355_HD int regRow(int h, int i) { return (i & 3) + 8 * (i >> 2) + 4 * h; }
 
-MX_HD int borderIdx(int p, int len, int type)              // borderInterpolate (core/src/copy.cpp:748-793); -1 for BORDER_CONSTANT
+MI355_HD int borderIdx(int p, int len, int type)              // borderInterpolate (core/src/copy.cpp:748-793); -1 for BORDER_CONSTANT
 {
     if ((unsigned)p < (unsigned)len) return p;
     if (type == 1) return p < 0 ? 0 : len - 1;
@@ -69,7 +65,7 @@ MX_HD int borderIdx(int p, int len, int type)              // borderInterpolate 
 //                acc = 256 Hh + L with Hh = (signed) byte 1, L = (unsigned) byte 0; l = L - 128, both in int8           =>  R = 256 Hh + l + 128 + 128 P
 //   column pass  accH = sum ky Hh,  accL = C + sum ky l  =>  (accH << 8) + accL = sum ky R + 2^15 with C = (128 + 128 P) sum(ky) + 2^15: a constant of the COLUMN (P differs
 //                where BORDER_CONSTANT drops taps), i.e. of the lane; the value is < 2^24 and the result is its byte 2
-MX_HD int colSeed(int sumPresentTapsX, int sumTapsY, int box) { return (128 + 128 * sumPresentTapsX) * sumTapsY + (box ? 0 : 32768); }      // (a box filter wants the plain sum)
+MI355_HD int colSeed(int sumPresentTapsX, int sumTapsY, int box) { return (128 + 128 * sumPresentTapsX) * sumTapsY + (box ? 0 : 32768); }      // (a box filter wants the plain sum)
 
 // Row-pass B operand of one wave (strip X0, wave w: output elements X0 + 32 w + n): tab[ks][lane][16], lane (n, h), byte i <-> staged column k = 32 ks + 16 h + i of the
 // wave's window, which starts at ROI element X0 + 32 w - ax cn - delta.  The LEFT / RIGHT BORDER IS FOLDED INTO THE MATRIX: tap i of output element x reads pixel
@@ -123,14 +119,14 @@ inline void buildColA(const Geom& g, const uint16_t* ky, int8_t* tab)
 
 // The walk's staging geometry, shared by the kernel, plan() and the host emulation (tests/hostemu/sepmx_emu.cpp): strip s owns ROI elements [stripX0, stripX0 + TW); a
 // staged row piece is pieceChunks 16-byte chunks, chunk cc from ROI element chunkE0; step t of the segment at output row y0 stages the TR source rows from stepRow0.
-MX_HD int numStrips(const Geom& g) { return (g.WE + g.shift + TW - 1) / TW; }
-MX_HD int stripX0(const Geom& g, int strip) { return strip * TW - g.shift; }
-MX_HD constexpr int pieceChunks(int ksx) { return (TW - 32 + 32 * ksx) / 16; }
-MX_HD int chunkE0(const Geom& g, int X0, int cc) { return X0 - g.ax * g.cn - g.delta + 16 * cc; }
-MX_HD int stepRow0(const Geom& g, int y0, int t) { return y0 - g.ay + TR * t; }                    // (a ROI row; + offY = the parent's)
+MI355_HD int numStrips(const Geom& g) { return (g.WE + g.shift + TW - 1) / TW; }
+MI355_HD int stripX0(const Geom& g, int strip) { return strip * TW - g.shift; }
+MI355_HD constexpr int pieceChunks(int ksx) { return (TW - 32 + 32 * ksx) / 16; }
+MI355_HD int chunkE0(const Geom& g, int X0, int cc) { return X0 - g.ax * g.cn - g.delta + 16 * cc; }
+MI355_HD int stepRow0(const Geom& g, int y0, int t) { return y0 - g.ay + TR * t; }                    // (a ROI row; + offY = the parent's)
 // the UNCHECKED loader: every row of the step is a real row of the parent that is neither its first nor its last, and g.fast (plan()) says that on such rows every chunk
 // of every strip lies inside the parent's memory -- the chunks are loaded without chunkKind's test
-MX_HD bool innerStep(const Geom& g, int y0, int t)
+MI355_HD bool innerStep(const Geom& g, int y0, int t)
 {
     const int syA = stepRow0(g, y0, t) + g.offY;
     return g.fast && syA >= 1 && syA + TR - 1 <= g.fullH - 2;
@@ -138,7 +134,7 @@ MX_HD bool innerStep(const Geom& g, int y0, int t)
 // what g.fast promises, from the same expressions: the first chunk of the first strip on the parent's row 1 does not start before the parent's first byte, the last chunk
 // of the last strip on row fullH - 2 ends at or before its last.  (The piece starts shift + ax cn + delta bytes before the ROI's row and ends up to 223 + 32 KSX - ax cn
 // - delta bytes after it: a centred window keeps both under 512, cv::boxFilter with an anchor near the window's left end and 13 K steps reaches 639 bytes.)
-MX_HD bool innerFits(const Geom& g, size_t sstep)
+MI355_HD bool innerFits(const Geom& g, size_t sstep)
 {
     const long long lo = (long long)sstep + chunkE0(g, stripX0(g, 0), 0) + g.offX * g.cn;
     const long long hi = (long long)(g.fullH - 2) * (long long)sstep + chunkE0(g, stripX0(g, numStrips(g) - 1), pieceChunks(g.ksx) - 1) + 16 + g.offX * g.cn;
@@ -201,7 +197,7 @@ inline bool plan(Geom& g, const uint16_t* kx, const uint16_t* ky, uintptr_t srcA
 // load; what the bytes of columns outside the image hold does not matter).  Only chunks that would reach before the first / past the last byte of the parent -- first and
 // last rows -- are assembled byte by byte.
 enum { CH_ZERO = 0, CH_LOAD = 1, CH_BYTES = 2 };
-MX_HD int chunkKind(const Geom& g, const unsigned char* src, size_t sstep, int sy, int e0, const unsigned char** ptr, long long* rel)
+MI355_HD int chunkKind(const Geom& g, const unsigned char* src, size_t sstep, int sy, int e0, const unsigned char** ptr, long long* rel)
 {
     const int yy = borderIdx(sy + g.offY, g.fullH, g.border);
     if (yy < 0) return CH_ZERO;

@@ -1,8 +1,8 @@
 // speckle.hip -- cv::filterSpeckles (calib3d, stereosgbm.cpp; the reference has no HAL hook for it) on one channel of CV_8U or CV_16S, in place, single maps and
 // batches.  The definition is the project's own restatement (tests/speckle_restate.py): the connected components of the graph whose nodes are the pixels
 // != newVal and whose edges join 4-neighbours with |a - b| <= maxDiff; every pixel of a component of at most maxSpeckleSize pixels becomes newVal.  The pieces that
-// can be wrong are in speckle_math.h, compiled for the host by tests/hostemu/speckle_emu.cpp.  A union-find over pixels in scratch whose root is the smallest linear
-// pixel index (parents only decrease), a 32-bit size at the root.
+// can be wrong are in speckle_math.h, compiled for the host by tests/hostemu/speckle_emu.cpp.  A union-find over pixels in scratch (unionfind.h) whose root is the
+// smallest linear pixel index (parents only decrease), a 32-bit size at the root.
 //
 //   plain path   k_spk_init    a parent per pixel, its own index or DEAD; the size counters zeroed (scratch is reused between calls)
 //                k_spk_link    a thread per pixel: the links to the left and the upper neighbour, united in HBM with atomicMin.  A find may read a parent another
@@ -30,6 +30,8 @@ using spk::DEAD;
 using spk::STRIP_H;
 using spk::TILE_W;
 using spk::WORDS;
+using uf::GlobalMem;
+using uf::LdsMem;
 
 static_assert(spk::MAX_DIM == lim::SPECKLE_MAX_DIM && TILE_W == lim::SPECKLE_TILE_COLS && STRIP_H == lim::SPECKLE_TILE_ROWS, "mi355cv_limit(\"speckle_*\")");
 static_assert((long long)spk::MAX_DIM * spk::MAX_DIM <= (1ll << 28), "a pixel index and a size in 32 bits, below DEAD");
@@ -39,17 +41,6 @@ struct Frame { const uchar* src; size_t sstep; uchar* dst; size_t dstep; };
 // the scratch of a call: parents and sizes, `frame` elements apart per frame
 struct Scr { uint32_t* P; uint32_t* C; size_t frame; };
 struct Rule { int newVal, maxDiff, maxSize; };
-
-struct GlobalMem {
-    uint32_t* P;
-    __device__ __forceinline__ uint32_t load(uint32_t i) const { return __hip_atomic_load(P + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
-    __device__ __forceinline__ uint32_t amin(uint32_t i, uint32_t v) const { return atomicMin(P + i, v); }
-};
-struct LdsMem {
-    uint32_t* par;
-    __device__ __forceinline__ uint32_t load(uint32_t i) const { return ((volatile uint32_t*)par)[i]; }
-    __device__ __forceinline__ uint32_t amin(uint32_t i, uint32_t v) const { return atomicMin(par + i, v); }
-};
 
 template <typename T> __device__ __forceinline__ const T* rowOf(const Frame& F, int y) { return reinterpret_cast<const T*>(F.src + (size_t)y * F.sstep); }
 
@@ -257,8 +248,6 @@ __global__ __launch_bounds__(256) void k_spk_erase(const Frame* __restrict__ fra
 
 // ------------------------------------------------------------------------------------------------------------------------------------ host side
 std::atomic<int> g_kernelMode{-1};       // mi355cv_filterSpecklesSetKernel: -1 the rule below (the tile kernel for every shape), 0 always the plain kernels
-
-inline size_t span(size_t step, int rows, size_t rowBytes) { return (size_t)(rows - 1) * step + rowBytes; }
 
 template <typename T>
 void launchAll(const Frame* dFrames, int W, int H, int nframes, Rule R, Scr s, bool fast, hipStream_t st)

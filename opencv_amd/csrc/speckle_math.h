@@ -3,9 +3,9 @@
 //
 //   live      a pixel is live iff its value != newVal
 //   linked    two live 4-neighbours are linked iff |a - b| <= maxDiff, in int: a CV_16S difference reaches 65535 and does not wrap; maxDiff < 0 links nothing
-//   roots     a union-find over pixels whose root is the SMALLEST linear pixel index of the set, parents only ever decrease (as ccl_math.h, whose bit helpers
-//             and tile geometry are shared, not copied); find / unite are written once over a memory policy: agent-scope loads and atomicMin on HBM, atomicMin
-//             on LDS, plain loads and stores in the host build
+//   roots     a union-find over pixels whose root is the SMALLEST linear pixel index of the set, parents only ever decrease.  It is unionfind.h's find / unite over
+//             a memory policy (agent-scope loads and atomicMin on HBM, atomicMin on LDS, plain loads and stores in the host build), the one ccl.hip merges
+//             with; the bit helpers and the tile geometry are ccl_math.h's, shared, not copied
 //   tile      the fast kernel cuts a frame into tiles of TILE_W x STRIP_H.  Per row three bit planes: live, link-left (pixel c is linked to c - 1 of the same tile
 //             row; never set in column 0 of a tile) and link-up (linked to the pixel above; never set in row 0 of a tile).  A run starts at a live pixel whose
 //             link-left bit is 0 (runStartOf); the node of a pixel is the first pixel of its run.  upDirect keeps one link-up bit per pair (run, run above).
@@ -13,6 +13,7 @@
 //   erase     a live pixel of a component with size <= maxSpeckleSize becomes newVal (erased); maxSpeckleSize <= 0 erases nothing since a size is >= 1
 #pragma once
 #include "ccl_math.h"
+#include "unionfind.h"
 
 namespace spk {
 
@@ -21,29 +22,14 @@ constexpr int STRIP_H = ccl::STRIP_H;            // ("speckle_tile_rows"): rows 
 constexpr int WORDS = ccl::WORDS;
 constexpr int MAX_DIM = 16384;                   // ("speckle_max_dim"): a pixel index and a component size stay below 2^28
 constexpr uint32_t DEAD = ccl::BG;               // parent of a pixel that is not live
+using uf::find;                                  // spk::find / spk::unite are unionfind.h's
+using uf::unite;
 
 MI355_HD bool live(int v, int newVal) { return v != newVal; }
 MI355_HD bool linked(int a, int b, int maxDiff) { const int d = a - b; return (d < 0 ? -d : d) <= maxDiff; }
 MI355_HD bool erased(bool isLive, uint32_t size, int maxSpeckleSize) { return isLive && (long long)size <= (long long)maxSpeckleSize; }
 // newVal as the depth stores it
 MI355_HD bool fitsDepth(int newVal, bool is16s) { return is16s ? (newVal >= -32768 && newVal <= 32767) : (newVal >= 0 && newVal <= 255); }
-
-// M: load(i) -> parent of i, amin(i, v) -> the old parent of i, which becomes min(old, v)
-template <class M> MI355_HD uint32_t find(M& m, uint32_t x)
-{
-    for (;;) { const uint32_t p = m.load(x); if (p >= x) return x; x = p; }
-}
-template <class M> MI355_HD void unite(M& m, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = find(m, a); b = find(m, b);
-        if (a == b) return;
-        if (a < b) { const uint32_t t = a; a = b; b = t; }
-        const uint32_t old = m.amin(a, b);                  // a was a root when read: old == a unless another union got there first
-        if (old == a) return;
-        a = old;                                            // the set a pointed to still has to meet b
-    }
-}
 
 // S = live & ~link-left, the run starts of a tile row; (j, lane) is a live pixel: the column in the tile of the first pixel of its run
 MI355_HD int runStartOf(const uint64_t* S, int j, int lane)

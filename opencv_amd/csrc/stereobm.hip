@@ -345,8 +345,6 @@ int checkParams(const mi355cv_StereoBMParams* p, int width, int height, int disp
     return MI355CV_OK;
 }
 
-inline size_t span(size_t step, int rows, size_t rowBytes) { return (size_t)(rows - 1) * step + rowBytes; }
-
 void launchPrefilter(const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, const Frame* frames, int which, int W, int H, int cap, int nframes,
                      bool srcAligned, bool dstAligned, hipStream_t st)
 {

@@ -11,16 +11,7 @@
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
-#if !defined(__HIPCC__)
-#ifndef __host__
-#define __host__
-#endif
-#ifndef __device__
-#define __device__
-#endif
-#endif
-
-#define SBM_HD __host__ __device__ inline
+#include "hd.h"
 
 namespace sbm {
 
@@ -36,8 +27,8 @@ constexpr int ROLL_TILE = 64;             // ("stereobm_tile_cols"): window colu
 constexpr int ROLL_STRIP = 32;            // ("stereobm_strip_rows"): rows a workgroup of the fast kernel walks down
 constexpr int GENERIC_TILE = 32;          // ("stereobm_generic_tile_cols"): pixels of a row per workgroup of the generic kernel
 
-SBM_HD int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
-SBM_HD int reflect101(int r, int len)
+MI355_HD_PLAIN int clampi(int v, int lo, int hi) { return v < lo ? lo : v > hi ? hi : v; }
+MI355_HD_PLAIN int reflect101(int r, int len)
 {
     if (len == 1) return 0;
     while (r < 0 || r >= len) r = r < 0 ? -r : 2 * (len - 1) - r;
@@ -45,7 +36,7 @@ SBM_HD int reflect101(int r, int len)
 }
 
 struct Geom { int m, n, Dmax, xlo, xhi, rlo, rhi, filtered; };
-SBM_HD Geom geomOf(int W, int m, int n)
+MI355_HD_PLAIN Geom geomOf(int W, int m, int n)
 {
     Geom g;
     g.m = m; g.n = n; g.Dmax = m + n - 1;
@@ -56,12 +47,12 @@ SBM_HD Geom geomOf(int W, int m, int n)
     g.filtered = (m - 1) * 16;
     return g;
 }
-SBM_HD int leftCol(int u, int W) { return clampi(u, 0, W - 1); }
+MI355_HD_PLAIN int leftCol(int u, int W) { return clampi(u, 0, W - 1); }
 // the right image's column for window column u and disparity D
-SBM_HD int rightCol(int u, int D, const Geom& g) { return clampi(u, g.rlo, g.rhi) - D; }
+MI355_HD_PLAIN int rightCol(int u, int D, const Geom& g) { return clampi(u, g.rlo, g.rhi) - D; }
 
 // one XSOBEL pixel from the three rows (already reflected) of the image
-SBM_HD uint8_t xsobelPixel(const uint8_t* rm, const uint8_t* r0, const uint8_t* rp, int x, int W, int cap)
+MI355_HD_PLAIN uint8_t xsobelPixel(const uint8_t* rm, const uint8_t* r0, const uint8_t* rp, int x, int W, int cap)
 {
     if (x < 1 || x > W - 2) return (uint8_t)cap;
     const int v = cap + ((int)rm[x + 1] - (int)rm[x - 1]) + 2 * ((int)r0[x + 1] - (int)r0[x - 1]) + ((int)rp[x + 1] - (int)rp[x - 1]);
@@ -69,7 +60,7 @@ SBM_HD uint8_t xsobelPixel(const uint8_t* rm, const uint8_t* r0, const uint8_t* 
 }
 
 // acc + |a - b| for two byte values: one v_sad_u8 on the device
-SBM_HD uint32_t absdiffAcc(uint32_t a, uint32_t b, uint32_t acc)
+MI355_HD_PLAIN uint32_t absdiffAcc(uint32_t a, uint32_t b, uint32_t acc)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_sad_u8(a, b, acc);
@@ -80,27 +71,27 @@ SBM_HD uint32_t absdiffAcc(uint32_t a, uint32_t b, uint32_t acc)
 
 // ---- the decision of one pixel over its n SADs, index i = Dmax - D
 // (cost, i) as one unsigned: the smallest key is the smallest i among the smallest costs.  cost < 2^19, i < 2^8
-SBM_HD uint32_t minKey(uint32_t cost, int i) { return (cost << 8) | (uint32_t)i; }
-SBM_HD int keyCost(uint32_t key) { return (int)(key >> 8); }
-SBM_HD int keyIndex(uint32_t key) { return (int)(key & 255u); }
-SBM_HD long long uniqThresh(int ms, int uniquenessRatio) { return (long long)ms + (long long)ms * uniquenessRatio / 100; }
+MI355_HD_PLAIN uint32_t minKey(uint32_t cost, int i) { return (cost << 8) | (uint32_t)i; }
+MI355_HD_PLAIN int keyCost(uint32_t key) { return (int)(key >> 8); }
+MI355_HD_PLAIN int keyIndex(uint32_t key) { return (int)(key & 255u); }
+MI355_HD_PLAIN long long uniqThresh(int ms, int uniquenessRatio) { return (long long)ms + (long long)ms * uniquenessRatio / 100; }
 // the uniqueness test looks at the smallest SAD outside [mi - 1, mi + 1]: `cost` for such an index, NO_COST inside (no compare: (1 - s * s) is negative iff |s| > 1)
 constexpr uint32_t NO_COST = 0xffffffffu;
-SBM_HD uint32_t outsideCost(int i, int mi, uint32_t cost) { const int s = i - mi; return cost | ~(uint32_t)((1 - s * s) >> 31); }
-SBM_HD bool uniqRejects(uint32_t minOutside, int ms, int uniquenessRatio) { return minOutside != NO_COST && (long long)minOutside <= uniqThresh(ms, uniquenessRatio); }
+MI355_HD_PLAIN uint32_t outsideCost(int i, int mi, uint32_t cost) { const int s = i - mi; return cost | ~(uint32_t)((1 - s * s) >> 31); }
+MI355_HD_PLAIN bool uniqRejects(uint32_t minOutside, int ms, int uniquenessRatio) { return minOutside != NO_COST && (long long)minOutside <= uniqThresh(ms, uniquenessRatio); }
 // p = SAD[mi + 1] (SAD[n - 2] at mi = n - 1), nn = SAD[mi - 1] (SAD[1] at mi = 0)
-SBM_HD int subpixel(int ms, int p, int nn, int Dmax, int mi)
+MI355_HD_PLAIN int subpixel(int ms, int p, int nn, int Dmax, int mi)
 {
     const int ad = p > nn ? p - nn : nn - p;
     const int dd = p + nn - 2 * ms + ad;
     const int q = dd ? (p - nn) * 256 / dd : 0;                 // C division: toward zero
     return ((Dmax - mi) * 256 + q + 15) >> 4;                   // arithmetic shift
 }
-SBM_HD int nextIndex(int mi, int n) { return mi + 1 < n ? mi + 1 : n - 2; }
-SBM_HD int prevIndex(int mi) { return mi > 0 ? mi - 1 : 1; }
+MI355_HD_PLAIN int nextIndex(int mi, int n) { return mi + 1 < n ? mi + 1 : n - 2; }
+MI355_HD_PLAIN int prevIndex(int mi) { return mi > 0 ? mi - 1 : 1; }
 
 // sad(i): the pixel's SAD at index i.  *winCost: the winner's SAD when the pixel is kept
-template <class F> SBM_HD int decide(F sad, int n, int T, int textureThreshold, int uniquenessRatio, const Geom& g, int* winCost)
+template <class F> MI355_HD_PLAIN int decide(F sad, int n, int T, int textureThreshold, int uniquenessRatio, const Geom& g, int* winCost)
 {
     if (T < textureThreshold) return g.filtered;
     uint32_t best = 0xffffffffu;
@@ -117,11 +108,11 @@ template <class F> SBM_HD int decide(F sad, int n, int T, int textureThreshold, 
 
 // ---- the left-right check: pixel x with disparity d (16S, not FILTERED) and winner's cost votes for column x2 with this key
 constexpr unsigned long long LR_NONE = ~0ull;
-SBM_HD int lrTarget(int x, int d) { return x - ((d + 8) >> 4); }
-SBM_HD unsigned long long lrKey(int cost, int x, int d) { return ((unsigned long long)(uint32_t)cost << 32) | ((unsigned long long)(uint32_t)x << 16) | (uint16_t)(int16_t)d; }
-SBM_HD int lrDisp(unsigned long long key, int filtered) { return key == LR_NONE ? filtered : (int)(int16_t)(uint16_t)(key & 0xffffu); }
+MI355_HD_PLAIN int lrTarget(int x, int d) { return x - ((d + 8) >> 4); }
+MI355_HD_PLAIN unsigned long long lrKey(int cost, int x, int d) { return ((unsigned long long)(uint32_t)cost << 32) | ((unsigned long long)(uint32_t)x << 16) | (uint16_t)(int16_t)d; }
+MI355_HD_PLAIN int lrDisp(unsigned long long key, int filtered) { return key == LR_NONE ? filtered : (int)(int16_t)(uint16_t)(key & 0xffffu); }
 // d2At(xk): the disparity voted into column xk (FILTERED when none); true: d[x] becomes FILTERED
-template <class F> SBM_HD bool lrRejects(F d2At, int x, int d, int W, int disp12MaxDiff, int filtered)
+template <class F> MI355_HD_PLAIN bool lrRejects(F d2At, int x, int d, int W, int disp12MaxDiff, int filtered)
 {
     const long long lim = 16ll * disp12MaxDiff;
     const int xs[2] = {x - (d >> 4), x - ((d + 15) >> 4)};

@@ -23,11 +23,7 @@
 #include <stdint.h>
 #include <stddef.h>
 
-#if defined(__HIPCC__)
-#define W8_HD __host__ __device__ __forceinline__
-#else
-#define W8_HD inline
-#endif
+#include "hd.h"
 
 namespace warp8 {
 
@@ -55,7 +51,7 @@ struct Args {
     double rzScaleX, rzInvX, rzScaleY, rzInvY; int rzArea;      // bilinear resize on the same machinery (k_resize8_lean): cv::resize's scale factors; INTER_AREA's coefficient form
 };
 
-W8_HD int satIntD(double v)
+MI355_HD int satIntD(double v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return v >= 2147483647.0 ? 2147483647 : v <= -2147483648.0 ? (int)-2147483648LL : (int)__double2int_rn(v);
@@ -65,7 +61,7 @@ W8_HD int satIntD(double v)
     return (int)__builtin_rint(v);                       // round half to even, like cvRound / v_cvt_i32_f64
 #endif
 }
-W8_HD double dmul(double a, double b)
+MI355_HD double dmul(double a, double b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __dmul_rn(a, b);
@@ -73,7 +69,7 @@ W8_HD double dmul(double a, double b)
     return a * b;                                        // the host emulation is compiled with -ffp-contract=off
 #endif
 }
-W8_HD double dadd(double a, double b)
+MI355_HD double dadd(double a, double b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __dadd_rn(a, b);
@@ -81,7 +77,7 @@ W8_HD double dadd(double a, double b)
     return a + b;
 #endif
 }
-W8_HD double ddiv(double a, double b)
+MI355_HD double ddiv(double a, double b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __ddiv_rn(a, b);
@@ -89,7 +85,7 @@ W8_HD double ddiv(double a, double b)
     return a / b;
 #endif
 }
-W8_HD uint32_t dot4(uint32_t a, uint32_t b, uint32_t c)
+MI355_HD uint32_t dot4(uint32_t a, uint32_t b, uint32_t c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_udot4(a, b, c, false);
@@ -98,7 +94,7 @@ W8_HD uint32_t dot4(uint32_t a, uint32_t b, uint32_t c)
 #endif
 }
 // packed 16-bit lanes: a * b (low 16 bits per lane), a * b + c, and the dot product of two pairs + c
-W8_HD uint32_t pkMul(uint32_t a, uint32_t b)
+MI355_HD uint32_t pkMul(uint32_t a, uint32_t b)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -107,7 +103,7 @@ W8_HD uint32_t pkMul(uint32_t a, uint32_t b)
     return (((a & 0xffffu) * (b & 0xffffu)) & 0xffffu) | ((((a >> 16) * (b >> 16)) & 0xffffu) << 16);
 #endif
 }
-W8_HD uint32_t pkMad(uint32_t a, uint32_t b, uint32_t c)
+MI355_HD uint32_t pkMad(uint32_t a, uint32_t b, uint32_t c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -116,7 +112,7 @@ W8_HD uint32_t pkMad(uint32_t a, uint32_t b, uint32_t c)
     return (((a & 0xffffu) * (b & 0xffffu) + (c & 0xffffu)) & 0xffffu) | ((((a >> 16) * (b >> 16) + (c >> 16)) & 0xffffu) << 16);
 #endif
 }
-W8_HD uint32_t dot2(uint32_t a, uint32_t b, uint32_t c)
+MI355_HD uint32_t dot2(uint32_t a, uint32_t b, uint32_t c)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef unsigned short u16x2 __attribute__((ext_vector_type(2)));
@@ -125,18 +121,18 @@ W8_HD uint32_t dot2(uint32_t a, uint32_t b, uint32_t c)
     return c + (a & 0xffffu) * (b & 0xffffu) + (a >> 16) * (b >> 16);
 #endif
 }
-W8_HD uint32_t ld16(const unsigned char* p)
+MI355_HD uint32_t ld16(const unsigned char* p)
 {
     typedef unsigned short u16u __attribute__((aligned(1)));
     return *reinterpret_cast<const u16u*>(p);
 }
-W8_HD uint32_t ld32(const unsigned char* p)
+MI355_HD uint32_t ld32(const unsigned char* p)
 {
     typedef uint32_t u32u __attribute__((aligned(1)));
     return *reinterpret_cast<const u32u*>(p);
 }
 // ({hi, lo} >> 8 * (sh & 3)) & 0xffffffff
-W8_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh)
+MI355_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_alignbyte(hi, lo, sh);
@@ -147,17 +143,17 @@ W8_HD uint32_t alignbyte(uint32_t hi, uint32_t lo, uint32_t sh)
 
 // (the four functions below are the definitions; tcolX .. trowY read the per-call tables when the launch provided them)
 // affine coordinate terms (WarpAffineInvoker imgwarp.cpp:2252-2262 with hal::warpAffineBlocklineNN's adelta / bdelta :2699-2713): 1/1024 px, round delta 16
-W8_HD int affRowX(const Args& a, int y) { return satIntD(dmul(dadd(dmul(a.M[1], (double)y), a.M[2]), 1024.0)) + 16; }
-W8_HD int affRowY(const Args& a, int y) { return satIntD(dmul(dadd(dmul(a.M[4], (double)y), a.M[5]), 1024.0)) + 16; }
-W8_HD int affColX(const Args& a, int x) { return satIntD(dmul(dmul(a.M[0], (double)x), 1024.0)); }
-W8_HD int affColY(const Args& a, int x) { return satIntD(dmul(dmul(a.M[3], (double)x), 1024.0)); }
-W8_HD int tcolX(const Args& a, int x) { return a.colT ? a.colT[x < a.dw ? x : a.dw - 1] : affColX(a, x); }
-W8_HD int tcolY(const Args& a, int x) { return a.colT ? a.colT[a.dw + (x < a.dw ? x : a.dw - 1)] : affColY(a, x); }
-W8_HD int trowX(const Args& a, int y) { return a.rowT ? a.rowT[y < a.dh ? y : a.dh - 1] : affRowX(a, y); }
-W8_HD int trowY(const Args& a, int y) { return a.rowT ? a.rowT[a.dh + (y < a.dh ? y : a.dh - 1)] : affRowY(a, y); }
+MI355_HD int affRowX(const Args& a, int y) { return satIntD(dmul(dadd(dmul(a.M[1], (double)y), a.M[2]), 1024.0)) + 16; }
+MI355_HD int affRowY(const Args& a, int y) { return satIntD(dmul(dadd(dmul(a.M[4], (double)y), a.M[5]), 1024.0)) + 16; }
+MI355_HD int affColX(const Args& a, int x) { return satIntD(dmul(dmul(a.M[0], (double)x), 1024.0)); }
+MI355_HD int affColY(const Args& a, int x) { return satIntD(dmul(dmul(a.M[3], (double)x), 1024.0)); }
+MI355_HD int tcolX(const Args& a, int x) { return a.colT ? a.colT[x < a.dw ? x : a.dw - 1] : affColX(a, x); }
+MI355_HD int tcolY(const Args& a, int x) { return a.colT ? a.colT[a.dw + (x < a.dw ? x : a.dw - 1)] : affColY(a, x); }
+MI355_HD int trowX(const Args& a, int y) { return a.rowT ? a.rowT[y < a.dh ? y : a.dh - 1] : affRowX(a, y); }
+MI355_HD int trowY(const Args& a, int y) { return a.rowT ? a.rowT[a.dh + (y < a.dh ? y : a.dh - 1)] : affRowY(a, y); }
 
 // projective coordinates in 1/32 px (WarpPerspectiveInvoker :3195-3235 / hal::warpPerspectiveBlockline: the row terms start at the block's first column)
-W8_HD void perspXY(const Args& a, int x, int y, int& X, int& Y)
+MI355_HD void perspXY(const Args& a, int x, int y, int& X, int& Y)
 {
     const int xb = (x / a.bw0) * a.bw0, x1 = x - xb;
     const double X0 = dadd(dadd(dmul(a.M[0], (double)xb), dmul(a.M[1], (double)y)), a.M[2]);
@@ -182,10 +178,10 @@ struct Box { int cx0, cy0, cw, ch, shift, all; };
 // The box is built from a handful of coordinate evaluations (`terms`), one per lane of the first wave, so that no thread walks the double arithmetic alone:
 //   affine       terms[0..7]  = rowX(y0), rowX(y1), colX(x0), colX(x1), rowY(y0), rowY(y1), colY(x0), colY(x1)
 //   perspective  terms[3i..3i+2] = X, Y (1/32 px) and the sign of the denominator at corner i of the tile (i = 0..3)
-template <int KIND> W8_HD int boxTermCount() { return KIND == 0 ? 8 : 12; }
+template <int KIND> MI355_HD int boxTermCount() { return KIND == 0 ? 8 : 12; }
 
 template <int KIND>
-W8_HD void boxTerm(const Args& a, int x0, int y0, int k, int* terms)
+MI355_HD void boxTerm(const Args& a, int x0, int y0, int k, int* terms)
 {
     const int x1 = (x0 + TW < a.dw ? x0 + TW : a.dw) - 1, y1 = (y0 + a.th < a.dh ? y0 + a.th : a.dh) - 1;
     if (KIND == 0) {
@@ -200,7 +196,7 @@ W8_HD void boxTerm(const Args& a, int x0, int y0, int k, int* terms)
 }
 
 template <int CN, int KIND>
-W8_HD Box boxFromTerms(const Args& a, const int* t)
+MI355_HD Box boxFromTerms(const Args& a, const int* t)
 {
     Box b = {0, 0, 0, 0, 0, 0};                                       // (perspective early-outs below: cw = ch = 0, the generic sampler takes the tile)
     int bx0, bx1, by0, by1, exact = 1;
@@ -237,7 +233,7 @@ W8_HD Box boxFromTerms(const Args& a, const int* t)
 // staging: thread `tid` of 256 copies its share of the box into the LDS tile, whole aligned dwords.  Row r of the tile starts at the aligned dword that
 // holds pixel (cx0, cy0 + r); sstep % 4 == 0 makes the in-dword shift the same for every row.  The last dword of the image's last row is assembled from
 // bytes (a whole-dword load could read up to 3 bytes past the last pixel).
-W8_HD void stage(const Args& a, const Box& b, int cn, const unsigned char* src, unsigned char* tile, int tid)
+MI355_HD void stage(const Args& a, const Box& b, int cn, const unsigned char* src, unsigned char* tile, int tid)
 {
     if (b.cw == 0) return;
     const uint32_t nd = (uint32_t)(b.shift + b.cw * cn + 3) >> 2, pd = (uint32_t)a.ldsPitch >> 2;       // dwords per row to load / per LDS row
@@ -281,7 +277,7 @@ W8_HD void stage(const Args& a, const Box& b, int cn, const unsigned char* src, 
 // 16-bit reads measured slow as well (4K 8UC1, 7 degrees: 30.9 us per frame against 17.1 with aligned dwords + a byte funnel shift), so FETCH 1 -- the
 // default -- reads the ALIGNED dwords around the taps and shifts; FETCH 0 keeps the reads at the taps' own addresses (A/B runs).
 template <int CN, int FETCH>
-W8_HD void fetchTaps(const unsigned char* p, uint32_t pitch, uint32_t (&t)[4])
+MI355_HD void fetchTaps(const unsigned char* p, uint32_t pitch, uint32_t (&t)[4])
 {
     const unsigned char* p1 = p + pitch;
     if (CN == 4) {                                                   // a pixel is a dword: always aligned
@@ -303,7 +299,7 @@ W8_HD void fetchTaps(const unsigned char* p, uint32_t pitch, uint32_t (&t)[4])
 
 // wx = (32 - ax) in both 16-bit lanes, wx1 = ax in both, wy = (32 - ay) | ay << 16
 template <int CN>
-W8_HD uint32_t bilinearOf(const uint32_t (&t)[4], uint32_t wx0, uint32_t wx1, uint32_t wy)
+MI355_HD uint32_t bilinearOf(const uint32_t (&t)[4], uint32_t wx0, uint32_t wx1, uint32_t wy)
 {
     const unsigned long long q0 = t[0] | ((unsigned long long)t[1] << 32), q1 = t[2] | ((unsigned long long)t[3] << 32);
     uint32_t out = 0;
@@ -323,14 +319,14 @@ W8_HD uint32_t bilinearOf(const uint32_t (&t)[4], uint32_t wx0, uint32_t wx1, ui
 // ---- the three phases of a workgroup (256 threads), separated by barriers in the kernel; tests/hostemu runs them thread by thread -------------------------
 // A: box terms (the first lanes)
 template <int KIND>
-W8_HD void phaseA(const Args& a, int x0, int y0, unsigned char* lds, int tid)
+MI355_HD void phaseA(const Args& a, int x0, int y0, unsigned char* lds, int tid)
 {
     if (tid < (KIND == 0 ? 8 : 4)) boxTerm<KIND>(a, x0, y0, tid, reinterpret_cast<int*>(lds + OFF_TERMS));
 }
 
 // B: the source box into the tile; affine: column terms of the tile's 128 columns and row terms of its rows (box origin folded into the row terms)
 template <int CN, int KIND>
-W8_HD void phaseB(const Args& a, const Box& b, int x0, int y0, const unsigned char* src, unsigned char* lds, int tid)
+MI355_HD void phaseB(const Args& a, const Box& b, int x0, int y0, const unsigned char* src, unsigned char* lds, int tid)
 {
     stage(a, b, CN, src, lds + OFF_TILE, tid);
     if (KIND == 0) {
@@ -344,9 +340,9 @@ W8_HD void phaseB(const Args& a, const Box& b, int x0, int y0, const unsigned ch
 // footprint is not strictly inside the loaded box reads LDS offset 0 instead) and stored as one dword / three / four when all four are good; otherwise the
 // group's bit is set in the returned mask and the kernel redoes the whole group with the generic sampler afterwards (same arithmetic for interior pixels,
 // borders and BORDER_TRANSPARENT handled there).  ALL = the tile's box is known to contain every footprint: no per-pixel test at all.
-template <int CN> W8_HD constexpr int tileRows() { return CN == 1 ? 32 : 16; }
+template <int CN> MI355_HD constexpr int tileRows() { return CN == 1 ? 32 : 16; }
 
-W8_HD uint32_t mad24(uint32_t x, uint32_t y, uint32_t z)
+MI355_HD uint32_t mad24(uint32_t x, uint32_t y, uint32_t z)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __umul24(x, y) + z;
@@ -356,7 +352,7 @@ W8_HD uint32_t mad24(uint32_t x, uint32_t y, uint32_t z)
 }
 
 template <int CN, int KIND, bool ALL, int FETCH>
-W8_HD unsigned rowsC(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, unsigned char* dst, int tid)
+MI355_HD unsigned rowsC(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, unsigned char* dst, int tid)
 {
     const int* col = reinterpret_cast<const int*>(lds + OFF_COL); const int* row = reinterpret_cast<const int*>(lds + OFF_ROW);
     const unsigned char* tile = lds + OFF_TILE;
@@ -428,7 +424,7 @@ W8_HD unsigned rowsC(const Args& a, const Box& b, int x0, int y0, const unsigned
 }
 
 template <int CN, int KIND, int FETCH = 0>
-W8_HD unsigned phaseC(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, unsigned char* dst, int tid)
+MI355_HD unsigned phaseC(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, unsigned char* dst, int tid)
 {
     if (b.cw == 0 && !(a.constBorder && b.ch == -1)) {                // nothing staged (box too large for the LDS allotment): every group is redone
         const int lane = tid & 63, x = x0 + (lane & (LX - 1)) * PX;
@@ -440,7 +436,7 @@ W8_HD unsigned phaseC(const Args& a, const Box& b, int x0, int y0, const unsigne
 // the groups phaseC left: slow(x, y, X, Y) for every destination pixel of them, (X, Y) = its source coordinates in 1/32 px (affine: from the row / column
 // terms still in LDS, box origin added back)
 template <int CN, int KIND, class Slow>
-W8_HD void redoGroups(const Args& a, const Box& b, unsigned redo, int x0, int y0, const unsigned char* lds, int tid, Slow slow)
+MI355_HD void redoGroups(const Args& a, const Box& b, unsigned redo, int x0, int y0, const unsigned char* lds, int tid, Slow slow)
 {
     const int* col = reinterpret_cast<const int*>(lds + OFF_COL); const int* row = reinterpret_cast<const int*>(lds + OFF_ROW);
     const int wave = tid >> 6, lane = tid & 63, lx = lane & (LX - 1), x = x0 + lx * PX;
@@ -463,7 +459,7 @@ W8_HD void redoGroups(const Args& a, const Box& b, unsigned redo, int x0, int y0
 // lanes (perm) and multiplies them with the Q15 weight pairs of initInterTab2D's table (dot2; the table sits in LDS beside the tile, `wq`: 8 dwords per
 // (ay * 32 + ax) entry, ESTR dwords apart).  Exact integers: (sum + 2^14) >> 15, saturated.  Pixels whose 4 x 4 footprint is not inside the staged box are left
 // to the generic sampler (redo mask), as on the bilinear path; BORDER_CONSTANT pixels wholly outside the source are the border value.
-W8_HD uint32_t permBytes(uint32_t hi, uint32_t lo, uint32_t sel)               // v_perm_b32: selector bytes 0-3 pick from lo, 4-7 from hi, 0x0c = zero
+MI355_HD uint32_t permBytes(uint32_t hi, uint32_t lo, uint32_t sel)               // v_perm_b32: selector bytes 0-3 pick from lo, 4-7 from hi, 0x0c = zero
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_perm(hi, lo, sel);
@@ -473,7 +469,7 @@ W8_HD uint32_t permBytes(uint32_t hi, uint32_t lo, uint32_t sel)               /
     return o;
 #endif
 }
-W8_HD int sdot2(uint32_t a, uint32_t b, int c)                                 // v_dot2_i32_i16
+MI355_HD int sdot2(uint32_t a, uint32_t b, int c)                                 // v_dot2_i32_i16
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     typedef short s16x2 __attribute__((ext_vector_type(2)));
@@ -485,7 +481,7 @@ W8_HD int sdot2(uint32_t a, uint32_t b, int c)                                 /
 
 // the affine box of boxFromTerms<CN, 0> grown by the bicubic margins; same conventions (cw == 0: nothing staged; ch == -1: nothing to stage but classifiable)
 template <int CN>
-W8_HD Box boxFromTerms4(const Args& a, const int* t)
+MI355_HD Box boxFromTerms4(const Args& a, const int* t)
 {
     Box b = {0, 0, 0, 0, 0, 0};
     const int bx0 = (((t[0] < t[1] ? t[0] : t[1]) + (t[2] < t[3] ? t[2] : t[3])) >> 10) - 1, bx1 = (((t[0] > t[1] ? t[0] : t[1]) + (t[2] > t[3] ? t[2] : t[3])) >> 10) + 2;
@@ -502,7 +498,7 @@ W8_HD Box boxFromTerms4(const Args& a, const int* t)
 
 // CN result bytes (low bits) of one pixel: `p` = its first tap in the tile, `w` = the 8 weight-pair dwords of its table entry
 template <int CN>
-W8_HD uint32_t bicubicAt(const unsigned char* p, uint32_t pitch, const uint32_t* w)
+MI355_HD uint32_t bicubicAt(const unsigned char* p, uint32_t pitch, const uint32_t* w)
 {
     constexpr int ND = CN == 1 ? 1 : 3;                                          // dwords of a tap row (4 * CN bytes)
     const uint32_t sh = (uint32_t)(uintptr_t)p & 3u;                             // the pitch is a multiple of 4: the same shift on every row
@@ -542,7 +538,7 @@ W8_HD uint32_t bicubicAt(const unsigned char* p, uint32_t pitch, const uint32_t*
 
 // phase C of the bicubic path: rowsC's structure (a lane = four neighbouring destination pixels of a row per step; one dword / three stored when all four are good)
 template <int CN, bool ALL>
-W8_HD unsigned rowsC4(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, const uint32_t* wq, int estr, unsigned char* dst, int tid)
+MI355_HD unsigned rowsC4(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, const uint32_t* wq, int estr, unsigned char* dst, int tid)
 {
     const int* col = reinterpret_cast<const int*>(lds + OFF_COL); const int* row = reinterpret_cast<const int*>(lds + OFF_ROW);
     const unsigned char* tile = lds + OFF_TILE;
@@ -598,7 +594,7 @@ W8_HD unsigned rowsC4(const Args& a, const Box& b, int x0, int y0, const unsigne
 }
 
 template <int CN>
-W8_HD unsigned phaseC4(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, const uint32_t* wq, int estr, unsigned char* dst, int tid)
+MI355_HD unsigned phaseC4(const Args& a, const Box& b, int x0, int y0, const unsigned char* lds, const uint32_t* wq, int estr, unsigned char* dst, int tid)
 {
     if (b.cw == 0 && !(a.constBorder && b.ch == -1)) {                // nothing staged: every group is redone
         const int lane = tid & 63, x = x0 + (lane & (LX - 1)) * PX;
@@ -619,7 +615,7 @@ W8_HD unsigned phaseC4(const Args& a, const Box& b, int x0, int y0, const unsign
 #define W8_UNI(x) (x)
 #endif
 
-W8_HD int imad24(int x, int y, int z)
+MI355_HD int imad24(int x, int y, int z)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __mul24(x, y) + z;
@@ -629,7 +625,7 @@ W8_HD int imad24(int x, int y, int z)
 }
 
 // LDS address of the tile as an integer (folded into the row terms, so that the taps' addresses need no base add), and a dword pair read from such an address
-W8_HD uint32_t ldsBaseOf(const unsigned char* tile)
+MI355_HD uint32_t ldsBaseOf(const unsigned char* tile)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) unsigned char*)tile;
@@ -637,7 +633,7 @@ W8_HD uint32_t ldsBaseOf(const unsigned char* tile)
     (void)tile; return 0u;
 #endif
 }
-W8_HD void ldsPair(const unsigned char* tile, uint32_t addr, uint32_t& lo, uint32_t& hi)
+MI355_HD void ldsPair(const unsigned char* tile, uint32_t addr, uint32_t& lo, uint32_t& hi)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const __attribute__((address_space(3))) uint32_t* q = (const __attribute__((address_space(3))) uint32_t*)(uintptr_t)addr;
@@ -647,7 +643,7 @@ W8_HD void ldsPair(const unsigned char* tile, uint32_t addr, uint32_t& lo, uint3
 #endif
 }
 // acc with byte B replaced by (v >> SH) & 255: one SDWA shift on the device instead of shift + mask + or
-template <int B, int SH> W8_HD uint32_t shrIntoByte(uint32_t acc, uint32_t v)
+template <int B, int SH> MI355_HD uint32_t shrIntoByte(uint32_t acc, uint32_t v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     const uint32_t ten = (uint32_t)SH;
@@ -659,7 +655,7 @@ template <int B, int SH> W8_HD uint32_t shrIntoByte(uint32_t acc, uint32_t v)
     return (acc & ~(255u << (8 * B))) | (((v >> SH) & 255u) << (8 * B));
 #endif
 }
-template <int B> W8_HD uint32_t shr10IntoByte(uint32_t acc, uint32_t v) { return shrIntoByte<B, 10>(acc, v); }
+template <int B> MI355_HD uint32_t shr10IntoByte(uint32_t acc, uint32_t v) { return shrIntoByte<B, 10>(acc, v); }
 
 // A tile as the lean kernel sees it (uniform over the workgroup: scalar loads, scalar arithmetic):
 //   LEAN_INSIDE   every 2 x 2 footprint inside the source: plain staging, no per-pixel test
@@ -673,7 +669,7 @@ enum { LEAN_NO = 0, LEAN_INSIDE = 1, LEAN_RIM = 2, LEAN_OUTSIDE = 3 };
 struct LBox { int cx0, cy0, cw, ch, shift, kind; };
 
 template <int CN>
-W8_HD LBox leanClassify(const Args& a, int x0, int y0)
+MI355_HD LBox leanClassify(const Args& a, int x0, int y0)
 {
     LBox L = {0, 0, 0, 0, 0, LEAN_NO};
     if (!a.colT || !a.rowT || !a.leanLW) return L;
@@ -705,7 +701,7 @@ W8_HD LBox leanClassify(const Args& a, int x0, int y0)
 //              image's right edge is fetched from the row's last four bytes and shifted down (nothing is read past a row's last pixel)
 //   leanStore  the same indices into the tile
 template <int CN, int LW, int NR, bool RIM>
-W8_HD void leanLoad(const Args& a, const LBox& b, const unsigned char* src, int tid, uint32_t (&v)[NR])
+MI355_HD void leanLoad(const Args& a, const LBox& b, const unsigned char* src, int tid, uint32_t (&v)[NR])
 {
     constexpr int RPR = 256 / LW;
     const int sub = LW >= 64 ? W8_UNI(tid / LW) : tid / LW, c = tid % LW;
@@ -749,7 +745,7 @@ W8_HD void leanLoad(const Args& a, const LBox& b, const unsigned char* src, int 
     }
 }
 template <int CN, int LW, int NR>
-W8_HD void leanStore(const Args& a, const LBox& b, unsigned char* tile, int tid, const uint32_t (&v)[NR])
+MI355_HD void leanStore(const Args& a, const LBox& b, unsigned char* tile, int tid, const uint32_t (&v)[NR])
 {
     constexpr int RPR = 256 / LW;
     const int sub = LW >= 64 ? W8_UNI(tid / LW) : tid / LW, c = tid % LW;
@@ -769,7 +765,7 @@ W8_HD void leanStore(const Args& a, const LBox& b, unsigned char* tile, int tid,
 // the row terms of a lane's rows (the same for every tile of a tile row: loaded once per workgroup)
 struct LeanRowT { int rX[MAX_TH / ROWS_PER_STEP], rY[MAX_TH / ROWS_PER_STEP]; };
 template <int CN>
-W8_HD void leanRowTerms(const Args& a, int y0, int tid, LeanRowT& rt)
+MI355_HD void leanRowTerms(const Args& a, int y0, int tid, LeanRowT& rt)
 {
     const int wave = W8_UNI(tid >> 6), ly = (tid & 63) >> 5;
 #if defined(__HIPCC__)
@@ -784,7 +780,7 @@ W8_HD void leanRowTerms(const Args& a, int y0, int tid, LeanRowT& rt)
 
 // a tile wholly outside the source under BORDER_CONSTANT
 template <int CN>
-W8_HD void leanFill(const Args& a, int x0, int y0, unsigned char* dst, int tid)
+MI355_HD void leanFill(const Args& a, int x0, int y0, unsigned char* dst, int tid)
 {
     const int wave = W8_UNI(tid >> 6), lane = tid & 63, lx = lane & (LX - 1), ly = lane >> 5;
     const int x = x0 + lx * PX;
@@ -800,7 +796,7 @@ W8_HD void leanFill(const Args& a, int x0, int y0, unsigned char* dst, int tid)
     }
 }
 
-W8_HD uint32_t ldsOne(const unsigned char* tile, uint32_t addr)
+MI355_HD uint32_t ldsOne(const unsigned char* tile, uint32_t addr)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     (void)tile; return *(const __attribute__((address_space(3))) uint32_t*)(uintptr_t)addr;
@@ -811,7 +807,7 @@ W8_HD uint32_t ldsOne(const unsigned char* tile, uint32_t addr)
 
 // a lane = four horizontally adjacent destination pixels of one row per step, two rows per wave, eight rows per step of the workgroup
 template <int CN, bool RIM>
-W8_HD void leanRows(const Args& a, const LBox& b, int x0, int y0, const unsigned char* tile, unsigned char* dst, int tid, const LeanRowT& rt)
+MI355_HD void leanRows(const Args& a, const LBox& b, int x0, int y0, const unsigned char* tile, unsigned char* dst, int tid, const LeanRowT& rt)
 {
     const int wave = W8_UNI(tid >> 6), lane = tid & 63, lx = lane & (LX - 1), ly = lane >> 5;
     const int x = x0 + lx * PX;
@@ -898,9 +894,9 @@ inline void leanGeometry(Args& a, int cn);
 // An axis-aligned map needs no per-pixel coordinate arithmetic at all: a pixel's LDS offset is (row part) + (column part), both from per-call tables
 // (k_resize8_terms) -- colT: sx[dw] (clamped like the reference's xofs), a0 | a1 << 16 [dw]; rowT: y0[dh], y1[dh] (clamped rows), b0 << 12 [dh], b1 << 12 [dh].
 // (b (t >> 4)) >> 16 is one v_mul_hi_u32_u24 of (t & ~15) and (b << 12); the tap pair of a row is one v_perm_b32 into two 16-bit lanes + one v_dot2_u32_u16.
-W8_HD int floorF(float v) { const int i = (int)v; return i - ((float)i > v); }
-W8_HD int floorD(double v) { const int i = (int)v; return i - ((double)i > v); }
-W8_HD int rintF(float v)
+MI355_HD int floorF(float v) { const int i = (int)v; return i - ((float)i > v); }
+MI355_HD int floorD(double v) { const int i = (int)v; return i - ((double)i > v); }
+MI355_HD int rintF(float v)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __float2int_rn(v);
@@ -908,13 +904,13 @@ W8_HD int rintF(float v)
     return (int)__builtin_rintf(v);
 #endif
 }
-W8_HD void rzCoef(int d, double scale, double inv, int areaMode, int& s, float& f)       // resize.cpp:3897-3925 (linear) / :3870-3895 (INTER_AREA upscale)
+MI355_HD void rzCoef(int d, double scale, double inv, int areaMode, int& s, float& f)       // resize.cpp:3897-3925 (linear) / :3870-3895 (INTER_AREA upscale)
 {
     if (!areaMode) { f = (float)(dadd(dmul((double)d + 0.5, scale), -0.5)); s = floorF(f); f -= (float)s; }
     else { s = floorD(dmul((double)d, scale)); f = (float)dadd((double)(d + 1), -dmul((double)(s + 1), inv)); f = f <= 0 ? 0.f : f - (float)floorF(f); }
 }
-W8_HD int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
-W8_HD void rzColTerm(const Args& a, int dx, int& sx, uint32_t& a01)
+MI355_HD int sat16(int v) { return v < -32768 ? -32768 : v > 32767 ? 32767 : v; }
+MI355_HD void rzColTerm(const Args& a, int dx, int& sx, uint32_t& a01)
 {
     float fx; rzCoef(dx, a.rzScaleX, a.rzInvX, a.rzArea, sx, fx);
     if (sx < 0) { fx = 0; sx = 0; }
@@ -922,13 +918,13 @@ W8_HD void rzColTerm(const Args& a, int dx, int& sx, uint32_t& a01)
     const int a0 = sat16(rintF((1.f - fx) * 2048)), a1 = sat16(rintF(fx * 2048));
     a01 = (uint32_t)a0 | ((uint32_t)a1 << 16);
 }
-W8_HD void rzRowTerm(const Args& a, int dy, int& y0, int& y1, uint32_t& b0s, uint32_t& b1s)
+MI355_HD void rzRowTerm(const Args& a, int dy, int& y0, int& y1, uint32_t& b0s, uint32_t& b1s)
 {
     int sy; float fy; rzCoef(dy, a.rzScaleY, a.rzInvY, a.rzArea, sy, fy);
     y0 = sy >= 0 ? (sy < a.sh ? sy : a.sh - 1) : 0; y1 = sy + 1 >= 0 ? (sy + 1 < a.sh ? sy + 1 : a.sh - 1) : 0;
     b0s = (uint32_t)sat16(rintF((1.f - fy) * 2048)) << 12; b1s = (uint32_t)sat16(rintF(fy * 2048)) << 12;
 }
-W8_HD uint32_t mulhi24(uint32_t x, uint32_t y)                                           // bits 47:32 of the product of two 24-bit values
+MI355_HD uint32_t mulhi24(uint32_t x, uint32_t y)                                           // bits 47:32 of the product of two 24-bit values
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     uint32_t r; asm("v_mul_hi_u32_u24 %0, %1, %2" : "=v"(r) : "v"(x), "v"(y)); return r;
@@ -937,7 +933,7 @@ W8_HD uint32_t mulhi24(uint32_t x, uint32_t y)                                  
 #endif
 }
 // bytes i0 and i1 (0..7) of the 8 bytes (hi:lo) as two 16-bit lanes
-template <int I0, int I1> W8_HD uint32_t bytePair(uint32_t hi, uint32_t lo)
+template <int I0, int I1> MI355_HD uint32_t bytePair(uint32_t hi, uint32_t lo)
 {
 #if defined(__HIP_DEVICE_COMPILE__)
     return __builtin_amdgcn_perm(hi, lo, 0x0c000c00u | (uint32_t)I0 | ((uint32_t)I1 << 16));
@@ -949,7 +945,7 @@ template <int I0, int I1> W8_HD uint32_t bytePair(uint32_t hi, uint32_t lo)
 
 // the source box of a destination tile, from the tables (the clamped indices are monotone in the destination index); every position is inside the image
 template <int CN>
-W8_HD LBox rzClassify(const Args& a, int x0, int y0)
+MI355_HD LBox rzClassify(const Args& a, int x0, int y0)
 {
     LBox L = {0, 0, 0, 0, 0, LEAN_NO};
     if (!a.colT || !a.rowT || !a.leanLW) return L;
@@ -967,7 +963,7 @@ W8_HD LBox rzClassify(const Args& a, int x0, int y0)
 
 struct RzRowT { int r0[MAX_TH / ROWS_PER_STEP], dy[MAX_TH / ROWS_PER_STEP]; uint32_t b0[MAX_TH / ROWS_PER_STEP], b1[MAX_TH / ROWS_PER_STEP]; };
 template <int CN>
-W8_HD void rzRowTerms(const Args& a, int y0, int tid, RzRowT& rt)
+MI355_HD void rzRowTerms(const Args& a, int y0, int tid, RzRowT& rt)
 {
     const int wave = W8_UNI(tid >> 6), ly = (tid & 63) >> 5;
 #if defined(__HIPCC__)
@@ -982,7 +978,7 @@ W8_HD void rzRowTerms(const Args& a, int y0, int tid, RzRowT& rt)
 }
 
 template <int CN>
-W8_HD void rzRows(const Args& a, const LBox& b, int x0, int y0, const unsigned char* tile, unsigned char* dst, int tid, const RzRowT& rt)
+MI355_HD void rzRows(const Args& a, const LBox& b, int x0, int y0, const unsigned char* tile, unsigned char* dst, int tid, const RzRowT& rt)
 {
     const int wave = W8_UNI(tid >> 6), lane = tid & 63, lx = lane & (LX - 1), ly = lane >> 5;
     const int x = x0 + lx * PX;

@@ -1,8 +1,10 @@
-// ccl_emu.cpp -- opencv_amd/csrc/ccl_math.h (the arithmetic of the kernels of ccl.hip) compiled for the CPU with -ffp-contract=off: a whole labelling run serially
+// ccl_emu.cpp -- opencv_amd/csrc/ccl_math.h (the arithmetic of the kernels of ccl.hip) and unionfind.h (their find / unite loops, over its host memory policy)
+// compiled for the CPU with -ffp-contract=off: a whole labelling run serially
 // through the same lines and in the kernels' order -- row words from the four byte ballots of a tile row, run nodes, the links of every row to the row above
 // merged per tile, the vertical and horizontal seams, flatten, the flags in pixel or block key space, the two-level scan, rank + 1 -- and the statistics from runs
 // of equal label.  tests/test_ccl_cpu.py compares it with the numpy restatement (tests/ccl_restate.py).  Test infrastructure.
 #include "ccl_math.h"
+#include "unionfind.h"
 #include <algorithm>
 #include <cstddef>
 #include <cstdint>
@@ -10,19 +12,6 @@
 
 namespace {
 using ccl::BG; using ccl::STRIP_H; using ccl::TILE_W; using ccl::WORDS;
-
-uint32_t find(const std::vector<uint32_t>& P, uint32_t x) { for (;;) { const uint32_t p = P[x]; if (p >= x) return x; x = p; } }
-void unite(std::vector<uint32_t>& P, uint32_t a, uint32_t b)
-{
-    for (;;) {
-        a = find(P, a); b = find(P, b);
-        if (a == b) return;
-        if (a < b) std::swap(a, b);
-        const uint32_t old = P[a]; P[a] = std::min(old, b);                  // atomicMin
-        if (old == a) return;
-        a = old;
-    }
-}
 
 // k_ccl_strip for the tile at (x0, y0)
 void strip(const unsigned char* src, size_t sstep, int w, int h, int conn8, int x0, int y0, std::vector<uint32_t>& P)
@@ -40,6 +29,7 @@ void strip(const unsigned char* src, size_t sstep, int w, int h, int conn8, int 
         for (int j = 0; j < WORDS; j++)
             for (int lane = 0; lane < 64; lane++)
                 if ((wd[r][j] >> lane) & 1) { const int c = 64 * j + lane; if (ccl::tileRunStart(wd[r], j, lane) == c) par[r * TILE_W + c] = r * TILE_W + c; }
+    uf::PlainMem m{par.data()};
     for (int r = 1; r < rows; r++) {
         const uint64_t* W = wd[r]; const uint64_t* U = wd[r - 1];
         for (int j = 0; j < WORDS; j++) {
@@ -49,9 +39,9 @@ void strip(const unsigned char* src, size_t sstep, int w, int h, int conn8, int 
             for (int lane = 0; lane < 64; lane++) {
                 if (!(((direct | left | right) >> lane) & 1)) continue;
                 const uint32_t a = r * TILE_W + ccl::tileRunStart(W, j, lane);
-                if ((direct >> lane) & 1) unite(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, j, lane));
-                if ((left >> lane) & 1) { const int c = 64 * j + lane - 1; unite(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
-                if ((right >> lane) & 1) { const int c = 64 * j + lane + 1; unite(par, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
+                if ((direct >> lane) & 1) uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, j, lane));
+                if ((left >> lane) & 1) { const int c = 64 * j + lane - 1; uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
+                if ((right >> lane) & 1) { const int c = 64 * j + lane + 1; uf::unite(m, a, (r - 1) * TILE_W + ccl::tileRunStart(U, c >> 6, c & 63)); }
             }
         }
     }
@@ -62,7 +52,7 @@ void strip(const unsigned char* src, size_t sstep, int w, int h, int conn8, int 
                 if (x >= w) continue;
                 uint32_t p = BG;
                 if ((wd[r][j] >> lane) & 1) {
-                    const uint32_t root = find(par, r * TILE_W + ccl::tileRunStart(wd[r], j, lane));
+                    const uint32_t root = uf::find(m, r * TILE_W + ccl::tileRunStart(wd[r], j, lane));
                     p = (uint32_t)(y0 + (int)(root / TILE_W)) * (uint32_t)w + (uint32_t)(x0 + (int)(root % TILE_W));
                 }
                 P[(size_t)(y0 + r) * w + x] = p;
@@ -71,19 +61,21 @@ void strip(const unsigned char* src, size_t sstep, int w, int h, int conn8, int 
 
 void vseam(std::vector<uint32_t>& P, int w, int h, int conn8, int x)
 {
+    uf::PlainMem m{P.data()};
     for (int y = 0; y < h; y++) {
         const uint32_t b = (uint32_t)y * w + x, a = b - 1;
-        const bool fa = P[a] != BG, fb = P[b] != BG;
-        if (fa && fb) unite(P, a, b);
+        const bool fa = m.load(a) != BG, fb = m.load(b) != BG;
+        if (fa && fb) uf::unite(m, a, b);
         if (conn8 && y > 0) {
-            if (fa && P[b - w] != BG) unite(P, a, b - w);
-            if (fb && P[a - w] != BG) unite(P, b, a - w);
+            if (fa && m.load(b - w) != BG) uf::unite(m, a, b - w);
+            if (fb && m.load(a - w) != BG) uf::unite(m, b, a - w);
         }
     }
 }
 
 void hseam(std::vector<uint32_t>& P, int w, int conn8, int x0, int y)
 {
+    uf::PlainMem m{P.data()};
     const uint32_t* cur = &P[(size_t)y * w]; const uint32_t* up = cur - w;
     uint64_t W[WORDS + 2], U[WORDS + 2];
     W[0] = x0 > 0 && cur[x0 - 1] != BG ? ~uint64_t(0) : 0; U[0] = x0 > 0 && up[x0 - 1] != BG ? ~uint64_t(0) : 0;
@@ -102,9 +94,9 @@ void hseam(std::vector<uint32_t>& P, int w, int conn8, int x0, int y)
         const uint64_t left = conn8 ? ccl::linkLeft(W[j], U[j], Wl, Ul) : 0, right = conn8 ? ccl::linkRight(W[j], U[j], Wr, Ur) : 0;
         for (int lane = 0; lane < 64; lane++) {
             const uint32_t a = (uint32_t)y * w + x0 + 64 * (j - 1) + lane;
-            if ((direct >> lane) & 1) unite(P, a, a - w);
-            if ((left >> lane) & 1) unite(P, a, a - w - 1);
-            if ((right >> lane) & 1) unite(P, a, a - w + 1);
+            if ((direct >> lane) & 1) uf::unite(m, a, a - w);
+            if ((left >> lane) & 1) uf::unite(m, a, a - w - 1);
+            if ((right >> lane) & 1) uf::unite(m, a, a - w + 1);
         }
     }
 }
@@ -125,11 +117,12 @@ extern "C" int emu_ccl(const unsigned char* src, size_t sstep, int w, int h, int
     const uint32_t nW = (npos + 63) >> 6, nchunk = (nW + ccl::CHUNK_WORDS - 1) / ccl::CHUNK_WORDS;
     std::vector<uint64_t> B(nW, 0);
     std::vector<uint32_t> K(order == ccl::ORDER_BLOCK ? nblocks : 0, BG), wpre(nW), chunk(nchunk);
+    uf::PlainMem m{P.data()};
     for (int y = 0; y < h; y++)
         for (int x = 0; x < w; x++) {
             const uint32_t g = (uint32_t)y * w + x;
             if (P[g] == BG) continue;
-            const uint32_t r = find(P, P[g]);
+            const uint32_t r = uf::find(m, m.load(g));
             P[g] = r;
             if (order == ccl::ORDER_PIXEL) { if (r == g) B[g >> 6] |= uint64_t(1) << (g & 63); }
             else if (r >= (uint32_t)(y & ~1) * w && ((x & 63) == 0 || P[g - 1] == BG)) {       // the first pixel of a run inside its 64-column word

@@ -1,4 +1,5 @@
-// speckle_emu.cpp -- opencv_amd/csrc/speckle_math.h (the pieces of the kernels of speckle.hip) compiled for the CPU, and the whole kernel sequence of either path
+// speckle_emu.cpp -- opencv_amd/csrc/speckle_math.h (the pieces of the kernels of speckle.hip) and unionfind.h (their find / unite loops, over its host memory
+// policy) compiled for the CPU, and the whole kernel sequence of either path
 // emulated serially around them -- k_spk_init / k_spk_link / k_spk_count, or k_spk_tile (ballots, bit planes, runs, the merge in LDS) / k_spk_vseam / k_spk_hseam /
 // k_spk_count_runs, then k_spk_erase -- for tests/test_speckle_cpu.py to hold against tests/speckle_restate.py bit for bit.  `stride` permutes the order in which the
 // emulated threads of a kernel run (thread i runs as (i * stride) mod n, gcd(stride, n) = 1): the image must not depend on it.
@@ -8,11 +9,7 @@
 
 namespace {
 
-struct PlainMem {
-    uint32_t* P;
-    uint32_t load(uint32_t i) const { return P[i]; }
-    uint32_t amin(uint32_t i, uint32_t v) const { const uint32_t old = P[i]; if (v < old) P[i] = v; return old; }
-};
+using uf::PlainMem;
 
 struct Img {
     uint8_t* p; size_t step; int w, h, is16;

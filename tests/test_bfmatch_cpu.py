@@ -10,6 +10,7 @@ import numpy as np
 import pytest
 
 import bfmatch_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NORMS_8U = (R.NORM_HAMMING, R.NORM_HAMMING2)
@@ -84,13 +85,8 @@ def test_known_answers():
 
 @functools.lru_cache(maxsize=1)
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "bfmatch_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "bfmatch_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libbfmatch_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        # the library's own flag: every product and sum is rounded on its own
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    # the library's own flag: every product and sum is rounded on its own
+    lib = emubuild.load("bfmatch_emu.cpp", "libbfmatch_emu.so", ["-ffp-contract=off"])
     i32, u32, vp, u64, f32 = ctypes.c_int, ctypes.c_uint, ctypes.c_void_p, ctypes.c_ulonglong, ctypes.c_float
     lib.emu_bf_distance.argtypes, lib.emu_bf_distance.restype = [i32, i32, vp, vp, i32], f32
     lib.emu_bf_hamming_words.argtypes, lib.emu_bf_hamming_words.restype = [i32, vp, vp, i32], u32

@@ -3,12 +3,12 @@ numpy.histogramdd where both definitions coincide; the lines of opencv_amd/csrc/
 and the refusals of the four mi355cv_calcHist* / mi355cv_calcBackProject* entries that come before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import calchist_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OK, NOT_IMPLEMENTED = 0, 1
@@ -132,17 +132,12 @@ def test_restatement_equals_histogramdd_where_the_definitions_coincide():
 # ---- calchist_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "calchist_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "calchist_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libcalchist_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        # -ffp-contract=fast, and -mfma where this CPU has it, on purpose: the header itself must make contraction impossible
-        try:
-            fma = ["-mfma"] if " fma " in open("/proc/cpuinfo").read() else []
-        except OSError:
-            fma = []
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=fast"] + fma + ["-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    # -ffp-contract=fast, and -mfma where this CPU has it, on purpose: the header itself must make contraction impossible
+    try:
+        fma = ["-mfma"] if " fma " in open("/proc/cpuinfo").read() else []
+    except OSError:
+        fma = []
+    lib = emubuild.load("calchist_emu.cpp", "libcalchist_emu.so", ["-ffp-contract=fast"] + fma)
     i32, vp, f32, dbl = ctypes.c_int, ctypes.c_void_p, ctypes.c_float, ctypes.c_double
     lib.emu_calchist_table.argtypes = [i32, i32, i32, vp, i32, vp]
     lib.emu_calchist_bins_f32.argtypes = [vp, i32, i32, f32, f32, vp]

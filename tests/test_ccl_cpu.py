@@ -3,12 +3,12 @@ compiled for the host (tests/hostemu/ccl_emu.cpp) against that restatement, and 
 before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import ccl_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_IMPLEMENTED = 1
@@ -108,12 +108,7 @@ def test_block_order_is_the_permutation_by_block_key():
 # ---- ccl_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "ccl_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "ccl_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libccl_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("ccl_emu.cpp", "libccl_emu.so", ["-ffp-contract=off"])
     u64, i32 = ctypes.c_uint64, ctypes.c_int
     lib.emu_ccl.restype = i32
     lib.emu_ccl.argtypes = [ctypes.c_void_p, ctypes.c_size_t, i32, i32, i32, i32, ctypes.c_void_p]

@@ -2,12 +2,12 @@
 (tests/hostemu/clahe_emu.cpp) against that restatement, and the argument refusals of mi355cv_clahe / mi355cv_claheBatch that come before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import clahe_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_IMPLEMENTED = 1
@@ -38,12 +38,7 @@ def test_padding_rule():
 # ---- clahe_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "clahe_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "clahe_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libclahe_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("clahe_emu.cpp", "libclahe_emu.so", ["-ffp-contract=off"])
     lib.emu_clahe_lut.restype = None
     lib.emu_clahe_lut.argtypes = [ctypes.c_void_p, ctypes.c_int, ctypes.c_int, ctypes.c_float, ctypes.c_int, ctypes.c_void_p]
     lib.emu_clahe.restype = ctypes.c_int

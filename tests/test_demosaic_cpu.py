@@ -3,12 +3,12 @@ the host (tests/hostemu/demosaic_emu.cpp, scalar and packed) against that restat
 come before any device is touched, and the constants of the Python surface."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import demosaic_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_IMPLEMENTED = 1
@@ -37,12 +37,7 @@ def test_pattern_is_relative_to_the_origin():
 # ---- demosaic_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "demosaic_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "demosaic_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libdemosaic_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("demosaic_emu.cpp", "libdemosaic_emu.so", ["-ffp-contract=off"])
     lib.emu_demosaic.restype = ctypes.c_int
     lib.emu_demosaic.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t] + [ctypes.c_int] * 5
     lib.emu_demosaic_packed.restype = ctypes.c_int

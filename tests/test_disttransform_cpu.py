@@ -3,12 +3,12 @@ opencv_amd/csrc/disttransform_math.h compiled for the host (tests/hostemu/disttr
 mi355cv_distanceTransform / mi355cv_distanceTransformBatch that come before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
 import disttransform_restate as R
+import emubuild
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 NOT_IMPLEMENTED = 1
@@ -94,12 +94,7 @@ def test_restatement_against_scipy():
 # ---- disttransform_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "disttransform_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "disttransform_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libdisttransform_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("disttransform_emu.cpp", "libdisttransform_emu.so", ["-ffp-contract=off"])
     lib.emu_disttransform.restype = ctypes.c_int
     lib.emu_disttransform.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.emu_dist_columns.restype = ctypes.c_int

@@ -6,11 +6,11 @@ device is touched, and the four limits.  Two tests print, without asserting a bo
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import farneback_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -183,13 +183,8 @@ def test_report_float32_against_float64():
 # ---- farneback_math.h compiled for the host
 @functools.lru_cache(maxsize=None)
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "farneback_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "farneback_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libfarneback_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        # the library's own flag: every product and sum is rounded on its own
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    # the library's own flag: every product and sum is rounded on its own
+    lib = emubuild.load("farneback_emu.cpp", "libfarneback_emu.so", ["-ffp-contract=off"])
     i32, vp, f64 = ctypes.c_int, ctypes.c_void_p, ctypes.c_double
     lib.emu_fb_limit.argtypes = [i32]
     lib.emu_fb_gaussian_taps.argtypes = [i32, f64, vp]

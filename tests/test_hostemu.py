@@ -8,6 +8,7 @@ import sys
 import numpy as np
 import pytest
 
+import emubuild
 import orc as o
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -15,12 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "hostemu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "libhostemu.so")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "hsv_math.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    return ctypes.CDLL(out)
+    return emubuild.load("hostemu.cpp", "libhostemu.so", ["-ffp-contract=off"])
 
 
 @pytest.mark.parametrize("code", [54, 55, 70, 71])
@@ -68,12 +64,7 @@ def test_hls_arithmetic_exhaustive(emu, code):
 # ---- the LDS-tile warp kernel (opencv_amd/csrc/warp8.h): plan, staging, box logic and per-pixel arithmetic run thread by thread on the CPU --------
 @pytest.fixture(scope="module")
 def emu8():
-    src = os.path.join(ROOT, "tests", "hostemu", "warp8_emu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "libwarp8emu.so")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "warp8.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("warp8_emu.cpp", "libwarp8emu.so", ["-ffp-contract=off"])
     lib.emu_warp8.restype = ctypes.c_int
     return lib
 
@@ -226,12 +217,7 @@ def test_resize8_lean_tiles_on_the_cpu(emu8):
 # ---- cv::ORB (opencv_amd/csrc/orb_math.h: per-lane arithmetic of the kernels; orb_host.h: the host control flow of orb.hip) ------------------------------
 @pytest.fixture(scope="module")
 def emuorb():
-    src = os.path.join(ROOT, "tests", "hostemu", "orb_emu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "liborbemu.so")
-    hdrs = [os.path.join(ROOT, "opencv_amd", "csrc", f) for f in ("orb_math.h", "orb_host.h", "orb_pattern.inc")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("orb_emu.cpp", "liborbemu.so", ["-ffp-contract=off"])
     lib.emu_orb_border.restype = ctypes.c_long
     lib.emu_orb_fastAtan2.restype = ctypes.c_float
     lib.emu_orb_fastAtan2.argtypes = [ctypes.c_float, ctypes.c_float]
@@ -386,12 +372,7 @@ def test_orb_host_tables_and_culls(emuorb):
 # ---- the 5 x 5 median on columns sorted once per position (opencv_amd/csrc/median5_math.h, networks of median_net.h) ---------------------------------
 @pytest.fixture(scope="module")
 def emumed():
-    src = os.path.join(ROOT, "tests", "hostemu", "median5_emu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "libmedian5emu.so")
-    hdrs = [os.path.join(ROOT, "opencv_amd", "csrc", f) for f in ("median5_math.h", "median_net.h")]
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(f) for f in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    return ctypes.CDLL(out)
+    return emubuild.load("median5_emu.cpp", "libmedian5emu.so", ["-Wno-unknown-pragmas"])
 
 
 @pytest.mark.parametrize("cn", [1, 3, 4])
@@ -413,12 +394,7 @@ def test_median5_sorted_columns_lines(emumed, cn):
 # ---- CV_8U cubic / Lanczos resize on 256 x 16 tiles with staged source bytes (opencv_amd/csrc/resize_tab8.h) ---------------------------------------------
 @pytest.fixture(scope="module")
 def emurt8():
-    src = os.path.join(ROOT, "tests", "hostemu", "resize_tab8_emu.cpp")
-    out = os.path.join(ROOT, "tests", "hostemu", "libresizetab8emu.so")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "resize_tab8.h")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-Wno-unknown-pragmas", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    return ctypes.CDLL(out)
+    return emubuild.load("resize_tab8_emu.cpp", "libresizetab8emu.so", ["-ffp-contract=off", "-Wno-unknown-pragmas"])
 
 
 @pytest.mark.parametrize("interp", [2, 4])

@@ -4,11 +4,11 @@ mi355cv_houghLines* entries that come before any device is touched."""
 import ctypes
 import math
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import hough_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -100,12 +100,7 @@ def test_geometry_edge_cases():
 # ---- hough_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "hough_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "hough_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libhough_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("hough_emu.cpp", "libhough_emu.so", ["-ffp-contract=off"])
     i32, dbl, vp = ctypes.c_int, ctypes.c_double, ctypes.c_void_p
     lib.emu_hough_geometry.argtypes = [i32, i32, dbl, dbl, dbl, dbl, ctypes.POINTER(i32), ctypes.POINTER(i32)]
     lib.emu_hough_table.argtypes = [i32, i32, dbl, dbl, dbl, dbl, vp, vp]

@@ -3,11 +3,11 @@ opencv_amd/csrc/minmax_math.h compiled for the host (tests/hostemu/minmax_emu.cp
 come before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import minmax_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -85,12 +85,7 @@ def test_restatements_agree_on_small_frames_full_of_ties():
 # ---- minmax_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "minmax_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "minmax_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libminmax_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("minmax_emu.cpp", "libminmax_emu.so", ["-ffp-contract=off"])
     i32, u32, u64, vp = ctypes.c_int, ctypes.c_uint32, ctypes.c_uint64, ctypes.c_void_p
     lib.emu_minmax_keys.argtypes = [i32, vp, i32, vp, vp]
     lib.emu_minmax_values.argtypes = [i32, vp, i32, vp]

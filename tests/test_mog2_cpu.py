@@ -4,11 +4,11 @@ against them bit for bit, the refusals of the mi355cv_mog2* entries that come be
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import mog2_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -122,13 +122,8 @@ def test_batch_rule_reinitialises_once():
 
 # ---- mog2_math.h compiled for the host
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "mog2_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "mog2_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libmog2_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        # the library's own flag: every product and sum is rounded on its own
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    # the library's own flag: every product and sum is rounded on its own
+    lib = emubuild.load("mog2_emu.cpp", "libmog2_emu.so", ["-ffp-contract=off"])
     i32, vp, f32 = ctypes.c_int, ctypes.c_void_p, ctypes.c_float
     lib.emu_mog2_apply.argtypes = [i32, i32, vp, i32, i32, vp, vp, vp, vp, i32, i32, f32, vp]
     lib.emu_mog2_background.argtypes = [i32, i32, i32, vp, vp, vp, vp, vp]

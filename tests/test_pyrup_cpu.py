@@ -2,11 +2,11 @@
 (tests/hostemu/pyrup_emu.cpp) against that restatement, and the argument refusals of mi355cv_pyrup / mi355cv_pyrupBatch that come before any device is touched."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import orc
 import pyrup_restate as R
 
@@ -38,12 +38,7 @@ def test_known_answers():
 # ---- pyrup_math.h on the host
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "pyrup_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "pyrup_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libpyrup_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("pyrup_emu.cpp", "libpyrup_emu.so", ["-ffp-contract=off"])
     lib.emu_pyrup.restype = ctypes.c_int
     lib.emu_pyrup.argtypes = [ctypes.c_void_p, ctypes.c_size_t, ctypes.c_void_p, ctypes.c_size_t, ctypes.c_int, ctypes.c_int, ctypes.c_int, ctypes.c_int]
     lib.emu_pyrup_packed.restype = ctypes.c_int

@@ -4,11 +4,11 @@ decisions (mi355cv_sepFilterInit + mi355cv_sepFilterDescribe: engine, integer ta
 tests/test_oracle_smooth.py pin to the reference.  Bit for bit, floats included: the kernel keeps the order of every multiply-add chain."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import orc as o
 from opencv_amd import _lib
 
@@ -20,12 +20,7 @@ NPD = {0: np.uint8, 2: np.uint16, 3: np.int16, 5: np.float32}
 
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "seplong_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "seplong_body.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libseplong_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("seplong_emu.cpp", "libseplong_emu.so", ["-ffp-contract=off"])
     lib.emu_seplong.restype = ctypes.c_int
     return lib
 

@@ -4,11 +4,11 @@ uploads -- against the restatement of fixedSmoothInvoker / boxFilter that tests/
 outside the image hold garbage in the replay (their weight must be zero).  The matrix instruction's lane map itself is pinned by tests/test_sepmx_gpu.py."""
 import ctypes
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import orc as o
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -16,12 +16,7 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 @pytest.fixture(scope="module")
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "sepmx_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "sepmx_body.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libsepmx_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-ffp-contract=off", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("sepmx_emu.cpp", "libsepmx_emu.so", ["-ffp-contract=off"])
     lib.emu_sepmx.restype = ctypes.c_int
     return lib
 

@@ -4,11 +4,11 @@ the restatement, the refusals of the mi355cv_filterSpeckles* entries that come b
 import ctypes
 import functools
 import os
-import subprocess
 
 import numpy as np
 import pytest
 
+import emubuild
 import speckle_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -95,12 +95,7 @@ def test_serpentine_and_spiral_are_one_component():
 
 @functools.lru_cache(maxsize=1)
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "speckle_emu.cpp")
-    hdrs = [os.path.join(ROOT, "opencv_amd", "csrc", h) for h in ("speckle_math.h", "ccl_math.h")]
-    out = os.path.join(ROOT, "tests", "hostemu", "libspeckle_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(p) for p in [src] + hdrs):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("speckle_emu.cpp", "libspeckle_emu.so")
     i32, vp = ctypes.c_int, ctypes.c_void_p
     lib.emu_spk_filter.argtypes = [vp, ctypes.c_size_t, i32, i32, i32, i32, i32, i32, i32, i32]
     lib.emu_spk_filter.restype = None

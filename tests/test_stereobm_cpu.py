@@ -9,6 +9,7 @@ import subprocess
 import numpy as np
 import pytest
 
+import emubuild
 import stereobm_restate as R
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -99,12 +100,7 @@ def test_the_smooth_pairs_meet_the_conditions_of_the_gpu_test_on_the_cpu():
 
 @functools.lru_cache(maxsize=1)
 def emu():
-    src = os.path.join(ROOT, "tests", "hostemu", "stereobm_emu.cpp")
-    hdr = os.path.join(ROOT, "opencv_amd", "csrc", "stereobm_math.h")
-    out = os.path.join(ROOT, "tests", "hostemu", "libstereobm_emu.so")
-    if not os.path.exists(out) or os.path.getmtime(out) < max(os.path.getmtime(src), os.path.getmtime(hdr)):
-        subprocess.check_call(["g++", "-O2", "-std=c++17", "-fPIC", "-shared", "-I" + os.path.join(ROOT, "opencv_amd", "csrc"), src, "-o", out])
-    lib = ctypes.CDLL(out)
+    lib = emubuild.load("stereobm_emu.cpp", "libstereobm_emu.so")
     i32, vp = ctypes.c_int, ctypes.c_void_p
     lib.emu_sbm_geom.argtypes = [i32, i32, i32, vp]
     lib.emu_sbm_prefilter.argtypes = [vp, i32, i32, i32, vp]
