@@ -187,7 +187,15 @@ MI355CV_API int mi355cv_sepSmoothFixedU8(const mi355cv_uchar* src_data, size_t s
 
 /* Batched form (frames are independent units): `nframes` images of identical
  * geometry, frame f at src_data + f*src_frame_stride; one launch, grid-z = frame.  Host-resident batches: the chunked two-buffer pipeline (see the
- * batch section below). */
+ * batch section below).
+ *
+ * Frame counts.  grid.y and grid.z of a launch hold 65535 workgroups, and most batch kernels take their frame from blockIdx.z.  Every *Batch entry therefore does one
+ * of two things with more than 65535 frames, and never hands the runtime a larger grid: it SERVES the batch -- in consecutive launches or calls of at most 65535
+ * frames (mi355cv_resizeBatch, mi355cv_warpAffineBatch, mi355cv_warpPerspectiveBatch, mi355cv_cvtBGRtoGrayBatch, mi355cv_pyrdownBatch, mi355cv_buildPyramidBatch,
+ * mi355cv_cornerHarrisBatch, mi355cv_integralBatch, mi355cv_matchTemplateBatch, mi355cv_demosaicBatch, mi355cv_pyrupBatch, the Gaussian entries), in groups its
+ * scratch budget sets (CLAHE, connected components with CV_32S labels, distanceTransform), from a 1-D grid, or frame by frame (threshold, Sobel, box, separable and
+ * 2-D filters) -- or it DECLINES with the bound in the reason and writes nothing: minMaxLoc, calcHist, calcBackProject, stereoBM, filterSpeckles, HoughLines,
+ * connected components with CV_16U labels and their statistics, bfKnnMatchBatch (pairs), and a Gaussian of more than 33 taps. */
 /* the same for any sigma (the Q8.8 taps cv::GaussianBlur computes for CV_8U, smooth.dispatch.cpp:658-724), device-resident frames only, kernel sizes odd and at most
  * mi355cv_limit("gauss8u_max_ksize") */
 MI355CV_API int mi355cv_gaussianBlurBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride,

@@ -189,6 +189,10 @@ MI355CV_API int mi355cv_cvtBGRtoGrayBatch(const uchar* src_data, size_t src_step
         return runHostBatch("cvtBGRtoGrayBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_cvtBGRtoGrayBatch(s, ss, sf, d, ds, df, nf, width, height, depth, scn, swapBlue); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_cvtBGRtoGrayBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, dst_data + f0 * dst_frame_stride, dst_step, dst_frame_stride, nf,
+                                             width, height, depth, scn, swapBlue); });
     return runBgr2Gray("cvtBGRtoGrayBatch", src_data, src_step, nframes == 1 ? 0 : src_frame_stride, dst_data, dst_step,
                        nframes == 1 ? 0 : dst_frame_stride, nframes, width, height, depth, scn, swapBlue != 0);
 }

@@ -1022,6 +1022,10 @@ MI355CV_API int mi355cv_pyrdownBatch(const uchar* src_data, size_t src_step, siz
         return runHostBatch("pyrdownBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_pyrdownBatch(s, ss, sf, src_width, src_height, d, ds, df, dst_width, dst_height, nf, depth, cn, border_type); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                                                                      // the kernels take the frame from blockIdx.z
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_pyrdownBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, src_width, src_height, dst_data + f0 * dst_frame_stride, dst_step,
+                                        dst_frame_stride, dst_width, dst_height, nf, depth, cn, border_type); });
     return runPyrDown("pyrdownBatch", src_data, src_step, nframes == 1 ? 0 : src_frame_stride, src_width, src_height, dst_data, dst_step,
                       nframes == 1 ? 0 : dst_frame_stride, dst_width, dst_height, nframes, depth, cn, 0, 0, 0, 0, border_type);
 }
@@ -1068,6 +1072,12 @@ MI355CV_API int mi355cv_buildPyramidBatch(const uchar* src_data, size_t src_step
         return runHostBatchN("buildPyramidBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* const* d, const size_t* ds, const size_t* df, int nf) {
             return mi355cv_buildPyramidBatch(s, ss, sf, width, height, depth, cn, d, ds, df, maxlevel, nf, border_type); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z (k_pyr3: blockIdx.y)
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            uchar* d[30];
+            for (int l = 0; l < maxlevel; l++) d[l] = dst_data[l] ? dst_data[l] + f0 * dst_frame_stride[l] : nullptr;
+            return mi355cv_buildPyramidBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, width, height, depth, cn, d, dst_step, dst_frame_stride, maxlevel, nf,
+                                             border_type); });
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice());
     if (!isDevicePtr(src_data)) return setError(MI355CV_NOT_IMPLEMENTED, "buildPyramidBatch: frames and levels all in device memory, or all in host memory");
@@ -1108,6 +1118,10 @@ MI355CV_API int mi355cv_cornerHarrisBatch(const uchar* src_data, size_t src_step
         return runHostBatch("cornerHarrisBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_cornerHarrisBatch(s, ss, sf, d, ds, df, nf, width, height, src_type, blockSize, ksize, k, borderType); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z; the scratch is per call
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_cornerHarrisBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, dst_data + f0 * dst_frame_stride, dst_step, dst_frame_stride, nf,
+                                             width, height, src_type, blockSize, ksize, k, borderType); });
     return runCorner("cornerHarrisBatch", src_data, src_step, nframes == 1 ? 0 : src_frame_stride, dst_data, dst_step,
                      nframes == 1 ? 0 : dst_frame_stride, nframes, width, height, src_type, blockSize, ksize, k, borderType, true);
 }

@@ -181,6 +181,19 @@ inline int divUp(int a, int b) { return (a + b - 1) / b; }
 inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }                                                  // b bytes rounded up to 256: the start of the next array in a scratch block, a staged row's pitch
 inline size_t span(size_t step, int rows, size_t rowBytes) { return (size_t)(rows - 1) * step + rowBytes; }          // bytes from the first byte of an image to one past its last
 
+// grid.y and grid.z hold 65535 workgroups each, and most batch kernels take their frame from blockIdx.z (include/mi355cv.h, "Frame counts"): a longer batch of
+// device-resident frames is served in slices of at most MAX_GRID_FRAMES frames -- run(f0, nf) is the entry's own path on frames [f0, f0 + nf) -- or declined by the
+// entries that say so in their argument checks (MI355_DECLINE_IF(nframes > 65535)); no launch ever gets a grid dimension above 65535
+constexpr int MAX_GRID_FRAMES = 65535;
+template <class Run> inline int sliceFrames(int nframes, Run run)
+{
+    for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_FRAMES) {
+        const int rc = run((size_t)f0, nframes - f0 < MAX_GRID_FRAMES ? nframes - f0 : MAX_GRID_FRAMES);
+        if (rc != MI355CV_OK) return rc;
+    }
+    return MI355CV_OK;
+}
+
 #if defined(__HIPCC__)
 // Workgroups of a 1-D grid go to the 8 XCDs round-robin (id % 8), each XCD behind its own L2.  A kernel whose neighbouring workgroups write the two halves of
 // the same 128-byte lines (rows whose pitch is not a multiple of the line: cv::integral's (W + 1)-element rows) sends every such line to memory twice as a

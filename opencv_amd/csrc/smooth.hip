@@ -694,8 +694,11 @@ void launchRoll(const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_
     }
     seg = divUp(seg, KS) * KS;
     if (seg > H) seg = divUp(H, KS) * KS;
-    dim3 grid(gx, divUp(H, seg), nframes);
-    hipLaunchKernelGGL((k_binomial_roll<KS, CN>), grid, dim3(256), 0, st, s, ss, sf, d, ds, df, W, H, nchunks, seg, border);
+    for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_FRAMES) {                          // the frame is blockIdx.z
+        dim3 grid(gx, divUp(H, seg), std::min(MAX_GRID_FRAMES, nframes - f0));
+        hipLaunchKernelGGL((k_binomial_roll<KS, CN>), grid, dim3(256), 0, st, s + (size_t)f0 * sf, ss, sf, d + (size_t)f0 * df, ds, df, W, H, nchunks, seg, border);
+    }
+    noteKernel("k_binomial_roll<%d,%d> grid=%dx%dx%d x256 seg=%d rows, %d launch(es)", KS, CN, gx, divUp(H, seg), std::min(MAX_GRID_FRAMES, nframes), seg, divUp(nframes, MAX_GRID_FRAMES));
 }
 
 bool rollEligible(const uchar* s, size_t ss, size_t sf, const uchar* d, size_t ds, size_t df, int W, int H, int cn, int ks)
@@ -778,13 +781,17 @@ int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
                    return seplongRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, MI355CV_8U, MI355CV_8U, mL + W + mR, mT + H + mB, mL, mT, border, t, st); }()) {
     } else {
         // taps that can saturate the reference's fixed-point types (never cv::GaussianBlur's own: they sum to 256), or MI355CV_SMOOTH_GENERIC=1: one thread per byte, <= 33 taps
+        MI355_DECLINE_IF((nx > 33 || ny > 33) && nframes > MAX_GRID_FRAMES);         // sepmxRun and seplongRun take up to 65535 frames, this kernel up to 33 taps
         if (nx > 33 || ny > 33) return MI355_DECLINED("Q8.8 taps that sum beyond 256 with more than 33 of them");
         FixedTaps t;
         t.nx = nx; t.ny = ny;
         for (int i = 0; i < 33; i++) { t.kx[i] = i < nx ? kx[i] : 0; t.ky[i] = i < ny ? ky[i] : 0; }
-        dim3 grid(divUp(W * cn, 64), divUp(H, 4), nframes);
-        hipLaunchKernelGGL(k_sepfixed_generic, grid, dim3(256), 0, st, dsrc, dss, sframe, ddst, dds, dframe,
-                           W, H, cn, mL, mT, mR, mB, border, t);
+        for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_FRAMES) {                      // the frame is blockIdx.z
+            dim3 grid(divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes - f0));
+            hipLaunchKernelGGL(k_sepfixed_generic, grid, dim3(256), 0, st, dsrc + (size_t)f0 * sframe, dss, sframe, ddst + (size_t)f0 * dframe, dds, dframe,
+                               W, H, cn, mL, mT, mR, mB, border, t);
+        }
+        noteKernel("k_sepfixed_generic grid=%dx%dx%d x256, %d launch(es)", divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes), divUp(nframes, MAX_GRID_FRAMES));
     }
     return stg.finish(entry);
 }

@@ -1583,6 +1583,10 @@ MI355CV_API int mi355cv_matchTemplateBatch(const uchar* img_data, size_t img_ste
         return runHostBatch("matchTemplateBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return runMatch("matchTemplateBatch", s, ss, nf == 1 ? 0 : sf, nf, img_width, img_height, templ_data, templ_step, templ_width, templ_height, type, d, ds, nf == 1 ? 0 : df, method); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z; the scratch is per call
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_matchTemplateBatch(img_data + f0 * img_frame_stride, img_step, img_frame_stride, nf, img_width, img_height, templ_data, templ_step, templ_width,
+                                              templ_height, type, result_data + f0 * result_frame_stride, result_step, result_frame_stride, method); });
     return runMatch("matchTemplateBatch", img_data, img_step, nframes == 1 ? 0 : img_frame_stride, nframes, img_width, img_height, templ_data, templ_step,
                     templ_width, templ_height, type, result_data, result_step, nframes == 1 ? 0 : result_frame_stride, method);
 }
@@ -1671,6 +1675,10 @@ MI355CV_API int mi355cv_integralBatch(const uchar* src_data, size_t src_step, si
     const size_t se = sdepth == D32S ? 4 : 8;
     MI355_DECLINE_IF((sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8))));
     MI355_DECLINE_IF(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z; the carries are scratch per call
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_integralBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, sum_data + f0 * sum_frame_stride, sum_step, sum_frame_stride,
+                                         sqsum_data ? sqsum_data + f0 * sqsum_frame_stride : nullptr, sqsum_step, sqsum_frame_stride, nf, width, height, sdepth); });
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(sum_data) || (sqsum_data && !isDevicePtr(sqsum_data)))
         return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: device-resident frames only");

@@ -207,16 +207,21 @@ extern "C" MI355CV_API int mi355cv_threshold(const uchar* src_data, size_t src_s
     const int epv = 16 / e;
     const int vec = ((((uintptr_t)ds | dss | (uintptr_t)dd | dds) & 15) == 0 && n % epv == 0) ? 1 : 0;
     const int perRow = vec ? n / epv : divUp(n, epv);
-    dim3 grid(divUp(perRow, 64), divUp(height, 4));
     hipStream_t st = stream();
-#define TH(T_, TY_) hipLaunchKernelGGL((k_threshold<T_, TY_>), grid, dim3(256), 0, st, ds, dss, dd, dds, n, height, (T_)thresh, (T_)maxValue, vec)
+    // grid.y holds 65535: a taller image (thresholdBatch's frames that lie back to back are one) takes one launch per 4 * 65535 rows
+    constexpr int SLICE = 4 * MAX_GRID_FRAMES;
+#define TH(T_, TY_) hipLaunchKernelGGL((k_threshold<T_, TY_>), grid, dim3(256), 0, st, ds + (size_t)y0 * dss, dss, dd + (size_t)y0 * dds, dds, n, rows, (T_)thresh, (T_)maxValue, vec)
 #define THT(T_) do { switch (thresholdType) { case 0: TH(T_, 0); break; case 1: TH(T_, 1); break; case 2: TH(T_, 2); break; case 3: TH(T_, 3); break; default: TH(T_, 4); } } while (0)
-    switch (depth) {
-    case D8U:  THT(uchar); break;
-    case D16U: THT(unsigned short); break;
-    case D16S: THT(short); break;
-    case D64F: THT(double); break;
-    default:   THT(float); break;
+    for (int y0 = 0; y0 < height; y0 += SLICE) {
+        const int rows = height - y0 < SLICE ? height - y0 : SLICE;
+        const dim3 grid(divUp(perRow, 64), divUp(rows, 4));
+        switch (depth) {
+        case D8U:  THT(uchar); break;
+        case D16U: THT(unsigned short); break;
+        case D16S: THT(short); break;
+        case D64F: THT(double); break;
+        default:   THT(float); break;
+        }
     }
 #undef THT
 #undef TH

@@ -3009,6 +3009,10 @@ MI355CV_API int mi355cv_resizeBatch(int src_type, const uchar* src_data, size_t 
         return runHostBatch("resizeBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_resizeBatch(src_type, s, ss, sf, src_width, src_height, d, ds, df, dst_width, dst_height, nf, inv_scale_x, inv_scale_y, interpolation); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                                                                      // the kernels take the frame from blockIdx.z
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_resizeBatch(src_type, src_data + f0 * src_frame_stride, src_step, src_frame_stride, src_width, src_height, dst_data + f0 * dst_frame_stride, dst_step,
+                                       dst_frame_stride, dst_width, dst_height, nf, inv_scale_x, inv_scale_y, interpolation); });
     return runResize("resizeBatch", src_type, src_data, src_step, src_frame_stride, src_width, src_height, dst_data, dst_step, dst_frame_stride, dst_width, dst_height,
                      nframes, inv_scale_x, inv_scale_y, interpolation);
 }
@@ -3036,6 +3040,10 @@ MI355CV_API int mi355cv_warpAffineBatch(int src_type, const uchar* src_data, siz
         return runHostBatch("warpAffineBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_warpAffineBatch(src_type, s, ss, sf, src_width, src_height, d, ds, df, dst_width, dst_height, nf, M, interpolation, borderType, borderValue); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                                                                      // the kernels take the frame from blockIdx.z
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_warpAffineBatch(src_type, src_data + f0 * src_frame_stride, src_step, src_frame_stride, src_width, src_height, dst_data + f0 * dst_frame_stride, dst_step,
+                   dst_frame_stride, dst_width, dst_height, nf, M, interpolation, borderType, borderValue); });
     return runWarp("warpAffineBatch", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    M, 0, interpolation, borderType, borderValue, nullptr, 0, nullptr, 0, nframes, src_frame_stride, dst_frame_stride);
 }
@@ -3063,6 +3071,10 @@ MI355CV_API int mi355cv_warpPerspectiveBatch(int src_type, const uchar* src_data
         return runHostBatch("warpPerspectiveBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
             return mi355cv_warpPerspectiveBatch(src_type, s, ss, sf, src_width, src_height, d, ds, df, dst_width, dst_height, nf, M, interpolation, borderType, borderValue); });
     }
+    if (nframes > MAX_GRID_FRAMES)                                                                                                      // the kernels take the frame from blockIdx.z
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_warpPerspectiveBatch(src_type, src_data + f0 * src_frame_stride, src_step, src_frame_stride, src_width, src_height, dst_data + f0 * dst_frame_stride, dst_step,
+                   dst_frame_stride, dst_width, dst_height, nf, M, interpolation, borderType, borderValue); });
     return runWarp("warpPerspectiveBatch", src_type, src_data, src_step, src_width, src_height, dst_data, dst_step, dst_width, dst_height,
                    M, 1, interpolation, borderType, borderValue, nullptr, 0, nullptr, 0, nframes, src_frame_stride, dst_frame_stride);
 }
