@@ -2594,7 +2594,8 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
         static const int tapsTile = [] { const char* v = getenv("MI355CV_WARP_TAPS_TILE"); return v ? atoi(v) : -1; }();
         if ((tapsTile < 0 ? cn == 1 : tapsTile != 0) && kind == 0 && depth == D8U && interpolation == MI355CV_INTER_CUBIC && (cn == 1 || cn == 3) && sw >= 4 && sh >= 4 && terms) {
             warp8::Args a8; size_t lds8 = 0;
-            if (warp8::plan(a8, cn, 0, M, sw, sh, dw, dh, dss, dds, ds, dd, w.bw0, &lds8, 3)) {
+            // (the plan judges pointers and steps; the frames of a batch start at multiples of the frame strides, which must be whole dwords as well)
+            if (((w.sframe | w.dframe) & 3) == 0 && warp8::plan(a8, cn, 0, M, sw, sh, dw, dh, dss, dds, ds, dd, w.bw0, &lds8, 3)) {
                 a8.sframe = w.sframe; a8.dframe = w.dframe;
                 a8.constBorder = borderType == B_CONSTANT;
                 for (int k = 0; k < cn; k++) a8.cval |= (uint32_t)fminf(fmaxf(rintf(s.cval[k]), 0.f), 255.f) << (8 * k);
@@ -2671,7 +2672,7 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
         // measured (profiles/r03_warp8.txt): the tile kernel wins for affine maps of 1- and 3-channel images (4K 8UC1 7 degrees 20.5 -> ~13 us per frame, 90 degrees
         // 27 -> 20; 8UC3 33 -> 31 / 45 -> 27); 4-channel images and perspective maps (a double division per pixel either way) stay on the gather kernel
         static const int warp8All = [] { const char* v = getenv("MI355CV_WARP8"); return v ? atoi(v) : 1; }();      // 2: every case the plan accepts (A/B runs)
-        if (depth == D8U && warp8On && (warp8All == 2 || (kind == 0 && cn != 4)) && warp8::plan(a8, cn, kind, M, sw, sh, dw, dh, dss, dds, ds, dd, w.bw0, &lds8)) {
+        if (depth == D8U && warp8On && (warp8All == 2 || (kind == 0 && cn != 4)) && ((w.sframe | w.dframe) & 3) == 0 /* every frame of a batch starts on a dword */ && warp8::plan(a8, cn, kind, M, sw, sh, dw, dh, dss, dds, ds, dd, w.bw0, &lds8)) {
             a8.sframe = w.sframe; a8.dframe = w.dframe;
             a8.constBorder = borderType == B_CONSTANT;
             static const bool leanOn = [] { const char* v = getenv("MI355CV_WARP8_LEAN"); return !v || atoi(v) != 0; }();
@@ -2795,10 +2796,12 @@ int runWarp(const char* entry, int src_type, const uchar* src, size_t sstep, int
         else           { if (depth == D32F) WLC(float, 1); else WLC(uchar, 1); }
 #undef WLC
 #undef WL
+        noteKernel("k_warp_lin<depth %d,%d,%d> grid=%ux%ux%u x256", depth, cn, kind, g2.x, g2.y, g2.z);
         return stg.finish(entry);
     }
     dim3 grid(divUp(dw, 64), divUp(dh, 4), nframes);
     hipLaunchKernelGGL(k_warp, grid, dim3(256), 0, stream(), ds, dss, dd, dds, s, w, g_tabDev, dmx, mxs, dmy, mys);
+    noteKernel("k_warp grid=%ux%ux%u x256 kind=%d mode=%d", grid.x, grid.y, grid.z, kind, s.linear);
     return stg.finish(entry);
 }
 
@@ -2890,7 +2893,8 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
             if (rows && depth == D8U && tab8(4)) {
                 hipLaunchKernelGGL(k_resize_tab8<4>, g8, dim3(256), lds8, stream(), ds, dss, dd, dds, geom8, tx, ty, rows);
                 noteKernel("k_resize_tab8<4> grid=%ux%u x256 lds=%zu", g8.x, g8.y, lds8);
-            } else if (rows) RZ_BY_DEPTH(RZ_T4); else RZ_BY_DEPTH(RZ_C);
+            } else if (rows) { RZ_BY_DEPTH(RZ_T4); noteKernel("k_resize_tiled<depth %d,4> grid=%ux%u x256 lds=%zu", depth, gt.x, gt.y, (size_t)rows * 256); }
+            else { RZ_BY_DEPTH(RZ_C); noteKernel("k_resize_cubic<depth %d> grid=%ux%u x256", depth, g1.x, g1.y); }
         } else {
             const LanczosTap *dxt, *dyt;
             MI355_DECLINE_IF(!cachedTab<LanczosTap>(6, dst_width, a.scale_x, 8, buildLanczosTab, &dxt, &unused, &keepX) || !cachedTab<LanczosTap>(6, dst_height, a.scale_y, 8, buildLanczosTab, &dyt, &rows, &keepY));
@@ -2900,7 +2904,8 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
             if (rows && depth == D8U && tab8(8)) {
                 hipLaunchKernelGGL(k_resize_tab8<8>, g8, dim3(256), lds8, stream(), ds, dss, dd, dds, geom8, tx, ty, rows);
                 noteKernel("k_resize_tab8<8> grid=%ux%u x256 lds=%zu", g8.x, g8.y, lds8);
-            } else if (rows) RZ_BY_DEPTH(RZ_T8); else RZ_BY_DEPTH(RZ_L);
+            } else if (rows) { RZ_BY_DEPTH(RZ_T8); noteKernel("k_resize_tiled<depth %d,8> grid=%ux%u x256 lds=%zu", depth, gt.x, gt.y, (size_t)rows * 256); }
+            else { RZ_BY_DEPTH(RZ_L); noteKernel("k_resize_lanczos<depth %d> grid=%ux%u x256", depth, g1.x, g1.y); }
 #undef RZ_T8
 #undef RZ_L
 #undef RZ_T4
@@ -2919,6 +2924,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         if (depth == D8U) hipLaunchKernelGGL((k_resize_exact<uchar, 8>), g7, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, dx, dy);
         else if (depth == D16U) hipLaunchKernelGGL((k_resize_exact<unsigned short, 16>), g7, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, dx, dy);
         else hipLaunchKernelGGL((k_resize_exact<short, 16>), g7, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, dx, dy);
+        noteKernel("k_resize_exact<depth %d,%d> grid=%ux%u x256", depth, shift, g7.x, g7.y);
         return stg.finish(entry);
     }
     if (a.mode == 3 && depth == D8U && a.isx == 2 && a.isy == 2 && (cn == 1 || cn == 3 || cn == 4) && src_width == 2 * dst_width && src_height == 2 * dst_height &&
@@ -2927,6 +2933,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         if (cn == 1) hipLaunchKernelGGL(k_area2x2_u8<1>, g3, dim3(256), 0, stream(), ds, dss, a.sframe, dd, dds, a.dframe, dst_width, dst_height);
         else if (cn == 3) hipLaunchKernelGGL(k_area2x2_u8<3>, g3, dim3(256), 0, stream(), ds, dss, a.sframe, dd, dds, a.dframe, dst_width, dst_height);
         else hipLaunchKernelGGL(k_area2x2_u8<4>, g3, dim3(256), 0, stream(), ds, dss, a.sframe, dd, dds, a.dframe, dst_width, dst_height);
+        noteKernel("k_area2x2_u8<%d> grid=%ux%ux%u x256", cn, g3.x, g3.y, g3.z);
         return stg.finish(entry);
     }
     if (a.mode == 3 && depth == D32F && cn == 1 && a.isx == 2 && a.isy == 2 && src_width == 2 * dst_width && src_height == 2 * dst_height &&
@@ -2944,6 +2951,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
 #define RA(T_) hipLaunchKernelGGL(k_resize_area<T_>, g4, dim3(256), 0, stream(), ds, dss, dd, dds, dst_width, dst_height, cn, depth, dxt, dxo, dyt, dyo)
         switch (depth) { case D8U: RA(uchar); break; case D16U: RA(unsigned short); break; case D16S: RA(short); break; default: RA(float); }
 #undef RA
+        noteKernel("k_resize_area<depth %d> grid=%ux%u x256", depth, g4.x, g4.y);
         return stg.finish(entry);
     }
     if ((a.mode == 1 || a.mode == 2) && depth == D8U && (cn == 1 || cn == 3)) {
@@ -2951,7 +2959,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         // scale factors, so a planned call has no tile the kernel cannot take.  MI355CV_RESIZE8_LEAN=0 keeps the column-owning kernels (A/B runs)
         static const int rzOn = [] { const char* v = getenv("MI355CV_RESIZE8_LEAN"); return v ? atoi(v) : 1; }();
         warp8::Args a8; size_t ldsR = 0;
-        if (rzOn && warp8::planResize(a8, cn, src_width, src_height, dst_width, dst_height, dss, dds, ds, dd, a.scale_x, a.inv_x, a.scale_y, a.inv_y, a.mode == 2, &ldsR)) {
+        if (rzOn && ((a.sframe | a.dframe) & 3) == 0 /* every frame of a batch starts on a dword */ && warp8::planResize(a8, cn, src_width, src_height, dst_width, dst_height, dss, dds, ds, dd, a.scale_x, a.inv_x, a.scale_y, a.inv_y, a.mode == 2, &ldsR)) {
             int* tt = (int*)stg.scratch((size_t)(2 * dst_width + 4 * dst_height) * sizeof(int));
             if (tt) {
                 a8.sframe = a.sframe; a8.dframe = a.dframe;
@@ -2973,6 +2981,7 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         dim3 g2(divUp(dst_width, 64), divUp(dst_height, 4 * RROWS), nframes);
         if (depth == D32F) hipLaunchKernelGGL(k_resize_lin1<float>, g2, dim3(256), 0, stream(), ds, dss, dd, dds, a);
         else hipLaunchKernelGGL(k_resize_lin1<uchar>, g2, dim3(256), 0, stream(), ds, dss, dd, dds, a);
+        noteKernel("k_resize_lin1<depth %d> grid=%ux%ux%u x256", depth, g2.x, g2.y, g2.z);
         return stg.finish(entry);
     }
     if ((a.mode == 1 || a.mode == 2) && (cn == 3 || cn == 4) && (depth == D32F || depth == D8U) && (dss % e) == 0 && ((uintptr_t)ds % e) == 0) {
@@ -2981,10 +2990,12 @@ static int runResize(const char* entry, int src_type, const uchar* src_data, siz
         if (depth == D32F) { if (cn == 3) RLC(float, 3); else RLC(float, 4); }
         else { if (cn == 3) RLC(uchar, 3); else RLC(uchar, 4); }
 #undef RLC
+        noteKernel("k_resize_linC<depth %d,%d> grid=%ux%ux%u x256", depth, cn, g2.x, g2.y, g2.z);
         return stg.finish(entry);
     }
     dim3 grid(divUp(dst_width, 64), divUp(dst_height, 4), nframes);
     hipLaunchKernelGGL(k_resize, grid, dim3(256), 0, stream(), ds, dss, dd, dds, a);
+    noteKernel("k_resize grid=%ux%ux%u x256 mode=%d", grid.x, grid.y, grid.z, a.mode);
     return stg.finish(entry);
 }
 

@@ -1073,9 +1073,10 @@ def remap(src, map1, map2=None, interpolation=INTER_LINEAR, borderMode=BORDER_CO
     return out
 
 
-def convertMaps(map1, map2, dstmap1type, nninterpolation=False):
+def convertMaps(map1, map2, dstmap1type, nninterpolation=False, dst=None):
     """cv::convertMaps (imgwarp.cpp:1925): (CV_32FC1, CV_32FC1) / CV_32FC2 -> (CV_16SC2, CV_16UC1) [CV_16SC2 alone with nninterpolation], and
-    CV_16SC2 (+ CV_16UC1) -> (CV_32FC1, CV_32FC1) / CV_32FC2.  Returns (dstmap1, dstmap2 or None)."""
+    CV_16SC2 (+ CV_16UC1) -> (CV_32FC1, CV_32FC1) / CV_32FC2.  Returns (dstmap1, dstmap2 or None).  dst: (dstmap1, dstmap2) to write into (views of a
+    parent are fine); dstmap2 is None, or left out, where the conversion has no second map."""
     m1 = Img(map1)
     m2 = Img(map2) if map2 is not None else None
     T16SC2, T16UC1, T32FC1, T32FC2 = CV_MAKETYPE(CV_16S, 2), CV_MAKETYPE(CV_16U, 1), CV_MAKETYPE(CV_32F, 1), CV_MAKETYPE(CV_32F, 2)
@@ -1091,6 +1092,13 @@ def convertMaps(map1, map2, dstmap1type, nninterpolation=False):
         o1, o2 = empty_like_kind(map1, m1.h, m1.w, 2, CV_32F), None
     else:
         raise ValueError("convertMaps: dstmap1type must be CV_16SC2, CV_32FC1 or CV_32FC2")
+    if dst is not None:
+        given = tuple(dst) if isinstance(dst, (tuple, list)) else (dst,)
+        given = given + (None,) * (2 - len(given))
+        for want, got in zip((o1, o2), given):
+            if (want is None) != (got is None) or (want is not None and (tuple(got.shape) != tuple(want.shape) or got.dtype != want.dtype)):
+                raise ValueError("convertMaps: dst geometry mismatch")
+        o1, o2 = given
     a, b = Img(o1), (Img(o2) if o2 is not None else None)
     bind_stream(m1, a)
     rc = L.mi355cv_convertMaps(_vp(m1.ptr), m1.step, m1.type, _vp(m2.ptr) if m2 is not None else None, m2.step if m2 is not None else 0,

@@ -22,6 +22,10 @@ Guards: ROWS_ABOVE / ROWS_BELOW parent rows around the view and at least TAIL_BY
 overruns by a vector or a row fails an assertion instead of faulting.  The destination parent is filled with per-byte pseudo-random data from a fixed seed (a
 constant would hide a stray 0 or 255); the source parent outside the view is hostile (NaN for float depths, the depth's extremes -- which `content` never
 produces -- otherwise), so a kernel that reads the parent where the border rule applies changes its output.
+
+Beyond one source and one destination, `run` takes further read-only inputs (maps), several guarded destinations from one call, and a destination that is an
+input too; `run_batch` takes frames in the forms of BATCH_FORMS_ALL and in ALIGNED, the control of 'oddstride'.  tests/test_viewcheck_cpu.py holds a correct and a
+deliberately wrong numpy stand-in against each of these.
 """
 import numpy as np
 
@@ -29,9 +33,10 @@ LAYOUTS = ("A", "B", "C", "D", "E", "F")
 _SIDES = {"A": ("a", "a"), "B": ("b", "b2"), "C": ("a", "b2"), "D": ("b", "a"), "E": ("e", "e"), "F": ("f", "f2")}
 ROWS_ABOVE, ROWS_BELOW, TAIL_BYTES = 4, 2, 64      # 4 rows above: 4 * pitch is a multiple of 16 for every pitch that is a multiple of 4 (layout E's base 0)
 SENTINEL_SEED = 0x5EED
-# every (depth, channels) a source or a destination of tests/test_views_gpu.py has; tests/test_viewcheck_cpu.py checks the layouts' residues for each
+# every (depth, channels) a source, a map or a destination of tests/test_views_gpu.py and tests/test_warp_views_gpu.py has; tests/test_viewcheck_cpu.py checks the
+# layouts' residues for each.  (CV_32FC4 is not among them on purpose: its pixels have 16 bytes, so layout B cannot be built for it.)
 PIXELS_USED = [(np.uint8, 1), (np.uint8, 2), (np.uint8, 3), (np.uint8, 4), (np.uint16, 1), (np.uint16, 3), (np.int16, 1), (np.int16, 2), (np.int32, 1),
-               (np.float32, 1), (np.float32, 3), (np.float64, 1)]
+               (np.float32, 1), (np.float32, 2), (np.float32, 3), (np.float64, 1)]
 
 
 class Unreachable(Exception):
@@ -40,7 +45,8 @@ class Unreachable(Exception):
 
 class GuardTouched(AssertionError):
     """a byte of a parent outside the view changed.  row / byte: position in the parent; rel_row / rel_byte: relative to the view's first row / to the first
-    byte of the view's row; where: 'above', 'below', 'left', 'right' (of the view, on one of its rows), 'inside' (a source view that changed)"""
+    byte of the view's row; where: 'above', 'below', 'left', 'right' (of the view, on one of its rows), 'inside' (a source view that changed), 'gap' (the bytes
+    between two frames of an 'oddstride' batch: row = the parent's row count, byte = the byte of the gap, frame = the frame the gap follows)"""
 
     def __init__(self, what, row, byte, rel_row, rel_byte, where, past_end, frame=None):
         self.row, self.byte, self.rel_row, self.rel_byte, self.where, self.past_end, self.frame = row, byte, rel_row, rel_byte, where, past_end, frame
@@ -249,35 +255,57 @@ class Host:
         return np.asarray(a)
 
 
-def run(call, layout, image, want, what="", compare=exact, device=Host, kernel_name=None):
+def _geometry_like(kind, dtype, shape):
+    return Geometry(kind, dtype, shape[2] if len(shape) == 3 else 1, shape[1], shape[0], len(shape))
+
+
+def run(call, layout, image, want, what="", compare=exact, device=Host, kernel_name=None, inputs=(), dst_like=None):
     """One op on one layout.  image: the source view's content, contiguous [h, w] or [h, w, cn]; want: the oracle's result for it (it fixes the destination's
     shape and dtype), or None for an op without an image output.  call(src_view, dst_view) runs the op into dst_view; without a destination it is
     call(src_view, None) and its return value is handed back.  device: put(ndarray) -> the array the op takes, get(array) -> ndarray.  kernel_name() is read
-    right after the call.  Returns (kernel name or None, the op's return value)."""
+    right after the call.  Returns (kernel name or None, the op's return value).
+
+    inputs: further read-only operands (the maps of remap and convertMaps).  Each is placed like the source side of the layout inside a hostile parent of its
+    own, the views follow the destination -- call(src_view, dst_view, *input_views) -- and every parent is checked unchanged afterwards.
+
+    want as a tuple or list of arrays: that many guarded destinations from one call (convertMaps); dst_view is then the tuple of their views, each in a parent
+    of its own with its own sentinel, and compare may be a tuple as well.
+
+    want as a callable, with dst_like = (dtype, shape): the destination is an input too (BORDER_TRANSPARENT keeps what the map does not reach).  The view starts
+    with its parent's sentinel; want(prev) gets a copy of that content -- it is the oracle's dst= -- and returns the expected array."""
     image = np.ascontiguousarray(image)
-    h, w = image.shape[:2]
-    cn = image.shape[2] if image.ndim == 3 else 1
+    inputs = [np.ascontiguousarray(a) for a in inputs]
+    ks, kd = _SIDES[layout]
+    sg = _geometry_like(ks, image.dtype, image.shape)
+    igs = [_geometry_like(ks, a.dtype, a.shape) for a in inputs]
+    several = isinstance(want, (tuple, list))
     if want is None:
-        sg, dg = plan(layout, image.dtype, cn, w, h, src_ndim=image.ndim)
+        wants = []
+    elif callable(want):
+        wants = [want]
     else:
-        want = np.ascontiguousarray(want)
-        dcn = want.shape[2] if want.ndim == 3 else 1
-        sg, dg = plan(layout, image.dtype, cn, w, h, want.dtype, dcn, want.shape[1], want.shape[0], image.ndim, want.ndim)
+        wants = [np.ascontiguousarray(w) for w in (want if several else [want])]
+    dgs = [_geometry_like(kd, *(dst_like if callable(w) else (w.dtype, w.shape))) for w in wants]
+    compares = list(compare) if isinstance(compare, (tuple, list)) else [compare] * len(wants)
     sp0 = source_parent(sg, image)
     sp = device.put(sp0.copy())
-    if dg is None:
-        rv = call(sg.view(sp), None)
-        name = kernel_name() if kernel_name else None
-        check_guard(what + " source", sp0, device.get(sp), sg, whole=True)
-        return name, rv
-    dp0 = sentinel(dg.dtype, dg.parent_shape())
-    dp = device.put(dp0.copy())
-    rv = call(sg.view(sp), dg.view(dp))
+    ip0 = [source_parent(g, a) for g, a in zip(igs, inputs)]
+    ip = [device.put(p.copy()) for p in ip0]
+    dp0 = [sentinel(g.dtype, g.parent_shape(), SENTINEL_SEED + k) for k, g in enumerate(dgs)]
+    dp = [device.put(p.copy()) for p in dp0]
+    dviews = [g.view(p) for g, p in zip(dgs, dp)]
+    rv = call(sg.view(sp), tuple(dviews) if several else dviews[0] if dviews else None, *[g.view(p) for g, p in zip(igs, ip)])
     name = kernel_name() if kernel_name else None
-    after = device.get(dp)
-    check_guard(what, dp0, after, dg)
+    after = [device.get(p) for p in dp]
+    tag = lambda k: " dst %d" % k if several else ""                                 # noqa: E731
+    for k, g in enumerate(dgs):
+        check_guard(what + tag(k), dp0[k], after[k], g)
     check_guard(what + " source", sp0, device.get(sp), sg, whole=True)
-    check_result(what, dg.view(after), want, compare)
+    for k, g in enumerate(igs):
+        check_guard(what + " input %d" % k, ip0[k], device.get(ip[k]), g, whole=True)
+    for k, g in enumerate(dgs):
+        expected = wants[k](np.array(g.view(dp0[k]), copy=True)) if callable(wants[k]) else wants[k]
+        check_result(what + tag(k), g.view(after[k]), expected, compares[k])
     return name, rv
 
 
@@ -299,18 +327,82 @@ def run_inplace(call, image, want, what="", compare=exact, device=Host, kernel_n
 
 
 BATCH_FORMS = ("roi", "columns")
+ODDSTRIDE, ALIGNED = "oddstride", "aligned"
+BATCH_FORMS_ALL = BATCH_FORMS + (ODDSTRIDE,)
 
 
 def batch_geometry(form, dtype, cn, w, h, ndim):
     """frames as views of a parent [n + 2, hp, wp(, cn)] (a guard frame before and after): 'roi' = parent[1:-1, 2:2+h, 3:3+w], base, pitch and frame stride all
-    ragged; 'columns' = parent[1:-1, :, 3:3+w], full height, so the frame stride is step * h (frames back to back are one tall image, with a step wider than the row)"""
-    g = Geometry("b2", dtype, cn, w, h, ndim)                           # x0 = 3, ragged pitch
-    if form == "roi":
-        g.y0, g.hp = 2, h + 4
+    ragged; 'columns' = parent[1:-1, :, 3:3+w], full height, so the frame stride is step * h (frames back to back are one tall image, with a step wider than the row).
+
+    'aligned' = parent[1:-1, 2:2+h, 0:w] with a pitch that is a multiple of 16: pointer, step and frame stride all pass every alignment predicate.  It is the control
+    of 'oddstride', which has the same frames, but in one flat allocation in which every frame's [hp, wp] block is followed by a gap of one element (g.gap bytes):
+    the first frame and the step stay multiples of 16 and the frame stride hp * pitch + 1 (1-byte elements) / + 2 (2-byte elements) is the only thing that is no
+    multiple of 4 -- what as_strided, or a header in front of every frame, gives.  That form is not built for wider elements: a frame stride has to be a multiple
+    of the element size, so it would be a multiple of 4."""
+    if form in (ODDSTRIDE, ALIGNED):
+        g = Geometry("a", dtype, cn, w, h, ndim)                        # x0 = 0, pitch a multiple of 16 (the tail of the row above is the guard on the left)
     else:
+        g = Geometry("b2", dtype, cn, w, h, ndim)                       # x0 = 3, ragged pitch
+    if form == "columns":
         g.y0, g.hp = 0, h
+    else:
+        g.y0, g.hp = 2, h + 4
+    g.gap = 0
+    if form == ODDSTRIDE:
+        if g.dtype.itemsize > 2:
+            raise ValueError("the 'oddstride' form is built for 1- and 2-byte elements, not for %s" % g.dtype)
+        g.gap = g.dtype.itemsize
+    g.frame_stride = g.hp * g.pitch + g.gap
     g.base = g.y0 * g.pitch + g.x0 * g.px
     return g
+
+
+def _strided(flat, dtype, shape, strides, offset):
+    """a view of the flat typed 1-D array `flat` (numpy, or a tensor: anything else with as_strided(size, stride, storage_offset)); strides and offset in bytes"""
+    if isinstance(flat, np.ndarray):
+        return np.ndarray(shape, dtype, buffer=flat, offset=offset, strides=strides)
+    isz = np.dtype(dtype).itemsize
+    assert offset % isz == 0 and all(v % isz == 0 for v in strides)
+    return flat.as_strided(tuple(shape), tuple(v // isz for v in strides), offset // isz)
+
+
+def _odd_offset(g, k):
+    """byte offset of block k of the flat allocation: the guard block (k = 0), the frames' blocks, each followed by its gap, the guard block behind them"""
+    return k * g.hp * g.pitch + max(k - 1, 0) * g.gap
+
+
+def _odd_flat(g, blocks):
+    """blocks [n + 2, hp, wp(, cn)] -> the flat allocation (typed, 1-D); the gaps hold a sentinel of their own"""
+    nb, body = blocks.shape[0], g.hp * g.pitch
+    flat = np.random.default_rng(SENTINEL_SEED ^ 0xA5).integers(0, 256, _odd_offset(g, nb - 1) + body, dtype=np.uint8)
+    rows = np.ascontiguousarray(blocks).reshape(nb, -1).view(np.uint8)
+    for k in range(nb):
+        flat[_odd_offset(g, k):_odd_offset(g, k) + body] = rows[k]
+    return flat.view(g.dtype)
+
+
+def _odd_split(g, flat, nb):
+    """the flat allocation -> (blocks [n + 2, hp, wp(, cn)], gap bytes [n, g.gap]: the gap behind each frame)"""
+    b, body = np.ascontiguousarray(flat).view(np.uint8), g.hp * g.pitch
+    blocks = np.stack([b[_odd_offset(g, k):_odd_offset(g, k) + body] for k in range(nb)])
+    gaps = np.stack([b[_odd_offset(g, k) + body:_odd_offset(g, k) + body + g.gap] for k in range(1, nb - 1)])
+    return np.ascontiguousarray(blocks).view(g.dtype).reshape((nb,) + g.parent_shape()), gaps
+
+
+def _odd_frames(g, flat, n):
+    isz = g.dtype.itemsize
+    shape = (n, g.h, g.w) + ((g.cn,) if g.ndim == 3 else ())
+    strides = (g.frame_stride, g.pitch, g.px) + ((isz,) if g.ndim == 3 else ())
+    return _strided(flat, g.dtype, shape, strides, _odd_offset(g, 1) + g.base)
+
+
+def check_gaps(what, before, after, geom):
+    """the gap bytes of an 'oddstride' allocation (before, after: [n, gap], the gap behind each frame) did not change"""
+    bad = np.argwhere(before != after)
+    if len(bad):
+        block, byte = (int(v) for v in bad[0])
+        raise GuardTouched(what, geom.hp, byte, geom.hp - geom.y0, byte - geom.x0 * geom.px, "gap", 0, block)
 
 
 def run_batch(call, form, frames, want, what="", compare=exact, device=Host, kernel_name=None):
@@ -322,12 +414,24 @@ def run_batch(call, form, frames, want, what="", compare=exact, device=Host, ker
     sp0 = np.stack([hostile(sg.dtype, sg.parent_shape())] * (n + 2))
     sp0[1:n + 1, sg.y0:sg.y0 + h, sg.x0:sg.x0 + w] = frames
     dp0 = sentinel(dg.dtype, (n + 2,) + dg.parent_shape())
-    sp, dp = device.put(sp0.copy()), device.put(dp0.copy())
-    rv = call(sp[1:n + 1, sg.y0:sg.y0 + h, sg.x0:sg.x0 + w], dp[1:n + 1, dg.y0:dg.y0 + dg.h, dg.x0:dg.x0 + dg.w])
-    name = kernel_name() if kernel_name else None
-    after = device.get(dp)
-    check_guard(what + " " + form, dp0, after, dg, frames=(1, n))
-    check_guard(what + " " + form + " source", sp0, device.get(sp), sg, frames=(1, n), whole=True)
+    if form == ODDSTRIDE:
+        sf0, df0 = _odd_flat(sg, sp0), _odd_flat(dg, dp0)
+        sf, df = device.put(sf0.copy()), device.put(df0.copy())
+        rv = call(_odd_frames(sg, sf, n), _odd_frames(dg, df, n))
+        name = kernel_name() if kernel_name else None
+        after, dgaps = _odd_split(dg, device.get(df), n + 2)
+        safter, sgaps = _odd_split(sg, device.get(sf), n + 2)
+        check_guard(what + " " + form, dp0, after, dg, frames=(1, n))
+        check_gaps(what + " " + form, _odd_split(dg, df0, n + 2)[1], dgaps, dg)
+        check_guard(what + " " + form + " source", sp0, safter, sg, frames=(1, n), whole=True)
+        check_gaps(what + " " + form + " source", _odd_split(sg, sf0, n + 2)[1], sgaps, sg)
+    else:
+        sp, dp = device.put(sp0.copy()), device.put(dp0.copy())
+        rv = call(sp[1:n + 1, sg.y0:sg.y0 + h, sg.x0:sg.x0 + w], dp[1:n + 1, dg.y0:dg.y0 + dg.h, dg.x0:dg.x0 + dg.w])
+        name = kernel_name() if kernel_name else None
+        after = device.get(dp)
+        check_guard(what + " " + form, dp0, after, dg, frames=(1, n))
+        check_guard(what + " " + form + " source", sp0, device.get(sp), sg, frames=(1, n), whole=True)
     got = after[1:n + 1, dg.y0:dg.y0 + dg.h, dg.x0:dg.x0 + dg.w]
     for f in range(n):
         check_result("%s %s frame %d" % (what, form, f), got[f], want[f], compare)
