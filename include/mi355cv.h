@@ -883,6 +883,38 @@ MI355CV_API int mi355cv_filterSpecklesBatch(mi355cv_uchar* img, size_t step, siz
  * in LDS), 0 always the plain per-pixel kernels.  Results do not depend on it. */
 MI355CV_API int mi355cv_filterSpecklesSetKernel(int mode);
 
+/* --------------------------------------------------- f3: calib3d StereoSGBM (csrc/sgbm.hip) */
+/* The parameters of cv::StereoSGBM (calib3d.hpp).  mode: 0 MODE_SGBM (5 directions), 1 MODE_HH (8), 2 MODE_SGBM_3WAY (declined), 3 MODE_HH4 (4).
+ * mi355cv_stereoSGBMDefaults fills the values of StereoSGBM::create(): 0, 16, 3, 0, 0, 0, 0, 0, 0, 0, MODE_SGBM. */
+typedef struct mi355cv_StereoSGBMParams {
+    int minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize, speckleRange, mode;
+} mi355cv_StereoSGBMParams;
+MI355CV_API void mi355cv_stereoSGBMDefaults(mi355cv_StereoSGBMParams* params);
+/* cv::StereoSGBM::compute (modules/calib3d, no HAL hook; the definition served is written down in DESIGN 6.19 and tests/sgbm_restate.py) on two rectified CV_8UC1
+ * images of width x height: the CV_16SC1 map of disparities times 16 (disp_depth = MI355CV_16S) or the CV_32FC1 map of disparities (MI355CV_32F, the former divided by
+ * 16, exact).  A pixel without a disparity holds (minDisparity - 1) * 16, respectively minDisparity - 1.  All arithmetic is integer: the map is determined bit for bit.
+ * speckleWindowSize > 0 runs mi355cv_filterSpecklesBatch on the CV_16S map (newVal (minDisparity - 1) * 16, maxDiff 16 * speckleRange) before it is delivered.
+ * Every image may live in host memory (staged through HBM, host-cost class HOST_HEAVY) or in this thread's device memory, at any pitch and byte address; device
+ * pointers run on the current stream.  Scratch: 6 bytes per valid pixel and disparity (the 16-bit block costs and the 32-bit path sums) from the runtime's pool.
+ * Declined (MI355CV_NOT_IMPLEMENTED, disp left untouched): MODE_SGBM_3WAY and unknown modes; other disparity depths; numDisparities not a positive multiple of 16 or
+ * above mi355cv_limit("sgbm_max_disparities") = 256; blockSize even or below 1; preFilterCap < 0; P1 < 0 or P2 < P1 (P1 = P2 = 0 is served as given); uniquenessRatio
+ * outside 0 .. 100; negative speckle arguments; blockSize^2 * (2 ft + 63) + P2 > mi355cv_limit("sgbm_max_cost") = 32767 with ft = max(preFilterCap, 15) | 1 (costs are
+ * 16 bit); minDisparity < -2047 or minDisparity + numDisparities - 1 > 2046; width or height above mi355cv_limit("sgbm_max_dim") = 16384; a frame whose scratch exceeds
+ * mi355cv_limit("sgbm_max_scratch_mib") = 16384 MiB; a pitch below the row; disparity rows off their element's boundary; a disparity map that overlaps an input. */
+MI355CV_API int mi355cv_stereoSGBM(const mi355cv_uchar* left, size_t left_step, const mi355cv_uchar* right, size_t right_step, mi355cv_uchar* disp, size_t disp_step,
+        int width, int height, int disp_depth, const mi355cv_StereoSGBMParams* params);
+/* nframes pairs at left + f * left_frame_stride, right + f * right_frame_stride into disp + f * disp_frame_stride; exactly the results of nframes single calls.  The
+ * frames run in chunks whose volumes fit the scratch bound, each chunk one sequence of launches with the frame in the grid's z.  Declined as well: nframes < 1, a frame
+ * stride below the frame, stacks whose extents overlap. */
+MI355CV_API int mi355cv_stereoSGBMBatch(const mi355cv_uchar* left, size_t left_step, size_t left_frame_stride, const mi355cv_uchar* right, size_t right_step,
+        size_t right_frame_stride, mi355cv_uchar* disp, size_t disp_step, size_t disp_frame_stride, int nframes, int width, int height, int disp_depth,
+        const mi355cv_StereoSGBMParams* params);
+/* A/B switch of the path aggregation (tools/sgbm_bench.py): -1 the built-in rule (the fast kernel: lanes across the disparities, loads of a block of steps in flight),
+ * 0 always the plain kernel (a workgroup per path, a lane per disparity), 1 always the fast one.  Results do not depend on it. */
+MI355CV_API int mi355cv_stereoSGBMSetKernel(int mode);
+/* Lowers the scratch bound to `bytes` (0: back to the limit), so that the chunking of batches can be exercised at small shapes.  Results do not depend on it. */
+MI355CV_API int mi355cv_stereoSGBMSetScratchLimit(size_t bytes);
+
 #ifdef __cplusplus
 }
 #endif

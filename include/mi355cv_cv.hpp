@@ -895,6 +895,65 @@ private:
     cv::Ptr<cv::StereoBM> stock_;
 };
 
+// cv::StereoSGBM (calib3d.hpp; stereosgbm.cpp).  The reference has no HAL hook for it.  mi355cv::StereoSGBM::create returns a cv::StereoSGBM that wraps the stock object,
+// where the parameters live; compute sends two 2-D CV_8UC1 cv::Mat images through mi355cv_stereoSGBM (csrc/sgbm.hip), the images and the map staying where the Mats live.
+// The map is the project's restatement of the algorithm (tests/sgbm_restate.py), all integer and determined bit for bit; where recollection of the
+// reference differs it is listed there.  speckleWindowSize > 0 is served (the map goes through the served filterSpeckles on the device).  Everything the entry declines
+// (MODE_SGBM_3WAY, 3-channel images, parameters over the limits or outside the 16-bit cost bound, UMat, no device) goes to the stock object, which finds the map
+// untouched.  Not compiled here: the reference's headers are absent.
+class StereoSGBM CV_FINAL : public cv::StereoSGBM
+{
+public:
+    explicit StereoSGBM(const cv::Ptr<cv::StereoSGBM>& stock) : stock_(stock) {}
+    static cv::Ptr<cv::StereoSGBM> create(int minDisparity = 0, int numDisparities = 16, int blockSize = 3, int P1 = 0, int P2 = 0, int disp12MaxDiff = 0, int preFilterCap = 0,
+                                          int uniquenessRatio = 0, int speckleWindowSize = 0, int speckleRange = 0, int mode = cv::StereoSGBM::MODE_SGBM)
+    {
+        return cv::makePtr<mi355cv::StereoSGBM>(cv::StereoSGBM::create(minDisparity, numDisparities, blockSize, P1, P2, disp12MaxDiff, preFilterCap, uniquenessRatio, speckleWindowSize,
+                                                                       speckleRange, mode));
+    }
+
+    int getMinDisparity() const CV_OVERRIDE { return stock_->getMinDisparity(); }              void setMinDisparity(int v) CV_OVERRIDE { stock_->setMinDisparity(v); }
+    int getNumDisparities() const CV_OVERRIDE { return stock_->getNumDisparities(); }          void setNumDisparities(int v) CV_OVERRIDE { stock_->setNumDisparities(v); }
+    int getBlockSize() const CV_OVERRIDE { return stock_->getBlockSize(); }                    void setBlockSize(int v) CV_OVERRIDE { stock_->setBlockSize(v); }
+    int getSpeckleWindowSize() const CV_OVERRIDE { return stock_->getSpeckleWindowSize(); }    void setSpeckleWindowSize(int v) CV_OVERRIDE { stock_->setSpeckleWindowSize(v); }
+    int getSpeckleRange() const CV_OVERRIDE { return stock_->getSpeckleRange(); }              void setSpeckleRange(int v) CV_OVERRIDE { stock_->setSpeckleRange(v); }
+    int getDisp12MaxDiff() const CV_OVERRIDE { return stock_->getDisp12MaxDiff(); }            void setDisp12MaxDiff(int v) CV_OVERRIDE { stock_->setDisp12MaxDiff(v); }
+    int getPreFilterCap() const CV_OVERRIDE { return stock_->getPreFilterCap(); }              void setPreFilterCap(int v) CV_OVERRIDE { stock_->setPreFilterCap(v); }
+    int getUniquenessRatio() const CV_OVERRIDE { return stock_->getUniquenessRatio(); }        void setUniquenessRatio(int v) CV_OVERRIDE { stock_->setUniquenessRatio(v); }
+    int getP1() const CV_OVERRIDE { return stock_->getP1(); }                                  void setP1(int v) CV_OVERRIDE { stock_->setP1(v); }
+    int getP2() const CV_OVERRIDE { return stock_->getP2(); }                                  void setP2(int v) CV_OVERRIDE { stock_->setP2(v); }
+    int getMode() const CV_OVERRIDE { return stock_->getMode(); }                              void setMode(int v) CV_OVERRIDE { stock_->setMode(v); }
+    void clear() CV_OVERRIDE { stock_->clear(); }
+    bool empty() const CV_OVERRIDE { return stock_->empty(); }
+    void write(cv::FileStorage& fs) const CV_OVERRIDE { stock_->write(fs); }
+    void read(const cv::FileNode& fn) CV_OVERRIDE { stock_->read(fn); }
+    cv::String getDefaultName() const CV_OVERRIDE { return stock_->getDefaultName(); }
+
+    void compute(cv::InputArray _left, cv::InputArray _right, cv::OutputArray _disp) CV_OVERRIDE
+    {
+        if (_left.kind() == cv::_InputArray::MAT && _right.kind() == cv::_InputArray::MAT && !_disp.isUMat()) {
+            cv::Mat left = _left.getMat(), right = _right.getMat();
+            // the reference writes CV_16S unless the destination was fixed to CV_32F by the caller
+            const int dtype = _disp.fixedType() && _disp.type() == CV_32FC1 ? CV_32FC1 : CV_16SC1;
+            if (left.dims <= 2 && !left.empty() && left.type() == CV_8UC1 && right.type() == CV_8UC1 && left.size() == right.size()) {
+                mi355cv_StereoSGBMParams p;
+                mi355cv_stereoSGBMDefaults(&p);
+                p.minDisparity = getMinDisparity(); p.numDisparities = getNumDisparities(); p.blockSize = getBlockSize(); p.P1 = getP1(); p.P2 = getP2();
+                p.disp12MaxDiff = getDisp12MaxDiff(); p.preFilterCap = getPreFilterCap(); p.uniquenessRatio = getUniquenessRatio();
+                p.speckleWindowSize = getSpeckleWindowSize(); p.speckleRange = getSpeckleRange(); p.mode = getMode();
+                // an overlapping destination is declined by the entry and the stock object then allocates as it always does
+                cv::Mat disp = _disp.getMat();
+                if (disp.size() != left.size() || disp.type() != dtype) { _disp.create(left.size(), dtype); disp = _disp.getMat(); }
+                if (mi355cv_stereoSGBM(left.data, left.step, right.data, right.step, disp.data, disp.step, left.cols, left.rows, dtype == CV_32FC1 ? MI355CV_32F : MI355CV_16S, &p) == MI355CV_OK)
+                    return;
+            }
+        }
+        stock_->compute(_left, _right, _disp);
+    }
+private:
+    cv::Ptr<cv::StereoSGBM> stock_;
+};
+
 // cv::filterSpeckles (calib3d.hpp; stereosgbm.cpp).  The reference has no HAL hook for it.  A 2-D CV_8UC1 or CV_16SC1 cv::Mat goes through mi355cv_filterSpeckles
 // (csrc/speckle.hip) in place, where the Mat lives: the step to take on the map mi355cv::StereoBM::compute left in HBM.  The image is the project's restatement of the
 // algorithm (tests/speckle_restate.py): it depends on component sizes only and is determined bit for bit.  newVal and maxDiff are truncated to int as the

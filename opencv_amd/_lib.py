@@ -81,6 +81,11 @@ def _load():
         "mi355cv_filterSpeckles": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_filterSpecklesBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, c_int, c_int]),
         "mi355cv_filterSpecklesSetKernel": (c_int, [c_int]),
+        "mi355cv_stereoSGBMDefaults": (None, [ctypes.c_void_p]),
+        "mi355cv_stereoSGBM": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_stereoSGBMBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_stereoSGBMSetKernel": (c_int, [c_int]),
+        "mi355cv_stereoSGBMSetScratchLimit": (c_int, [c_sz]),
         "mi355cv_remap": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int,
                                   c_int, c_int, ctypes.c_void_p]),
         "mi355cv_convertMaps": (c_int, [ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz,

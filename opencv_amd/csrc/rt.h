@@ -64,6 +64,14 @@ constexpr int STEREOBM_GENERIC_TILE_COLS = 32; // ... pixels of a row per workgr
 constexpr int SPECKLE_MAX_DIM = 16384;         // mi355cv_filterSpeckles*: width and height (the neighbours' bound; a pixel index and a component size stay below 2^28; speckle_math.h)
 constexpr int SPECKLE_TILE_COLS = 256;         // ... geometry, reported for the tests' shapes: columns of a tile of the fast kernel (64 lanes x 4 pixels)
 constexpr int SPECKLE_TILE_ROWS = 16;          // ... and its rows, merged in LDS
+constexpr int SGBM_MAX_DIM = 16384;            // mi355cv_stereoSGBM*: width and height (the neighbours' bound; a column fits the 16 bits the left-right key gives it; sgbm_math.h)
+constexpr int SGBM_MAX_DISPARITIES = 256;      // ... numDisparities: four values per lane of a wave in the fast path kernel, a wave per 16 disparities in the cost kernel
+constexpr int SGBM_MAX_COST = 32767;           // ... blockSize^2 * (2 ft + 63) + P2, ft = max(preFilterCap, 15) | 1: every block cost and path cost fits 16 bits
+constexpr long long SGBM_MAX_SCRATCH_BYTES = 16384ll << 20; // ... the volumes of the frames in flight, 6 bytes per valid pixel and disparity (reported in MiB: "sgbm_max_scratch_mib")
+constexpr int SGBM_TILE_COLS = 64;             // ... geometry, reported for the tests' shapes: window columns per workgroup of the cost kernel, 64 - (blockSize - 1) pixels of a row
+constexpr int SGBM_STRIP_ROWS = 32;            // ... rows a workgroup of the cost kernel walks down
+constexpr int SGBM_CHUNK = 16;                 // ... disparities per lane of the cost kernel
+constexpr int SGBM_PATH_BLOCK = 16;            // ... steps of a path per block of loads in the fast path kernel up to 64 disparities (8 up to 128, 4 above)
 }
 
 struct ThreadCtx;

@@ -581,7 +581,9 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"stereobm_max_dim", STEREOBM_MAX_DIM}, {"stereobm_max_disparities", STEREOBM_MAX_DISPARITIES}, {"stereobm_max_block", STEREOBM_MAX_BLOCK},
         {"stereobm_roll_max_block", STEREOBM_ROLL_MAX_BLOCK}, {"stereobm_chunk", STEREOBM_CHUNK}, {"stereobm_tile_cols", STEREOBM_TILE_COLS},
         {"stereobm_strip_rows", STEREOBM_STRIP_ROWS}, {"stereobm_generic_tile_cols", STEREOBM_GENERIC_TILE_COLS},
-        {"speckle_max_dim", SPECKLE_MAX_DIM}, {"speckle_tile_cols", SPECKLE_TILE_COLS}, {"speckle_tile_rows", SPECKLE_TILE_ROWS}};
+        {"speckle_max_dim", SPECKLE_MAX_DIM}, {"speckle_tile_cols", SPECKLE_TILE_COLS}, {"speckle_tile_rows", SPECKLE_TILE_ROWS},
+        {"sgbm_max_dim", SGBM_MAX_DIM}, {"sgbm_max_disparities", SGBM_MAX_DISPARITIES}, {"sgbm_max_cost", SGBM_MAX_COST}, {"sgbm_max_scratch_mib", (int)(SGBM_MAX_SCRATCH_BYTES >> 20)},
+        {"sgbm_tile_cols", SGBM_TILE_COLS}, {"sgbm_strip_rows", SGBM_STRIP_ROWS}, {"sgbm_chunk", SGBM_CHUNK}, {"sgbm_path_block", SGBM_PATH_BLOCK}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
