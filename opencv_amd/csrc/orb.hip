@@ -3,7 +3,7 @@
 // PCIe twice per pyramid level.  Here the pyramid buffer, the FAST score images, the smoothed pyramid and the pattern live in device scratch; the host
 // sees the candidate lists (to cull them the way the reference does) and the final keypoints / descriptors.
 //
-//   pyramid      every level = cv::resize(INTER_LINEAR_EXACT) of the previous one (mi355cv_resize, warp.hip k_resize_exact), packed side by side in one
+//   pyramid      every level = cv::resize(INTER_LINEAR_EXACT) of the previous one (mi355cv_resize, resize.hip k_resize_exact), packed side by side in one
 //                8-bit buffer with a BORDER_REFLECT_101 ring of max(edgeThreshold, ceil(halfPatch sqrt 2), 4) + 1 pixels (k_orb_border): the reference's
 //                own layout (orb.cpp:1056-1095), so Harris / angle / descriptor reads near a level's edge see the same pixels
 //   keypoints    FAST 9-16 with suppression on all levels in one launch per pass (fast.hip k_fast_*_levels), the candidates of all levels in raster order

@@ -4,7 +4,7 @@
 //   hpass   the horizontal sums S_k of every staged row for the tile's 256 elements (integer taps * 2048, exact) -> LDS ints
 //   vpass   each lane combines NT of them for its four neighbouring elements of a row (the reference's vector body in float for cubic, the integer
 //           (sum + 2^21) >> 22 form in its scalar tail and for Lanczos) and stores one dword
-// against the 64 x 16 tile kernel (warp.hip k_resize_tiled), whose lanes gather their taps byte by byte from global memory (a byte gather is served lane by
+// against the 64 x 16 tile kernel (resize.hip k_resize_tiled), whose lanes gather their taps byte by byte from global memory (a byte gather is served lane by
 // lane: profiles/r02_warp_pmc.txt) and store single bytes.  The phases are functions of the thread index so that tests/hostemu/resize_tab8_emu.cpp can run
 // a workgroup thread by thread on the CPU against the pinned restatement; the tap tables (also used by the other cubic / Lanczos kernels) are built here.
 #pragma once

@@ -7,6 +7,7 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 #include <stdint.h>
+#include <stdlib.h>
 #include <vector>
 #include <functional>
 #include "../../include/mi355cv.h"
@@ -186,6 +187,7 @@ int runHostBatchN(const char* entry, const HostBatchN& hb, const HostBatchNFn& r
 
 inline int depthBytes(int depth) { return depth <= 1 ? 1 : depth <= 3 ? 2 : depth <= 5 ? 4 : 8; }     // CV_8U .. CV_64F
 inline int divUp(int a, int b) { return (a + b - 1) / b; }
+inline int envInt(const char* name, int dflt) { const char* v = getenv(name); return v ? atoi(v) : dflt; }           // an A/B switch; `static const int x = envInt(...)` reads it once per process
 inline size_t pad256(size_t b) { return (b + 255) & ~size_t(255); }                                                  // b bytes rounded up to 256: the start of the next array in a scratch block, a staged row's pitch
 inline size_t span(size_t step, int rows, size_t rowBytes) { return (size_t)(rows - 1) * step + rowBytes; }          // bytes from the first byte of an image to one past its last
 

@@ -888,7 +888,7 @@ MI355_HD void leanRows(const Args& a, const LBox& b, int x0, int y0, const unsig
 
 inline void leanGeometry(Args& a, int cn);
 
-// ---- bilinear resize of 8-bit images on the lean kernel's machinery (k_resize8_lean) -----------------------------------------------------------------------
+// ---- bilinear resize of 8-bit images on the lean kernel's machinery (k_resize8_lean, resize.hip) -----------------------------------------------------------
 // cv::resize INTER_LINEAR on CV_8U (resize.cpp: HResizeLinear + VResizeLinear<uchar, int, short, FixedPtCast<int, uchar, 22>>): coefficients of 11 bits,
 //   t = p0 a0 + p1 a1 per tap row,  pixel = (((b0 (t0 >> 4)) >> 16) + ((b1 (t1 >> 4)) >> 16) + 2) >> 2.
 // An axis-aligned map needs no per-pixel coordinate arithmetic at all: a pixel's LDS offset is (row part) + (column part), both from per-call tables
@@ -1066,7 +1066,11 @@ inline bool planResize(Args& a, int cn, int sw, int sh, int dw, int dh, size_t s
 }
 
 // the lean kernels' staging geometry for a call whose LDS box is ldsPitch x ldsRows: LW threads per box row (the row's dwords, a power of two), 256 / LW rows
-// per round, NR rounds in registers; two LDS buffers within the 64 KB a workgroup may ask for
+// per round, NR rounds in registers; two LDS buffers within the 64 KB a workgroup may ask for.  WARP8_LEAN_SHAPES(X) expands X(CN, LW, NR) for every (channels, leanLW,
+// leanNR) it can answer: the instantiations of k_warp8_lean (warp.hip) and k_resize8_lean (resize.hip)
+#define WARP8_LEAN_NRS(X, CN, LW) X(CN, LW, 6); X(CN, LW, 10); X(CN, LW, 14); X(CN, LW, 20)
+#define WARP8_LEAN_SHAPES(X) WARP8_LEAN_NRS(X, 1, 16); WARP8_LEAN_NRS(X, 1, 32); WARP8_LEAN_NRS(X, 1, 64); \
+                             WARP8_LEAN_NRS(X, 3, 32); WARP8_LEAN_NRS(X, 3, 64); WARP8_LEAN_NRS(X, 3, 128); WARP8_LEAN_NRS(X, 3, 256)
 inline void leanGeometry(Args& a, int cn)
 {
     a.leanLW = a.leanNR = 0;
@@ -1075,7 +1079,7 @@ inline void leanGeometry(Args& a, int cn)
     if (lw > 256) return;
     const int rounds = (a.ldsRows + 256 / lw - 1) / (256 / lw);
     const int nr = rounds <= 6 ? 6 : rounds <= 10 ? 10 : rounds <= 14 ? 14 : rounds <= 20 ? 20 : 0;
-    if (!nr || (cn == 1 && lw > 64) || (cn == 3 && lw < 32)) return;                   // (the instantiated combinations)
+    if (!nr || (cn == 1 && lw > 64) || (cn == 3 && lw < 32)) return;                   // (the instantiated combinations: WARP8_LEAN_SHAPES)
     a.leanBuf = ((uint32_t)a.ldsPitch * (uint32_t)a.ldsRows + 15u) & ~15u;
     if (2 * (size_t)a.leanBuf > 64 * 1024) return;
     a.leanLW = lw; a.leanNR = nr;

@@ -14,7 +14,7 @@ HIPCC = "/opt/rocm/bin/hipcc"
 
 
 @pytest.mark.skipif(not os.path.exists(HIPCC) and shutil.which("hipcc") is None, reason="no hipcc")
-@pytest.mark.parametrize("source", ["warp.hip"])
+@pytest.mark.parametrize("source", ["warp.hip", "resize.hip"])
 def test_no_ashr_pk_u8_in_the_packing_kernels(source):
     obj = os.path.join(ROOT, "opencv_amd", "csrc", "build", source.replace(".hip", ".o"))
     llvm = "/opt/rocm/lib/llvm/bin"

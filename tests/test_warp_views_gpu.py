@@ -129,7 +129,7 @@ resize_row("cubic x 2", 2, U8, 1, up2, 109, compare=same_values, kernel="k_resiz
 resize_row("cubic x 2", 2, U8, 3, up2, 110, compare=same_values, kernel="k_resize_tab8<4>")
 resize_row("cubic x 2", 2, F32, 1, up2, 111, compare=same_values)
 resize_row("cubic x 2", 2, U16, 3, up2, 112, compare=same_values)
-# Lanczos CV_8U: k_resize_tab8<8> is opt-in (MI355CV_RESIZE_TAB8=1, read once per process: warp.hip runResize, tab8); what serves it by default is the tiled kernel
+# Lanczos CV_8U: k_resize_tab8<8> is opt-in (MI355CV_RESIZE_TAB8=1, read once per process: resize.hip cubicLanczos, tab8); what serves it by default is the tiled kernel
 resize_row("Lanczos x 2", 4, U8, 1, up2, 113, compare=same_values, kernel="k_resize_tiled<depth 0,8>")
 resize_row("Lanczos x 2", 4, F32, 1, up2, 114, compare=same_values)
 resize_row("LINEAR_EXACT x 3/2", 5, U8, 3, three2, 115, compare=same_values, kernel="k_resize_exact")
