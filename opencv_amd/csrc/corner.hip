@@ -16,6 +16,7 @@
 //     including the tabR column stepping of :897-910 for non-default dsize.
 #include "rt.h"
 #include "roll.h"
+#include "deriv_taps.h"
 #include <algorithm>
 #include <cmath>
 #include <cstring>
@@ -839,21 +840,6 @@ __global__ __launch_bounds__(256) void k_harris_roll_p(const uchar* __restrict__
     walk(std::integral_constant<bool, FAST>{});
 }
 
-bool derivTaps(int order, int ksize, bool scharr, std::vector<int>& k)
-{
-    if (scharr) { if (order == 0) k = {3, 10, 3}; else k = {-1, 0, 1}; return true; }
-    if (ksize == 1 && order > 0) ksize = 3;
-    if (ksize % 2 == 0 || ksize > 7 || ksize <= order) return false;
-    if (ksize == 1) { k = {1}; return true; }
-    if (ksize == 3) { if (order == 0) k = {1, 2, 1}; else k = {-1, 0, 1}; return true; }
-    std::vector<int> kerI(ksize + 1, 0);
-    kerI[0] = 1;
-    for (int i = 0; i < ksize - order - 1; i++) { int ov = kerI[0]; for (int j = 1; j <= ksize; j++) { int nv = kerI[j] + kerI[j - 1]; kerI[j - 1] = ov; ov = nv; } }
-    for (int i = 0; i < order; i++) { int ov = -kerI[0]; for (int j = 1; j <= ksize; j++) { int nv = kerI[j - 1] - kerI[j]; kerI[j - 1] = ov; ov = nv; } }
-    k.assign(kerI.begin(), kerI.begin() + ksize);
-    return true;
-}
-
 int launchCorner(const uchar* ds, size_t dss, size_t sframe, uchar* dd, size_t dds, size_t dframe, int nframes,
                  int W, int H, int sdepth, int blockSize, int ksize, double k, int border, bool harris, hipStream_t st)
 {
@@ -868,7 +854,8 @@ int launchCorner(const uchar* ds, size_t dss, size_t sframe, uchar* dd, size_t d
     std::vector<int> d1, s0x, s0y;
     // Dx = Sobel(1,0): kx = derivative taps, ky = smoothing taps * scale; Dy = Sobel(0,1): kx = smoothing * scale, ky = derivative
     std::vector<int> dxr, dxc, dyr, dyc;
-    MI355_DECLINE_IF(!derivTaps(1, ksize, scharr, dxr) || !derivTaps(0, ksize, scharr, dxc) || !derivTaps(0, ksize, scharr, dyr) || !derivTaps(1, ksize, scharr, dyc));
+    // (only orders 0 and 1 are asked for, so derivKernel's refusal of a Scharr order above 1 never shows here; ksize up to 7: CornerArgs holds 8 taps per kernel)
+    MI355_DECLINE_IF(!derivKernel(1, ksize, scharr, 7, dxr) || !derivKernel(0, ksize, scharr, 7, dxc) || !derivKernel(0, ksize, scharr, 7, dyr) || !derivKernel(1, ksize, scharr, 7, dyc));
     a.dxNRow = (int)dxr.size(); a.dxNCol = (int)dxc.size(); a.dyNRow = (int)dyr.size(); a.dyNCol = (int)dyc.size();
     for (int i = 0; i < a.dxNRow; i++) a.dxRow[i] = (float)dxr[i];
     for (int i = 0; i < a.dxNCol; i++) a.dxCol[i] = (float)((double)dxc[i] * scale);     // `ky *= scale` (dx != 0)

@@ -16,15 +16,21 @@
 //  * Sobel / Scharr (deriv.cpp:87 getSobelKernels, :55 getScharrKernels, :414 cv::Sobel): kernels generated as the
 //    reference does, `scale` folded into the smoothing kernel, then the separable engine.
 //
-// The kernels in this file are the GENERAL path: one thread per output element, taps read through L1/L2.  They are
-// correct for every depth/border/anchor/ROI combination above.  The 4K 8U 3x3 configuration of BASELINE.json has
-// its own fast path (TODO next round: register-rolling 3x3).
-#include "rt.h"
+// What is in this file:
+//  * kernels: the generic ones (k_filter2d_generic, k_sepfilter_generic<MAXK> and their CV_64F forms) -- one thread per output element, taps read through L1/L2, correct
+//    for every depth / border / anchor / ROI combination above --, the LDS tile of filter2D (k_filter2d_tile), and filter2D on the register-rolling skeleton of roll.h
+//    (k_filter2d_roll 3x3 / 5x5 on CV_8U, k_filter2d_roll_f32, and k_gray_filter2d_roll: cvtColor to gray + filter2D in one pass).  The rolling and LDS-ring kernels of
+//    the separable engine live in seproll.hip and seplong.hip.
+//  * host: the contexts of the *Init hooks (FilterCtx), and per family ONE ordered list of served paths -- sepServe (sepFilter2D, Sobel, Scharr) and filterServe
+//    (filter2D) -- that the single-image hook and the batch entry both call with a description of their images (filter_common.h CallImages).  The two entries of a
+//    family differ in their front halves only: the hook applies the host policy and stages the parent region, the batch entry wants device-resident frames.
+// cv::boxFilter (row a5) is box.hip.
+#include "filter_common.h"
 #include <climits>
 #include "roll.h"
 #include "seproll.h"
 #include "seplong.h"
-#include "sepmx.h"
+#include "deriv_taps.h"
 #include <cmath>
 #include <cstring>
 #include <new>
@@ -34,8 +40,7 @@ using namespace mi355;
 
 namespace {
 
-enum { D8U = MI355CV_8U, D16U = MI355CV_16U, D16S = MI355CV_16S, D32F = MI355CV_32F, D64F = MI355CV_64F };
-
+// (the store that goes with it, stF, is in filter_common.h: the box kernels finish through it too)
 __device__ __forceinline__ float ldF(const uchar* row, int idx, int depth)
 {
     switch (depth) {
@@ -43,17 +48,6 @@ __device__ __forceinline__ float ldF(const uchar* row, int idx, int depth)
     case D16U: return (float)reinterpret_cast<const unsigned short*>(row)[idx];
     case D16S: return (float)reinterpret_cast<const short*>(row)[idx];
     default:   return reinterpret_cast<const float*>(row)[idx];
-    }
-}
-
-// saturate_cast<DT>(float): cvRound (round-half-even) then clamp (core/saturate.hpp:103-142)
-__device__ __forceinline__ void stF(uchar* row, int idx, int depth, float s)
-{
-    switch (depth) {
-    case D8U:  { float r = rintf(s); r = fminf(fmaxf(r, 0.f), 255.f); row[idx] = (uchar)(int)r; break; }
-    case D16U: { float r = rintf(s); r = fminf(fmaxf(r, 0.f), 65535.f); reinterpret_cast<unsigned short*>(row)[idx] = (unsigned short)(int)r; break; }
-    case D16S: { float r = rintf(s); r = fminf(fmaxf(r, -32768.f), 32767.f); reinterpret_cast<short*>(row)[idx] = (short)(int)r; break; }
-    default:   reinterpret_cast<float*>(row)[idx] = s;
     }
 }
 
@@ -635,203 +629,8 @@ __global__ __launch_bounds__(256) void k_sepfilter_generic64(
     reinterpret_cast<double*>(dst + (size_t)y * dstep)[e] = s;
 }
 
-// ---------------------------------------------------------------------------------- box filter (row a5)
-// cv::boxFilter (box_filter.dispatch.cpp:440, createBoxFilter box_filter.simd.hpp:1250):
-//   8U->8U, area <= 256 : u16 sums; normalised result = ((s + dd) * ds) >> 23 with the reciprocal pair (ds, dd) of
-//                         ColumnSum<ushort,uchar> (:429-455); un-normalised = saturate_u8(s)
-//   other integer inputs: int32 sums; normalised = cvRound(float(s) * float(1/area)) (the SIMD body of
-//                         ColumnSum<int,uchar> :340-372), un-normalised = saturate(s)
-//   float input         : double sums (RowSum<float,double>, ColumnSum<double,float>), result = float(s * scale)
-struct BoxParams { int kw, kh, ax, ay, normalize, mode /*0 u16, 1 int, 2 double*/, divScale, divDelta; float scaleF; double scaleD; };
-
-__global__ __launch_bounds__(256) void k_box_generic(
-    const uchar* __restrict__ src, size_t sstep, uchar* __restrict__ dst, size_t dstep,
-    int W, int H, int cn, int sdepth, int ddepth, int fullW, int fullH, int offX, int offY, int border, BoxParams p)
-{
-    const int e = blockIdx.x * 64 + (threadIdx.x & 63);
-    const int y = blockIdx.y * 4 + (threadIdx.x >> 6);
-    if (e >= W * cn || y >= H) return;
-    const int x = e / cn, ch = e - x * cn;
-    const int fx0 = x + offX - p.ax, fy0 = y + offY - p.ay;
-    uchar* drow = dst + (size_t)y * dstep;
-    if (p.mode == 2) {
-        double s = 0.0;
-        for (int j = 0; j < p.kh; j++) {
-            const int yy = mi355_borderInterpolate(fy0 + j, fullH, border);
-            if (yy < 0) continue;
-            const uchar* row = src + (ptrdiff_t)(yy - offY) * (ptrdiff_t)sstep;
-            double rs = 0.0;
-            for (int i = 0; i < p.kw; i++) {
-                const int xx = mi355_borderInterpolate(fx0 + i, fullW, border);
-                if (xx >= 0) rs += sdepth == D64F ? reinterpret_cast<const double*>(row)[(xx - offX) * cn + ch] : (double)reinterpret_cast<const float*>(row)[(xx - offX) * cn + ch];
-            }
-            s += rs;
-        }
-        if (ddepth == D64F) reinterpret_cast<double*>(drow)[e] = p.normalize ? s * p.scaleD : s;
-        else reinterpret_cast<float*>(drow)[e] = (float)(p.normalize ? s * p.scaleD : s);
-        return;
-    }
-    int s = 0;
-    for (int j = 0; j < p.kh; j++) {
-        const int yy = mi355_borderInterpolate(fy0 + j, fullH, border);
-        if (yy < 0) continue;
-        const uchar* row = src + (ptrdiff_t)(yy - offY) * (ptrdiff_t)sstep;
-        for (int i = 0; i < p.kw; i++) {
-            const int xx = mi355_borderInterpolate(fx0 + i, fullW, border);
-            if (xx < 0) continue;
-            const int idx = (xx - offX) * cn + ch;
-            s += sdepth == D8U ? (int)row[idx] : sdepth == D16U ? (int)reinterpret_cast<const unsigned short*>(row)[idx]
-                                                              : (int)reinterpret_cast<const short*>(row)[idx];
-        }
-    }
-    if (p.mode == 0) {
-        unsigned r = p.normalize ? (((unsigned)s + (unsigned)p.divDelta) * (unsigned)p.divScale) >> 23 : (unsigned)s;
-        drow[e] = (uchar)(p.normalize ? r : (r > 255u ? 255u : r));
-        return;
-    }
-    if (ddepth == D64F) {           // ColumnSum<int, double> (box_filter.simd.hpp:1195-1240): the exact int sum, one multiply in double
-        reinterpret_cast<double*>(drow)[e] = p.normalize ? (double)s * p.scaleD : (double)s;
-        return;
-    }
-    if (ddepth == D32F) {
-        // ColumnSum<int, float> (box_filter.simd.hpp:1109-1130): the vector body multiplies in float, the last (W*cn) % 4 elements of a row in double
-        reinterpret_cast<float*>(drow)[e] = !p.normalize ? (float)s : e < ((W * cn) & ~3) ? __fmul_rn((float)s, p.scaleF) : (float)((double)s * p.scaleD);
-        return;
-    }
-    if (p.normalize && e >= ((W * cn) & ~7)) {
-        // the reference's scalar tail (the last (W*cn) % 8 elements of a row, box_filter.simd.hpp:380-385) multiplies in double
-        const double r = rint((double)s * p.scaleD);
-        if (ddepth == D8U) drow[e] = (uchar)(int)fmin(fmax(r, 0.0), 255.0);
-        else if (ddepth == D16U) reinterpret_cast<unsigned short*>(drow)[e] = (unsigned short)(int)fmin(fmax(r, 0.0), 65535.0);
-        else reinterpret_cast<short*>(drow)[e] = (short)(int)fmin(fmax(r, -32768.0), 32767.0);
-        return;
-    }
-    float v = p.normalize ? rintf((float)s * p.scaleF) : (float)s;
-    stF(drow, e, ddepth, v);
-}
-
-// ---------------------------------------------------------------------------------- box filter in two passes (what neither the rolling kernels nor k_sepmx take)
-// RowSum then ColumnSum like the reference (box_filter.simd.hpp:60-180, 182-1240) instead of k_box_generic's kw * kh gathers per output (a 121 x 121 window of a guided
-// filter on a 4K float frame: 14 641 loads per element, slower than the CPU's running sums):
-//   k_box_rows   window sums along x of every parent row the call touches, into a scratch image of int (integer sources: exact) or double (float sources: the reference's
-//                sum type) -- a workgroup stages 1024 + kw - 1 values of one channel of one row in LDS (border rule resolved there), a lane takes 4 neighbouring windows:
-//                one sum of kw values, three slides;
-//   k_box_cols   a lane owns an output column and walks down a segment with the running column sum (add the row entering, subtract the row leaving -- ColumnSum's own
-//                recurrence), and finishes every sum exactly as k_box_generic does (the reference's normalisations per depth pair).
-// Integer results are those of k_box_generic bit for bit; double sums differ from it in the last bits of the DOUBLE (the order of the additions), i.e. not at all after
-// the rounding to float in all but isolated elements -- the float bar of the path is 1e-4.
-template <typename SUM> struct BoxStage { typedef int L; };
-template <> struct BoxStage<double> { typedef float L; };
-
-template <typename ST, typename SUM>
-__global__ __launch_bounds__(256) void k_box_rows(const uchar* __restrict__ src, size_t sstep, SUM* __restrict__ R, size_t rpitch, int W, int cn, int fullW, int offX, int offY,
-                                                  int r0, int kw, int ax, int border)
-{
-    typedef typename BoxStage<SUM>::L LT;
-    extern __shared__ __attribute__((aligned(16))) uchar boxlds_[];
-    LT* L = reinterpret_cast<LT*>(boxlds_);
-    const int tid = threadIdx.x, ch = blockIdx.z, prow = r0 + blockIdx.y, xb = blockIdx.x * 1024;
-    const ST* row = reinterpret_cast<const ST*>(src + (ptrdiff_t)(prow - offY) * (ptrdiff_t)sstep);
-    const int nout = min(1024, W - xb), nst = nout + kw + 3;
-    for (int j = tid; j < nst; j += 256) {
-        int fx = xb + j + offX - ax;
-        if ((unsigned)fx >= (unsigned)fullW) fx = mi355_borderInterpolate(fx, fullW, border);
-        L[j] = (fx >= 0 && j < nout + kw - 1) ? (LT)row[(fx - offX) * cn + ch] : (LT)0;
-    }
-    __syncthreads();
-    const int x = 4 * tid;
-    if (x >= nout) return;
-    typedef LT l4 __attribute__((ext_vector_type(4)));
-    const LT* q = L + x;
-    SUM s = 0;
-    int t = 0;
-    for (; t + 4 <= kw; t += 4) { const l4 v = *reinterpret_cast<const l4*>(q + t); s += (SUM)v.x; s += (SUM)v.y; s += (SUM)v.z; s += (SUM)v.w; }
-    for (; t < kw; t++) s += (SUM)q[t];
-    SUM* out = R + (size_t)blockIdx.y * rpitch + (size_t)(xb + x) * cn + ch;
-    out[0] = s;
-#pragma unroll
-    for (int i = 1; i < 4; i++) {
-        if (x + i >= nout) break;
-        s += (SUM)q[kw + i - 1]; s -= (SUM)q[i - 1];
-        out[(size_t)i * cn] = s;
-    }
-}
-
-template <typename SUM>
-__device__ __forceinline__ void boxFinish(uchar* drow, int e, SUM s, int W, int cn, int ddepth, const BoxParams& p);
-template <>
-__device__ __forceinline__ void boxFinish<double>(uchar* drow, int e, double s, int W, int cn, int ddepth, const BoxParams& p)
-{
-    if (ddepth == D64F) reinterpret_cast<double*>(drow)[e] = p.normalize ? s * p.scaleD : s;
-    else reinterpret_cast<float*>(drow)[e] = (float)(p.normalize ? s * p.scaleD : s);
-}
-template <>
-__device__ __forceinline__ void boxFinish<int>(uchar* drow, int e, int s, int W, int cn, int ddepth, const BoxParams& p)
-{
-    if (p.mode == 0) {
-        unsigned r = p.normalize ? (((unsigned)s + (unsigned)p.divDelta) * (unsigned)p.divScale) >> 23 : (unsigned)s;
-        drow[e] = (uchar)(p.normalize ? r : (r > 255u ? 255u : r));
-        return;
-    }
-    if (ddepth == D64F) { reinterpret_cast<double*>(drow)[e] = p.normalize ? (double)s * p.scaleD : (double)s; return; }
-    if (ddepth == D32F) { reinterpret_cast<float*>(drow)[e] = !p.normalize ? (float)s : e < ((W * cn) & ~3) ? __fmul_rn((float)s, p.scaleF) : (float)((double)s * p.scaleD); return; }
-    if (p.normalize && e >= ((W * cn) & ~7)) {
-        const double r = rint((double)s * p.scaleD);
-        if (ddepth == D8U) drow[e] = (uchar)(int)fmin(fmax(r, 0.0), 255.0);
-        else if (ddepth == D16U) reinterpret_cast<unsigned short*>(drow)[e] = (unsigned short)(int)fmin(fmax(r, 0.0), 65535.0);
-        else reinterpret_cast<short*>(drow)[e] = (short)(int)fmin(fmax(r, -32768.0), 32767.0);
-        return;
-    }
-    const float v = p.normalize ? rintf((float)s * p.scaleF) : (float)s;
-    stF(drow, e, ddepth, v);
-}
-
-template <typename SUM>
-__global__ __launch_bounds__(256) void k_box_cols(const SUM* __restrict__ R, size_t rpitch, int r0, uchar* __restrict__ dst, size_t dstep, int W, int H, int cn, int ddepth,
-                                                  int fullH, int offY, int border, BoxParams p, int seg)
-{
-    const int e = blockIdx.x * 256 + threadIdx.x;
-    if (e >= W * cn) return;
-    const int y0 = blockIdx.y * seg, y1 = min(H, y0 + seg);
-    auto rowSum = [&](int fy) -> SUM {                                                 // (fy is uniform: the row's address is scalar work)
-        if ((unsigned)fy >= (unsigned)fullH) fy = mi355_borderInterpolate(fy, fullH, border);
-        return fy < 0 ? (SUM)0 : R[(size_t)(fy - r0) * rpitch + e];
-    };
-    SUM s = 0;
-    for (int j = 0; j < p.kh; j++) s += rowSum(y0 + offY - p.ay + j);
-    for (int y = y0; y < y1; y++) {
-        boxFinish<SUM>(dst + (size_t)y * dstep, e, s, W, cn, ddepth, p);
-        if (y + 1 < y1) { s += rowSum(y + 1 + offY - p.ay + p.kh - 1); s -= rowSum(y + offY - p.ay); }
-    }
-}
-
-// the two-pass box filter (k_box_rows / k_box_cols) for one image; false: not its case (the caller falls back to k_box_generic)
-// parent rows the windows can touch: the window's own rows, and what a mirroring border rule folds back into them; BORDER_WRAP reaches across the image
-static void boxRowRange(int H, int kh, int fullH, int offY, int border, int* r0, int* r1)
-{
-    *r0 = std::max(0, offY - kh); *r1 = std::min(fullH, offY + H + kh);
-    if (border == B_WRAP) { *r0 = 0; *r1 = fullH; }
-}
-
-template <typename ST, typename SUM>
-static bool boxTwoPassT(void* scratch, const BoxParams& p, const uchar* src, size_t sstep, uchar* dst, size_t dstep, int W, int H, int cn, int ddepth,
-                        int fullW, int fullH, int offX, int offY, int border, hipStream_t st)
-{
-    int r0, r1;
-    boxRowRange(H, p.kh, fullH, offY, border, &r0, &r1);
-    const int nr = r1 - r0;
-    const size_t rpitch = ((size_t)W * cn + 3) & ~(size_t)3;
-    SUM* R = (SUM*)scratch;
-    const size_t lds = (size_t)(1024 + p.kw + 8) * 4;
-    hipLaunchKernelGGL((k_box_rows<ST, SUM>), dim3(divUp(W, 1024), nr, cn), dim3(256), lds, st, src, sstep, R, rpitch, W, cn, fullW, offX, offY, r0, p.kw, p.ax, border);
-    const int seg = 32;
-    hipLaunchKernelGGL((k_box_cols<SUM>), dim3(divUp(W * cn, 256), divUp(H, seg)), dim3(256), 0, st, R, rpitch, r0, dst, dstep, W, H, cn, ddepth, fullH, offY, border, p, seg);
-    return true;
-}
 
 // ---------------------------------------------------------------------------------- host: contexts
-int depthSize(int d) { return d == D8U ? 1 : (d == D16U || d == D16S) ? 2 : d == D32F ? 4 : d == D64F ? 8 : 0; }
-
 double kernelAt(const uchar* data, size_t step, int type, int r, int c)
 {
     const uchar* p = data + (size_t)r * step;
@@ -982,13 +781,59 @@ int sepInit(FilterCtx& c, int stype, int dtype, const std::vector<double>& kx, c
 }
 
 // the LDS-ring kernel for everything the rolling kernels do not take (seplong.hip): any tap count, anchor, border, 1-4 channels
-bool sepLong(Stager& stg, const FilterCtx& c, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes,
-             int W, int H, int fullW, int fullH, int offX, int offY)
+bool sepLong(Stager& stg, const FilterCtx& c, const CallImages& im)
 {
     const SepLongTaps t = {c.lkxf.data(), c.lkyf.data(), c.lkxi.data(), c.lkyi.data(), c.lnx, c.lny, c.ax, c.ay, c.lmode, c.lsymY, c.ldeltaF, c.ldeltaI};
-    return seplongRun(stg, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, c.cn, c.sdepth, c.ddepth, fullW, fullH, offX, offY, c.border, t, stream());
+    return seplongRun(stg, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, c.cn, c.sdepth, c.ddepth, im.fullW, im.fullH, im.offX, im.offY, c.border, t, stream());
 }
 
+// the served paths of the separable engine in order, for the hook's image and for a batch alike: the first that takes the call launches it (the rolling and LDS-ring
+// kernels take the frames in one launch, the generic kernels go frame by frame; all in stream order, one synchronisation at most)
+int sepServe(Stager& stg, const char* entry, const FilterCtx& c, const CallImages& im)
+{
+    const dim3 grid(divUp(im.W * c.cn, 64), divUp(im.H, 4));           // of the generic kernels
+    if (c.wide) {                                // CV_64F destinations: the generic double kernel
+        for (int f = 0; f < im.nframes; f++)
+            hipLaunchKernelGGL(k_sepfilter_generic64, grid, dim3(256), 0, stream(), im.src + (size_t)f * im.sframe, im.sstep, im.dst + (size_t)f * im.dframe, im.dstep,
+                               im.W, im.H, c.cn, c.sdepth, im.fullW, im.fullH, im.offX, im.offY, c.border, c.sp64);
+        noteKernel("k_sepfilter_generic64 (depth %d -> CV_64F, %d x %d taps)", c.sdepth, c.sp64.nx, c.sp64.ny);
+        return stg.finish(entry);
+    }
+    if (c.big) {                                 // 34 .. lim::SEP_MAX_TAPS taps: the LDS-ring kernel, frames along grid z
+        if (!sepLong(stg, c, im)) return MI355_DECLINED("seplongRun refused a kernel beyond 33 taps");
+        return stg.finish(entry);
+    }
+    const SepParams& p = c.sp;
+    // a submatrix with real pixels around it stays on the rolling kernels: they run on the parent's geometry and store the window (roll.h Win)
+    const Roi roiv = {im.fullW, im.fullH, im.offX, im.offY};
+    const Roi* roi = im.whole() ? nullptr : &roiv;
+    const bool centred = p.nx == p.ny && p.ax == p.nx / 2 && p.ay == p.ny / 2;
+    if (p.mode == 2 && c.ddepth == D16S && centred && p.deltaI == 0 &&
+        seprollDeriv16(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, c.cn, p.kxi, p.kyi, p.nx, c.border, stream(), roi))
+        return stg.finish(entry);
+    if (p.mode == 1 && c.sdepth == D8U && c.ddepth == D8U && centred && p.ny > 1 &&
+        seprollFix8U(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, c.cn, p.kxi, p.kyi, p.nx, p.deltaF, c.border, stream(), roi))
+        return stg.finish(entry);
+    if (p.mode == 0 && c.sdepth == D8U && (c.ddepth == D32F || c.ddepth == D8U) && centred &&
+        seprollFloat(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, c.cn, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.ddepth == D32F ? 4 : 1, c.border, stream(), roi))
+        return stg.finish(entry);
+    if (p.mode == 0 && c.sdepth == D32F && c.ddepth == D32F && c.cn == 1 && centred &&
+        seprollF32(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream(), roi))
+        return stg.finish(entry);
+    if (p.mode == 0 && (c.sdepth == D16U || c.sdepth == D16S) && (c.ddepth == c.sdepth || c.ddepth == D32F) && c.cn == 1 && centred &&
+        seprollF16(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.nframes, im.W, im.H, c.sdepth == D16S, c.ddepth == D32F, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream(), roi))
+        return stg.finish(entry);
+    // everything else with 1-4 channels: the LDS-ring kernel, nx + ny multiply-adds per element
+    if (std::getenv("MI355CV_SEP_GENERIC") == nullptr && sepLong(stg, c, im)) return stg.finish(entry);
+    // more than 4 channels (at most 33 taps, sepInit): one thread per output element, nx * ny gathers -- the correctness path of cv::sepFilter2D on exotic Mats
+    for (int f = 0; f < im.nframes; f++)
+        hipLaunchKernelGGL((k_sepfilter_generic<33>), grid, dim3(256), 0, stream(), im.src + (size_t)f * im.sframe, im.sstep, im.dst + (size_t)f * im.dframe, im.dstep,
+                           im.W, im.H, c.cn, c.sdepth, c.ddepth, im.fullW, im.fullH, im.offX, im.offY, c.border, c.sp);
+    noteKernel("k_sepfilter_generic<33> (%d x %d taps, %d channels)", c.sp.nx, c.sp.ny, c.cn);
+    return stg.finish(entry);
+}
+
+// the hook: one image (host or device) that may be a window of a larger one
 int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep, uchar* dst, size_t dstep,
            int W, int H, int fullW, int fullH, int offX, int offY)
 {
@@ -996,131 +841,33 @@ int sepRun(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice());
     MI355_DECLINE_IF(hostImageTooSmall(src, (size_t)W * H, minPixels(HOST_HEAVY)));
-    const int se = depthSize(c.sdepth), de = depthSize(c.ddepth);
+    const int se = depthBytes(c.sdepth), de = depthBytes(c.ddepth);
     // stage the whole parent region so that non-isolated borders can read real neighbours
     const uchar* top = src - (ptrdiff_t)offY * (ptrdiff_t)sstep - (ptrdiff_t)offX * c.cn * se;
-    if (overlapOnDevice(top, (size_t)(fullH - 1) * sstep + (size_t)fullW * c.cn * se, dst, (size_t)(H - 1) * dstep + (size_t)W * c.cn * de))
+    if (overlapOnDevice(top, span(sstep, fullH, (size_t)fullW * c.cn * se), dst, span(dstep, H, (size_t)W * c.cn * de)))
         return setError(MI355CV_NOT_IMPLEMENTED, "%s: dst overlaps the device-resident source rows (in-place)", entry);
     size_t dss, dds;
     const uchar* dtop = stg.in(top, sstep, (size_t)fullW * c.cn * se, fullH, &dss);
     uchar* dd = stg.out(dst, dstep, (size_t)W * c.cn * de, H, &dds);
     MI355_DECLINE_IF(!dtop || !dd);
-    const uchar* ds = dtop + (size_t)offY * dss + (size_t)offX * c.cn * se;
-    if (c.wide) {
-        hipLaunchKernelGGL(k_sepfilter_generic64, dim3(divUp(W * c.cn, 64), divUp(H, 4)), dim3(256), 0, stream(), ds, dss, dd, dds, W, H, c.cn, c.sdepth,
-                           fullW, fullH, offX, offY, c.border, c.sp64);
-        noteKernel("k_sepfilter_generic64 (depth %d -> CV_64F, %d x %d taps)", c.sdepth, c.sp64.nx, c.sp64.ny);
-        return stg.finish(entry);
-    }
-    if (c.big) {
-        if (!sepLong(stg, c, ds, dss, 0, dd, dds, 0, 1, W, H, fullW, fullH, offX, offY)) return MI355_DECLINED("seplongRun refused a kernel beyond 33 taps");
-        return stg.finish(entry);
-    }
-    const SepParams& p = c.sp;
-    // a submatrix with real pixels around it stays on the rolling kernels: they run on the parent's geometry and store the window (roll.h Win)
-    const Roi roiv = {fullW, fullH, offX, offY};
-    const Roi* roi = (fullW != W || fullH != H) ? &roiv : nullptr;
-    const bool centred = p.nx == p.ny && p.ax == p.nx / 2 && p.ay == p.ny / 2;
-    if (p.mode == 2 && c.ddepth == D16S && centred && p.deltaI == 0 &&
-        seprollDeriv16(ds, dss, 0, dd, dds, 0, 1, W, H, c.cn, p.kxi, p.kyi, p.nx, c.border, stream(), roi))
-        return stg.finish(entry);
-    if (p.mode == 1 && c.sdepth == D8U && c.ddepth == D8U && centred && p.ny > 1 &&
-        seprollFix8U(ds, dss, 0, dd, dds, 0, 1, W, H, c.cn, p.kxi, p.kyi, p.nx, p.deltaF, c.border, stream(), roi))
-        return stg.finish(entry);
-    if (p.mode == 0 && c.sdepth == D8U && (c.ddepth == D32F || c.ddepth == D8U) && centred &&
-        seprollFloat(ds, dss, 0, dd, dds, 0, 1, W, H, c.cn, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.ddepth == D32F ? 4 : 1, c.border, stream(), roi))
-        return stg.finish(entry);
-    if (p.mode == 0 && c.sdepth == D32F && c.ddepth == D32F && c.cn == 1 && centred &&
-        seprollF32(ds, dss, 0, dd, dds, 0, 1, W, H, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream(), roi))
-        return stg.finish(entry);
-    if (p.mode == 0 && (c.sdepth == D16U || c.sdepth == D16S) && (c.ddepth == c.sdepth || c.ddepth == D32F) && c.cn == 1 && centred &&
-        seprollF16(ds, dss, 0, dd, dds, 0, 1, W, H, c.sdepth == D16S, c.ddepth == D32F, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream(), roi))
-        return stg.finish(entry);
-    // everything else with 1-4 channels: the LDS-ring kernel, nx + ny multiply-adds per element
-    if (std::getenv("MI355CV_SEP_GENERIC") == nullptr && sepLong(stg, c, ds, dss, 0, dd, dds, 0, 1, W, H, fullW, fullH, offX, offY)) return stg.finish(entry);
-    // more than 4 channels (at most 33 taps, sepInit): one thread per output element, nx * ny gathers -- the correctness path of cv::sepFilter2D on exotic Mats
-    dim3 grid(divUp(W * c.cn, 64), divUp(H, 4));
-    hipLaunchKernelGGL((k_sepfilter_generic<33>), grid, dim3(256), 0, stream(), ds, dss, dd, dds, W, H, c.cn, c.sdepth, c.ddepth,
-                       fullW, fullH, offX, offY, c.border, c.sp);
-    noteKernel("k_sepfilter_generic<33> (%d x %d taps, %d channels)", c.sp.nx, c.sp.ny, c.cn);
-    return stg.finish(entry);
+    const CallImages im = {dtop + (size_t)offY * dss + (size_t)offX * c.cn * se, dss, 0, dd, dds, 0, 1, W, H, fullW, fullH, offX, offY};
+    return sepServe(stg, entry, c, im);
 }
 
-// the same over a batch of device-resident whole frames (every frame its own image: isolated borders): one launch of the rolling kernels
-// where they apply, the generic kernel frame by frame otherwise (all in stream order, one synchronisation at most)
+// a batch of device-resident whole frames (every frame its own image: isolated borders)
 int sepRunBatch(const char* entry, const FilterCtx& c, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes, int W, int H)
 {
     MI355_DECLINE_IF(disabled() || W <= 0 || H <= 0 || nframes < 1);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice());
     if (!isDevicePtr(src) || !isDevicePtr(dst)) return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
-    const int se = depthSize(c.sdepth), de = depthSize(c.ddepth);
-    // one check for every path below, the CV_64F and long-kernel ones included (they used to launch before it)
-    if (overlapOnDevice(src, (size_t)(nframes - 1) * sframe + (size_t)(H - 1) * sstep + (size_t)W * c.cn * se,
-                        dst, (size_t)(nframes - 1) * dframe + (size_t)(H - 1) * dstep + (size_t)W * c.cn * de))
+    const int se = depthBytes(c.sdepth), de = depthBytes(c.ddepth);
+    // one check for every path of the chain: nothing is launched ahead of it
+    if (overlapOnDevice(src, (size_t)(nframes - 1) * sframe + span(sstep, H, (size_t)W * c.cn * se), dst, (size_t)(nframes - 1) * dframe + span(dstep, H, (size_t)W * c.cn * de)))
         return setError(MI355CV_NOT_IMPLEMENTED, "%s: dst overlaps the source frames (in-place)", entry);
-    if (c.wide) {                                // CV_64F destinations: the generic double kernel, frame by frame
-        for (int f = 0; f < nframes; f++)
-            hipLaunchKernelGGL(k_sepfilter_generic64, dim3(divUp(W * c.cn, 64), divUp(H, 4)), dim3(256), 0, stream(), src + (size_t)f * sframe, sstep, dst + (size_t)f * dframe, dstep,
-                               W, H, c.cn, c.sdepth, W, H, 0, 0, c.border, c.sp64);
-        return stg.finish(entry);
-    }
-    if (c.big) {                                 // 34 .. lim::SEP_MAX_TAPS taps: the LDS-ring kernel, frames along grid z
-        if (!sepLong(stg, c, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, W, H, 0, 0)) return MI355_DECLINED("seplongRun refused a kernel beyond 33 taps");
-        return stg.finish(entry);
-    }
     if (nframes == 1) { sframe = 0; dframe = 0; }
-    const SepParams& p = c.sp;
-    const bool centred = p.nx == p.ny && p.ax == p.nx / 2 && p.ay == p.ny / 2;
-    if (p.mode == 2 && c.ddepth == D16S && centred && p.deltaI == 0 &&
-        seprollDeriv16(src, sstep, sframe, dst, dstep, dframe, nframes, W, H, c.cn, p.kxi, p.kyi, p.nx, c.border, stream()))
-        return stg.finish(entry);
-    if (p.mode == 1 && c.sdepth == D8U && c.ddepth == D8U && centred && p.ny > 1 &&
-        seprollFix8U(src, sstep, sframe, dst, dstep, dframe, nframes, W, H, c.cn, p.kxi, p.kyi, p.nx, p.deltaF, c.border, stream()))
-        return stg.finish(entry);
-    if (p.mode == 0 && c.sdepth == D8U && (c.ddepth == D32F || c.ddepth == D8U) && centred &&
-        seprollFloat(src, sstep, sframe, dst, dstep, dframe, nframes, W, H, c.cn, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.ddepth == D32F ? 4 : 1, c.border, stream()))
-        return stg.finish(entry);
-    if (p.mode == 0 && c.sdepth == D32F && c.ddepth == D32F && c.cn == 1 && centred &&
-        seprollF32(src, sstep, sframe, dst, dstep, dframe, nframes, W, H, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream()))
-        return stg.finish(entry);
-    if (p.mode == 0 && (c.sdepth == D16U || c.sdepth == D16S) && (c.ddepth == c.sdepth || c.ddepth == D32F) && c.cn == 1 && centred &&
-        seprollF16(src, sstep, sframe, dst, dstep, dframe, nframes, W, H, c.sdepth == D16S, c.ddepth == D32F, p.kxf, p.kyf, p.nx, p.symY, p.deltaF, c.border, stream()))
-        return stg.finish(entry);
-    if (std::getenv("MI355CV_SEP_GENERIC") == nullptr && sepLong(stg, c, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, W, H, 0, 0)) return stg.finish(entry);
-    dim3 grid(divUp(W * c.cn, 64), divUp(H, 4));            // more than 4 channels
-    for (int f = 0; f < nframes; f++)
-        hipLaunchKernelGGL((k_sepfilter_generic<33>), grid, dim3(256), 0, stream(), src + (size_t)f * sframe, sstep, dst + (size_t)f * dframe, dstep, W, H, c.cn, c.sdepth, c.ddepth,
-                           W, H, 0, 0, c.border, c.sp);
-    return stg.finish(entry);
-}
-
-// getSobelKernels / getScharrKernels (deriv.cpp:55-162) as integer taps
-bool derivKernel(int order, int ksize, bool scharr, std::vector<int>& k)
-{
-    if (scharr) {
-        if (order == 0) k = {3, 10, 3}; else if (order == 1) k = {-1, 0, 1}; else return false;
-        return true;
-    }
-    if (ksize == 1 && order > 0) ksize = 3;
-    if (ksize % 2 == 0 || ksize > 31 || ksize <= order) return false;
-    if (ksize == 1) { k = {1}; return true; }
-    if (ksize == 3) {
-        if (order == 0) k = {1, 2, 1}; else if (order == 1) k = {-1, 0, 1}; else k = {1, -2, 1};
-        return true;
-    }
-    std::vector<int> kerI(ksize + 1, 0);
-    kerI[0] = 1;
-    for (int i = 0; i < ksize - order - 1; i++) {
-        int oldval = kerI[0];
-        for (int j = 1; j <= ksize; j++) { int nv = kerI[j] + kerI[j - 1]; kerI[j - 1] = oldval; oldval = nv; }
-    }
-    for (int i = 0; i < order; i++) {
-        int oldval = -kerI[0];
-        for (int j = 1; j <= ksize; j++) { int nv = kerI[j - 1] - kerI[j]; kerI[j - 1] = oldval; oldval = nv; }
-    }
-    k.assign(kerI.begin(), kerI.begin() + ksize);
-    return true;
+    const CallImages im = {src, sstep, sframe, dst, dstep, dframe, nframes, W, H, W, H, 0, 0};
+    return sepServe(stg, entry, c, im);
 }
 
 int derivRun(const char* entry, const uchar* src, size_t sstep, uchar* dst, size_t dstep, int W, int H, int sdepth, int ddepth,
@@ -1129,7 +876,7 @@ int derivRun(const char* entry, const uchar* src, size_t sstep, uchar* dst, size
 {
     MI355_DECLINE_IF(dx < 0 || dy < 0 || (scharr ? dx + dy != 1 : dx + dy <= 0) || inPlaceOnDevice(src, dst));
     std::vector<int> ix, iy;
-    MI355_DECLINE_IF(!derivKernel(dx, ksize, scharr, ix) || !derivKernel(dy, ksize, scharr, iy));
+    MI355_DECLINE_IF(!derivKernel(dx, ksize, scharr, 31, ix) || !derivKernel(dy, ksize, scharr, 31, iy));
     // ktype = max(CV_32F, ddepth, sdepth): `kx *= scale` is evaluated in double and stored back in the kernel's type (deriv.cpp:421, :432-439) -- float unless
     // the source or the destination is CV_64F
     const bool wideK = MI355CV_MAT_DEPTH(sdepth) == D64F || MI355CV_MAT_DEPTH(ddepth) == D64F;
@@ -1194,67 +941,88 @@ MI355CV_API int mi355cv_filterInit(cvhalFilter2D** context, uchar* kernel_data, 
     return MI355CV_OK;
 }
 
-// launches the rolling kernel when the geometry allows it; returns false otherwise
-static bool tryFilterRoll(const FilterCtx* c, const uchar* ds, size_t dss, size_t sframe, uchar* dd, size_t dds, size_t dframe, int nframes, int W, int H, hipStream_t st)
+// the K x K taps of a context as the rolling kernels take them: dense in raster order, zeros where the kernel has none
+static DenseTaps denseTaps(const FilterCtx& c)
 {
-    const int K = c->kw;
-    if (c->sdepth == D32F && c->ddepth == D32F && c->cn == 1 && c->kw == c->kh && (K == 3 || K == 5) && c->ax == K / 2 && c->ay == K / 2 &&
-        (((uintptr_t)ds | dss | sframe | (uintptr_t)dd | dds | dframe) & 3) == 0 && roll::eligible(ds, dss, sframe, dd, dds, dframe, W, 4, K / 2, c->border)) {
-        DenseTaps t; memset(&t, 0, sizeof t);
-        for (const Tap2D& tp : c->taps) t.k[tp.dy * K + tp.dx] = tp.k;
-        t.delta = c->delta;
-        const roll::Geom g = roll::geometry(W, H, 4, nframes, K == 3 ? 16 : 12, K);
-        if (K == 3) hipLaunchKernelGGL((k_filter2d_roll_f32<3>), dim3(g.blocks), dim3(256), 0, st, ds, dss, sframe, dd, dds, dframe, W, H, g.nchunks, g.nstrips, g.seg, g.nseg, nframes, c->border, roll::wholeImage(), t);
-        else        hipLaunchKernelGGL((k_filter2d_roll_f32<5>), dim3(g.blocks), dim3(256), 0, st, ds, dss, sframe, dd, dds, dframe, W, H, g.nchunks, g.nstrips, g.seg, g.nseg, nframes, c->border, roll::wholeImage(), t);
+    DenseTaps t; memset(&t, 0, sizeof t);
+    for (const Tap2D& tp : c.taps) t.k[tp.dy * c.kw + tp.dx] = tp.k;
+    t.delta = c.delta;
+    return t;
+}
+
+// launches the rolling kernel when the geometry allows it; returns false otherwise
+static bool tryFilterRoll(const FilterCtx& c, const CallImages& im, hipStream_t st)
+{
+    const int K = c.kw;
+    if (c.sdepth == D32F && c.ddepth == D32F && c.cn == 1 && c.kw == c.kh && (K == 3 || K == 5) && c.ax == K / 2 && c.ay == K / 2 &&
+        (((uintptr_t)im.src | im.sstep | im.sframe | (uintptr_t)im.dst | im.dstep | im.dframe) & 3) == 0 &&
+        roll::eligible(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.W, 4, K / 2, c.border)) {
+        const DenseTaps t = denseTaps(c);
+        const roll::Geom g = roll::geometry(im.W, im.H, 4, im.nframes, K == 3 ? 16 : 12, K);
+        if (K == 3) hipLaunchKernelGGL((k_filter2d_roll_f32<3>), dim3(g.blocks), dim3(256), 0, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.W, im.H, g.nchunks, g.nstrips, g.seg, g.nseg, im.nframes, c.border, roll::wholeImage(), t);
+        else        hipLaunchKernelGGL((k_filter2d_roll_f32<5>), dim3(g.blocks), dim3(256), 0, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.W, im.H, g.nchunks, g.nstrips, g.seg, g.nseg, im.nframes, c.border, roll::wholeImage(), t);
         noteKernel("k_filter2d_roll_f32<%d> blocks=%u seg=%d rows", K, g.blocks, g.seg);
         return true;
     }
-    if (c->sdepth != D8U || c->ddepth != D8U || c->kw != c->kh || (K != 3 && K != 5) || c->ax != K / 2 || c->ay != K / 2) return false;
-    if (!((K == 3 && (c->cn == 1 || c->cn == 3 || c->cn == 4)) || (K == 5 && c->cn == 1))) return false;
-    if (!roll::eligible(ds, dss, sframe, dd, dds, dframe, W, c->cn, K / 2, c->border)) return false;
-    DenseTaps t; memset(&t, 0, sizeof t);
-    for (const Tap2D& tp : c->taps) t.k[tp.dy * K + tp.dx] = tp.k;
-    t.delta = c->delta;
+    if (c.sdepth != D8U || c.ddepth != D8U || c.kw != c.kh || (K != 3 && K != 5) || c.ax != K / 2 || c.ay != K / 2) return false;
+    if (!((K == 3 && (c.cn == 1 || c.cn == 3 || c.cn == 4)) || (K == 5 && c.cn == 1))) return false;
+    if (!roll::eligible(im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.W, c.cn, K / 2, c.border)) return false;
+    const DenseTaps t = denseTaps(c);
     // 5x5: 32-row segments (a 4-row halo re-read per 32 rows instead of per 12; 64 x 4K sweep, profiles/r03_roll_seg_sweep.txt: 0.356 -> 0.408 of HBM)
-    const roll::Geom g = roll::geometry(W, H, c->cn, nframes, K == 3 ? 16 : 32, K);
-#define FROLL(K_, CN_) hipLaunchKernelGGL((k_filter2d_roll<K_, CN_>), dim3(g.blocks), dim3(256), 0, st, ds, dss, sframe, dd, dds, dframe, W, H, g.nchunks, g.nstrips, g.seg, g.nseg, nframes, c->border, 1, t)
-    if (K == 3) { if (c->cn == 1) FROLL(3, 1); else if (c->cn == 3) FROLL(3, 3); else FROLL(3, 4); }
+    const roll::Geom g = roll::geometry(im.W, im.H, c.cn, im.nframes, K == 3 ? 16 : 32, K);
+#define FROLL(K_, CN_) hipLaunchKernelGGL((k_filter2d_roll<K_, CN_>), dim3(g.blocks), dim3(256), 0, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, im.W, im.H, g.nchunks, g.nstrips, g.seg, g.nseg, im.nframes, c.border, 1, t)
+    if (K == 3) { if (c.cn == 1) FROLL(3, 1); else if (c.cn == 3) FROLL(3, 3); else FROLL(3, 4); }
     else FROLL(5, 1);
 #undef FROLL
     return true;
 }
 
 // the LDS-tile kernel for what the rolling kernels do not take: any anchor / depth pair / channel count / ROI window, kernels of 9 .. 1024 taps up to 32 wide
-static bool tryFilterTile(Stager& stg, const FilterCtx* c, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes,
-                          int W, int H, int fullW, int fullH, int offX, int offY, hipStream_t st)
+static bool tryFilterTile(Stager& stg, const FilterCtx& c, const CallImages& im, hipStream_t st)
 {
     static const bool off = [] { const char* v = getenv("MI355CV_FILTER_TILE"); return v && atoi(v) == 0; }();
-    const int nc = (c->kw + 3) / 4;
-    if (off || c->wide || c->kw * c->kh < 9 || nc > 8 || (long long)nframes * c->cn > 65535 || divUp(H, FT_H) > 65535) return false;
+    const int nc = (c.kw + 3) / 4;
+    if (off || c.wide || c.kw * c.kh < 9 || nc > 8 || (long long)im.nframes * c.cn > 65535 || divUp(im.H, FT_H) > 65535) return false;
     bool any = false;
-    for (const Tap2D& tp : c->taps) any = any || tp.k != 0.f;
+    for (const Tap2D& tp : c.taps) any = any || tp.k != 0.f;
     if (!any) return false;                                          // an all-zero kernel is the generic kernel's single zero tap (filter.simd.hpp:393-395)
-    std::vector<float> kd((size_t)c->kh * 4 * nc, 0.f);
-    std::vector<unsigned> km((size_t)c->kh, 0u);
-    for (const Tap2D& tp : c->taps) { kd[(size_t)tp.dy * 4 * nc + tp.dx] = tp.k; km[tp.dy] |= 1u << tp.dx; }
+    std::vector<float> kd((size_t)c.kh * 4 * nc, 0.f);
+    std::vector<unsigned> km((size_t)c.kh, 0u);
+    for (const Tap2D& tp : c.taps) { kd[(size_t)tp.dy * 4 * nc + tp.dx] = tp.k; km[tp.dy] |= 1u << tp.dx; }
     const float* dk = (const float*)stg.param(kd.data(), kd.size() * sizeof(float));
     const unsigned* dm = (const unsigned*)stg.param(km.data(), km.size() * sizeof(unsigned));
     if (!dk || !dm) return false;
     TileArgs a;
-    a.W = W; a.H = H; a.cn = c->cn; a.ddepth = c->ddepth; a.fullW = fullW; a.fullH = fullH; a.offX = offX; a.offY = offY;
-    a.kw = c->kw; a.kh = c->kh; a.ax = c->ax; a.ay = c->ay; a.border = c->border; a.ncols = FT_W + 4 * nc; a.pitch = a.ncols; a.delta = c->delta;
-    const size_t lds = ((size_t)(FT_HH + c->kh - 1) * a.pitch * 2 + (size_t)c->kh * 4 * nc) * sizeof(float);
+    a.W = im.W; a.H = im.H; a.cn = c.cn; a.ddepth = c.ddepth; a.fullW = im.fullW; a.fullH = im.fullH; a.offX = im.offX; a.offY = im.offY;
+    a.kw = c.kw; a.kh = c.kh; a.ax = c.ax; a.ay = c.ay; a.border = c.border; a.ncols = FT_W + 4 * nc; a.pitch = a.ncols; a.delta = c.delta;
+    const size_t lds = ((size_t)(FT_HH + c.kh - 1) * a.pitch * 2 + (size_t)c.kh * 4 * nc) * sizeof(float);
     if (lds > 64 * 1024) return false;
-    const dim3 grid(divUp(W, FT_W), divUp(H, FT_H), nframes * c->cn);
-    switch (c->sdepth) {
-    case D8U:  launchFilterTile<uchar>(nc, grid, lds, st, src, sstep, sframe, dst, dstep, dframe, a, dk, dm); break;
-    case D16U: launchFilterTile<unsigned short>(nc, grid, lds, st, src, sstep, sframe, dst, dstep, dframe, a, dk, dm); break;
-    case D16S: launchFilterTile<short>(nc, grid, lds, st, src, sstep, sframe, dst, dstep, dframe, a, dk, dm); break;
-    case D32F: launchFilterTile<float>(nc, grid, lds, st, src, sstep, sframe, dst, dstep, dframe, a, dk, dm); break;
+    const dim3 grid(divUp(im.W, FT_W), divUp(im.H, FT_H), im.nframes * c.cn);
+    switch (c.sdepth) {
+    case D8U:  launchFilterTile<uchar>(nc, grid, lds, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, a, dk, dm); break;
+    case D16U: launchFilterTile<unsigned short>(nc, grid, lds, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, a, dk, dm); break;
+    case D16S: launchFilterTile<short>(nc, grid, lds, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, a, dk, dm); break;
+    case D32F: launchFilterTile<float>(nc, grid, lds, st, im.src, im.sstep, im.sframe, im.dst, im.dstep, im.dframe, a, dk, dm); break;
     default: return false;
     }
-    noteKernel("k_filter2d_tile<%d> %dx%d taps (%zu non-zero), depth %d -> %d, %d channel(s), lds %zu", nc, c->kw, c->kh, c->taps.size(), c->sdepth, c->ddepth, c->cn, lds);
+    noteKernel("k_filter2d_tile<%d> %dx%d taps (%zu non-zero), depth %d -> %d, %d channel(s), lds %zu", nc, c.kw, c.kh, c.taps.size(), c.sdepth, c.ddepth, c.cn, lds);
     return true;
+}
+
+// the served paths of filter2D in order, for the hook's image and for a batch alike (CV_64F destinations are the hook's own branch): the rolling kernels for a whole
+// image, the LDS tile, then the generic kernel frame by frame
+static int filterServe(Stager& stg, const char* entry, const FilterCtx& c, const CallImages& im)
+{
+    if (im.whole() && tryFilterRoll(c, im, stream())) return stg.finish(entry);
+    if (tryFilterTile(stg, c, im, stream())) return stg.finish(entry);
+    Tap2D* dt = (Tap2D*)stg.param(c.taps.data(), c.taps.size() * sizeof(Tap2D));
+    MI355_DECLINE_IF(!dt);
+    const dim3 grid(divUp(im.W * c.cn, 64), divUp(im.H, 4));
+    for (int f = 0; f < im.nframes; f++)
+        hipLaunchKernelGGL(k_filter2d_generic, grid, dim3(256), 0, stream(), im.src + (size_t)f * im.sframe, im.sstep, im.dst + (size_t)f * im.dframe, im.dstep,
+                           im.W, im.H, c.cn, c.sdepth, c.ddepth, im.fullW, im.fullH, im.offX, im.offY, dt, (int)c.taps.size(), c.ax, c.ay, c.kw, c.kh, c.delta, c.border);
+    noteKernel("k_filter2d_generic %dx%d taps, depth %d -> %d, %d channel(s)", c.kw, c.kh, c.sdepth, c.ddepth, c.cn);
+    return stg.finish(entry);
 }
 
 // batched filter2D over device-resident frames with a context from mi355cv_filterInit (frames are whole images:
@@ -1274,19 +1042,8 @@ MI355CV_API int mi355cv_filterBatch(cvhalFilter2D* context, const uchar* src_dat
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(dst_data));
     if (nframes == 1) { src_frame_stride = 0; dst_frame_stride = 0; }
-    if (!tryFilterRoll(c, src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, stream()) &&
-        !tryFilterTile(stg, c, src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, width, height, 0, 0, stream())) {
-        Tap2D* dt = (Tap2D*)stg.param(c->taps.data(), c->taps.size() * sizeof(Tap2D));
-        MI355_DECLINE_IF(!dt);
-        const int se = depthSize(c->sdepth), de = depthSize(c->ddepth); (void)se; (void)de;
-        for (int f = 0; f < nframes; f++) {
-            dim3 grid(divUp(width * c->cn, 64), divUp(height, 4));
-            hipLaunchKernelGGL(k_filter2d_generic, grid, dim3(256), 0, stream(), src_data + (size_t)f * src_frame_stride, src_step,
-                               dst_data + (size_t)f * dst_frame_stride, dst_step, width, height, c->cn, c->sdepth, c->ddepth,
-                               width, height, 0, 0, dt, (int)c->taps.size(), c->ax, c->ay, c->kw, c->kh, c->delta, c->border);
-        }
-    }
-    return stg.finish("filterBatch");
+    const CallImages im = {src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, width, height, 0, 0};
+    return filterServe(stg, "filterBatch", *c, im);
 }
 
 // cv::cvtColor(src, gray, COLOR_BGR2GRAY / RGB2GRAY / BGRA2GRAY / RGBA2GRAY) + cv::filter2D(gray, dst, ...) on device-resident CV_8UC3 / CV_8UC4
@@ -1312,9 +1069,7 @@ MI355CV_API int mi355cv_cvtBGRtoGrayFilterBatch(cvhalFilter2D* context, const uc
     if (nframes == 1) { src_frame_stride = 0; dst_frame_stride = 0; }
     if (!roll::eligible(dst_data, dst_step, dst_frame_stride, dst_data, dst_step, dst_frame_stride, width, 1, K / 2, c->border) || (width & 15))
         return setError(MI355CV_NOT_IMPLEMENTED, "cvtBGRtoGrayFilterBatch: width must be a multiple of 16 pixels");
-    DenseTaps t; memset(&t, 0, sizeof t);
-    for (const Tap2D& tp : c->taps) t.k[tp.dy * K + tp.dx] = tp.k;
-    t.delta = c->delta;
+    const DenseTaps t = denseTaps(*c);
     const roll::Geom g = roll::geometry(width, height, 1, nframes, K == 3 ? 16 : 12, K);
     const int k0 = swapBlue ? 9798 : 3735, k1 = 19235, k2 = swapBlue ? 3735 : 9798;      // color.simd_helpers.hpp:16-24 ({B2Y, G2Y, R2Y} in channel order)
 #define GROLL(K_, S_) hipLaunchKernelGGL((k_gray_filter2d_roll<K_, S_>), dim3(g.blocks), dim3(256), 0, stream(), src_data, src_step, src_frame_stride, dst_data, dst_step, \
@@ -1334,7 +1089,7 @@ MI355CV_API int mi355cv_filter(cvhalFilter2D* context, uchar* src_data, size_t s
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice());
     MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
-    const int se = depthSize(c->sdepth), de = depthSize(c->ddepth);
+    const int se = depthBytes(c->sdepth), de = depthBytes(c->ddepth);
     // hal::filter2D tries the hook before its own DFT path (filter.dispatch.cpp:1436-1470): for a whole image and a kernel of >= 130 taps
     // (8U -> 8U / 16S, 32F -> 32F; >= 50 otherwise) the CPU result comes from float FFTs (dftFilter2D :1274-1340), which a direct sum does
     // not reproduce bit for bit -- leave those to the CPU
@@ -1353,13 +1108,12 @@ MI355CV_API int mi355cv_filter(cvhalFilter2D* context, uchar* src_data, size_t s
             return setError(MI355CV_NOT_IMPLEMENTED, "filter: %dx%d kernel on a whole image is the reference's DFT case", c->kw, c->kh);
     }
     const uchar* top = src_data - (ptrdiff_t)offset_y * (ptrdiff_t)src_step - (ptrdiff_t)offset_x * c->cn * se;
-    if (overlapOnDevice(top, (size_t)(full_height - 1) * src_step + (size_t)full_width * c->cn * se, dst_data, (size_t)(height - 1) * dst_step + (size_t)width * c->cn * de))
+    if (overlapOnDevice(top, span(src_step, full_height, (size_t)full_width * c->cn * se), dst_data, span(dst_step, height, (size_t)width * c->cn * de)))
         return setError(MI355CV_NOT_IMPLEMENTED, "filter: dst overlaps the device-resident source rows (in-place)");
     size_t dss, dds;
     const uchar* dtop = stg.in(top, src_step, (size_t)full_width * c->cn * se, full_height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width * c->cn * de, height, &dds);
-    Tap2D* dt = (Tap2D*)stg.param(c->taps.data(), c->taps.size() * sizeof(Tap2D));
-    MI355_DECLINE_IF(!dtop || !dd || !dt);
+    MI355_DECLINE_IF(!dtop || !dd);
     const uchar* ds = dtop + (size_t)offset_y * dss + (size_t)offset_x * c->cn * se;
     if (c->wide) {
         Tap2D64* dt64 = (Tap2D64*)stg.param(c->taps64.data(), c->taps64.size() * sizeof(Tap2D64));
@@ -1369,15 +1123,8 @@ MI355CV_API int mi355cv_filter(cvhalFilter2D* context, uchar* src_data, size_t s
         noteKernel("k_filter2d_generic64 (depth %d -> CV_64F, %zu taps)", c->sdepth, c->taps64.size());
         return stg.finish("filter");
     }
-    if (full_width == width && full_height == height && tryFilterRoll(c, ds, dss, 0, dd, dds, 0, 1, width, height, stream()))
-        return stg.finish("filter");
-    if (tryFilterTile(stg, c, ds, dss, 0, dd, dds, 0, 1, width, height, full_width, full_height, offset_x, offset_y, stream()))
-        return stg.finish("filter");
-    dim3 grid(divUp(width * c->cn, 64), divUp(height, 4));
-    hipLaunchKernelGGL(k_filter2d_generic, grid, dim3(256), 0, stream(), ds, dss, dd, dds, width, height, c->cn, c->sdepth, c->ddepth,
-                       full_width, full_height, offset_x, offset_y, dt, (int)c->taps.size(), c->ax, c->ay, c->kw, c->kh, c->delta, c->border);
-    noteKernel("k_filter2d_generic %dx%d taps, depth %d -> %d, %d channel(s)", c->kw, c->kh, c->sdepth, c->ddepth, c->cn);
-    return stg.finish("filter");
+    const CallImages im = {ds, dss, 0, dd, dds, 0, 1, width, height, full_width, full_height, offset_x, offset_y};
+    return filterServe(stg, "filter", *c, im);
 }
 
 MI355CV_API int mi355cv_filterFree(cvhalFilter2D* context)
@@ -1482,164 +1229,6 @@ MI355CV_API int mi355cv_sepFilterBatch(cvhalFilter2D* context, const uchar* src_
             return mi355cv_sepFilterBatch(context, s, ss, sf, d, ds, df, nf, width, height); });
     }
     return sepRunBatch("sepFilterBatch", *c, src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height);
-}
-
-static int boxRun(const char* entry, const uchar* src_data, size_t src_step, size_t sframe, uchar* dst_data, size_t dst_step, size_t dframe, int nframes, int width, int height,
-        int src_depth, int dst_depth, int cn, int margin_left, int margin_top, int margin_right, int margin_bottom,
-        size_t ksize_width, size_t ksize_height, int anchor_x, int anchor_y, bool normalize, int border_type);
-
-MI355CV_API int mi355cv_boxFilterBatch(const uchar* src_data, size_t src_step, size_t src_frame_stride, uchar* dst_data, size_t dst_step, size_t dst_frame_stride,
-        int nframes, int width, int height, int src_depth, int dst_depth, int cn, size_t ksize_width, size_t ksize_height, int anchor_x, int anchor_y, bool normalize,
-        int border_type)
-{
-    mi355::EntryGuard entry_(__func__);
-    MI355_DECLINE_IF(nframes < 1);
-    if (width > 0 && height > 0 && hostBatchEligible(src_data, dst_data, nframes)) {            // frames in host memory: chunks through two sets of device buffers
-        const HostBatch hb = {src_data, src_step, src_frame_stride, (size_t)width * cn * depthBytes(src_depth), height, dst_data, dst_step, dst_frame_stride, (size_t)width * cn * depthBytes(dst_depth), height, nframes};
-        return runHostBatch("boxFilterBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
-            return mi355cv_boxFilterBatch(s, ss, sf, d, ds, df, nf, width, height, src_depth, dst_depth, cn, ksize_width, ksize_height, anchor_x, anchor_y, normalize, border_type); });
-    }
-    return boxRun("boxFilterBatch", src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, src_depth, dst_depth, cn,
-                  0, 0, 0, 0, ksize_width, ksize_height, anchor_x, anchor_y, normalize, border_type);
-}
-
-MI355CV_API int mi355cv_boxFilter(const uchar* src_data, size_t src_step, uchar* dst_data, size_t dst_step, int width, int height,
-        int src_depth, int dst_depth, int cn, int margin_left, int margin_top, int margin_right, int margin_bottom,
-        size_t ksize_width, size_t ksize_height, int anchor_x, int anchor_y, bool normalize, int border_type)
-{
-    mi355::EntryGuard entry_(__func__);
-    return boxRun("boxFilter", src_data, src_step, 0, dst_data, dst_step, 0, 0, width, height, src_depth, dst_depth, cn, margin_left, margin_top, margin_right, margin_bottom,
-                  ksize_width, ksize_height, anchor_x, anchor_y, normalize, border_type);
-}
-
-static bool boxTwoPass(Stager& stg, const BoxParams& p, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes, int W, int H, int cn,
-                       int sdepth, int ddepth, int fullW, int fullH, int offX, int offY, int border)
-{
-    static const bool off = [] { const char* v = getenv("MI355CV_BOX_TWOPASS"); return v && atoi(v) == 0; }();
-    if (off || p.kw * p.kh < 16 || p.kw > 1024 || cn > 64 || sdepth == D64F || divUp(H, 32) > 65535) return false;
-    hipStream_t st = stream();
-    int r0, r1;
-    boxRowRange(H, p.kh, fullH, offY, border, &r0, &r1);
-    if (r1 - r0 < 1 || r1 - r0 > 65535 || (sdepth != D8U && sdepth != D16U && sdepth != D16S && sdepth != D32F)) return false;
-    // ONE scratch image of row sums (int or double) for the whole batch: the frames go through it one after the other, in stream order
-    void* R = stg.scratch((((size_t)W * cn + 3) & ~(size_t)3) * (size_t)(r1 - r0) * (sdepth == D32F ? sizeof(double) : sizeof(int)));
-    if (!R) return false;
-    for (int f = 0; f < nframes; f++) {
-        const uchar* s = src + (size_t)f * sframe; uchar* d = dst + (size_t)f * dframe;
-        switch (sdepth) {
-        case D8U:  boxTwoPassT<uchar, int>(R, p, s, sstep, d, dstep, W, H, cn, ddepth, fullW, fullH, offX, offY, border, st); break;
-        case D16U: boxTwoPassT<unsigned short, int>(R, p, s, sstep, d, dstep, W, H, cn, ddepth, fullW, fullH, offX, offY, border, st); break;
-        case D16S: boxTwoPassT<short, int>(R, p, s, sstep, d, dstep, W, H, cn, ddepth, fullW, fullH, offX, offY, border, st); break;
-        default:   boxTwoPassT<float, double>(R, p, s, sstep, d, dstep, W, H, cn, ddepth, fullW, fullH, offX, offY, border, st); break;
-        }
-    }
-    noteKernel("k_box_rows + k_box_cols %dx%d window, depth %d -> %d, %d channel(s), %d frame(s)", p.kw, p.kh, sdepth, ddepth, cn, nframes);
-    return true;
-}
-
-// nframes == 0: the hook (one image, margins, host or device); nframes >= 1: a batch of device-resident whole frames
-// CV_8U -> CV_8U windows the rolling kernels do not take (9 .. 129 per axis, any anchor, 2 channels, ROI windows): the window sum is two products with banded matrices of
-// ones -- k_sepmx (sepmx.hip) computes it exactly on the matrix cores, nx + ny "taps" per byte instead of the kw * kh loads of k_box_generic, and finishes with the
-// reference's own normalisation.
-static bool boxOnMatrixCores(Stager& stg, const BoxParams& p, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe, int nframes, int W, int H, int cn,
-                             int sdepth, int ddepth, int fullW, int fullH, int offX, int offY, int border)
-{
-    if (sdepth != D8U || ddepth != D8U || cn > 4 || p.mode == 2 || p.kw > lim::BOX_MAX_KSIZE || p.kh > lim::BOX_MAX_KSIZE) return false;      // (the kernel declines rows of taps beyond its K steps: 255 for one channel)
-    if (std::getenv("MI355CV_SEPMX") && std::getenv("MI355CV_SEPMX")[0] == '0') return false;
-    uint16_t ones[lim::BOX_MAX_KSIZE];
-    for (int i = 0; i < lim::BOX_MAX_KSIZE; i++) ones[i] = 1;
-    const SepmxBox b = {!p.normalize ? 3 : p.mode == 0 ? 1 : 2, p.divScale, p.divDelta, p.scaleF, p.scaleD};
-    return sepmxRun(stg, src, sstep, sframe, dst, dstep, dframe, nframes, W, H, cn, fullW, fullH, offX, offY, border, ones, p.kw, p.ax, ones, p.kh, p.ay, stream(), &b);
-}
-
-static int boxRun(const char* entry, const uchar* src_data, size_t src_step, size_t sframe, uchar* dst_data, size_t dst_step, size_t dframe, int nframes, int width, int height,
-        int src_depth, int dst_depth, int cn, int margin_left, int margin_top, int margin_right, int margin_bottom,
-        size_t ksize_width, size_t ksize_height, int anchor_x, int anchor_y, bool normalize, int border_type)
-{
-    MI355_DECLINE_IF(disabled() || width <= 0 || height <= 0 || cn < 1 || cn > 512 || inPlaceOnDevice(src_data, dst_data));
-    // cv::boxFilter hands its `ddepth` argument through as the caller gave it (box_filter.dispatch.cpp:451-474): a caller that passed a TYPE there (CV_8UC2 = 8 --
-    // the reference's own Imgproc_Blur test does) arrives with channel bits set; the destination Mat was created from CV_MAKETYPE(ddepth, cn), i.e. from the depth bits
-    src_depth = MI355CV_MAT_DEPTH(src_depth); dst_depth = MI355CV_MAT_DEPTH(dst_depth);
-    const int kw = (int)ksize_width, kh = (int)ksize_height;
-    MI355_DECLINE_IF(kw < 1 || kh < 1 || kw > lim::BOX_MAX_KSIZE || kh > lim::BOX_MAX_KSIZE);
-    const int border = border_type & ~MI355CV_BORDER_ISOLATED;
-    MI355_DECLINE_IF(border < 0 || border > B_REFLECT_101);
-    // integer sources: int sums into any of the destination depths the reference has a ColumnSum<int, T> for (8U -> 16S is what an un-normalised cv::boxFilter of
-    // bytes usually asks for); a signed source into an unsigned destination is left to the caller's path
-    const bool okDepth = (src_depth == D8U && (dst_depth == D8U || dst_depth == D16U || dst_depth == D16S || dst_depth == D32F)) ||
-                         (src_depth == D16U && (dst_depth == D8U || dst_depth == D16U || dst_depth == D16S || dst_depth == D32F)) ||
-                         (src_depth == D16S && (dst_depth == D16S || dst_depth == D32F)) ||
-                         (src_depth == D32F && (dst_depth == D32F || dst_depth == D64F)) || (src_depth == D64F && dst_depth == D64F) ||
-                         ((src_depth == D8U || src_depth == D16U || src_depth == D16S) && dst_depth == D64F);
-    if (!okDepth) return setError(MI355CV_NOT_IMPLEMENTED, "boxFilter: depth pair %d -> %d outside the GPU path", src_depth, dst_depth);
-    BoxParams p; memset(&p, 0, sizeof p);
-    p.kw = kw; p.kh = kh;
-    p.ax = anchor_x < 0 ? kw / 2 : anchor_x; p.ay = anchor_y < 0 ? kh / 2 : anchor_y;
-    MI355_DECLINE_IF(p.ax >= kw || p.ay >= kh);
-    p.normalize = normalize ? 1 : 0;
-    const int area = kw * kh;
-    const double scale = 1.0 / area;
-    p.scaleD = scale; p.scaleF = (float)scale;
-    if (normalize && area == 1) p.normalize = 0;                       // scale == 1: the reference skips the multiply
-    if (src_depth == D32F || src_depth == D64F) p.mode = 2;
-    else if (src_depth == D8U && dst_depth == D8U && area <= 256) {
-        p.mode = 0;
-        // ColumnSum<ushort,uchar> constructor (box_filter.simd.hpp:441-455)
-        const int d = (int)nearbyint(1.0 / scale);
-        double scalef = ((double)(1 << 23)) / d;
-        p.divScale = (int)std::floor(scalef);
-        scalef -= p.divScale;
-        p.divDelta = d / 2;
-        if (scalef < 0.5) p.divDelta++; else p.divScale++;
-    } else {
-        p.mode = 1;
-        const long long lim = src_depth == D8U ? (1LL << 23) : src_depth == D16U ? (1LL << 15) : (1LL << 16);
-        MI355_DECLINE_IF(normalize && area > lim);    // the reference switches to double sums there
-    }
-    Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    MI355_DECLINE_IF(!ensureDevice());
-    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
-    const int se = depthSize(src_depth), de = depthSize(dst_depth);
-    const int fullW = margin_left + width + margin_right, fullH = margin_top + height + margin_bottom;
-    if (nframes >= 1) {
-        if (!isDevicePtr(src_data) || !isDevicePtr(dst_data)) return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
-        if (nframes == 1) { sframe = 0; dframe = 0; }
-        if (p.mode == 0 && p.normalize && kw == kh && p.ax == kw / 2 && p.ay == kh / 2 &&
-            seprollBox(src_data, src_step, sframe, dst_data, dst_step, dframe, nframes, width, height, cn, kw, (unsigned)p.divScale, (unsigned)p.divDelta, border, stream()))
-            return stg.finish(entry);
-        if (p.mode == 2 && src_depth == D32F && dst_depth == D32F && cn == 1 && kw == kh && p.ax == kw / 2 && p.ay == kh / 2 &&
-            seprollBoxF32(src_data, src_step, sframe, dst_data, dst_step, dframe, nframes, width, height, kw, p.normalize != 0, border, stream()))
-            return stg.finish(entry);
-        if (boxOnMatrixCores(stg, p, src_data, src_step, sframe, dst_data, dst_step, dframe, nframes, width, height, cn, src_depth, dst_depth, width, height, 0, 0, border)) return stg.finish(entry);
-        if (boxTwoPass(stg, p, src_data, src_step, sframe, dst_data, dst_step, dframe, nframes, width, height, cn, src_depth, dst_depth, width, height, 0, 0, border)) return stg.finish(entry);
-        dim3 grid(divUp(width * cn, 64), divUp(height, 4));
-        for (int f = 0; f < nframes; f++)
-            hipLaunchKernelGGL(k_box_generic, grid, dim3(256), 0, stream(), src_data + (size_t)f * sframe, src_step, dst_data + (size_t)f * dframe, dst_step, width, height, cn,
-                               src_depth, dst_depth, width, height, 0, 0, border, p);
-        noteKernel("k_box_generic %dx%d window, depth %d -> %d, %d channel(s)", kw, kh, src_depth, dst_depth, cn);
-        return stg.finish(entry);
-    }
-    size_t dss, dds;
-    const uchar* top = src_data - (ptrdiff_t)margin_top * (ptrdiff_t)src_step - (ptrdiff_t)margin_left * cn * se;
-    const uchar* dtop = stg.in(top, src_step, (size_t)fullW * cn * se, fullH, &dss);
-    uchar* dd = stg.out(dst_data, dst_step, (size_t)width * cn * de, height, &dds);
-    MI355_DECLINE_IF(!dtop || !dd);
-    const uchar* ds = dtop + (size_t)margin_top * dss + (size_t)margin_left * cn * se;
-    const Roi roiv = {fullW, fullH, margin_left, margin_top};
-    const Roi* roi = (fullW != width || fullH != height) ? &roiv : nullptr;       // a submatrix with real pixels around it: the rolling kernels store the window
-    if (p.mode == 0 && p.normalize && kw == kh && p.ax == kw / 2 && p.ay == kh / 2 &&
-        seprollBox(ds, dss, 0, dd, dds, 0, 1, width, height, cn, kw, (unsigned)p.divScale, (unsigned)p.divDelta, border, stream(), roi))
-        return stg.finish(entry);
-    if (p.mode == 2 && src_depth == D32F && dst_depth == D32F && cn == 1 && kw == kh && p.ax == kw / 2 && p.ay == kh / 2 &&
-        seprollBoxF32(ds, dss, 0, dd, dds, 0, 1, width, height, kw, p.normalize != 0, border, stream(), roi))
-        return stg.finish(entry);
-    if (boxOnMatrixCores(stg, p, ds, dss, 0, dd, dds, 0, 1, width, height, cn, src_depth, dst_depth, fullW, fullH, margin_left, margin_top, border)) return stg.finish(entry);
-    if (boxTwoPass(stg, p, ds, dss, 0, dd, dds, 0, 1, width, height, cn, src_depth, dst_depth, fullW, fullH, margin_left, margin_top, border)) return stg.finish(entry);
-    dim3 grid(divUp(width * cn, 64), divUp(height, 4));
-    hipLaunchKernelGGL(k_box_generic, grid, dim3(256), 0, stream(), ds, dss, dd, dds, width, height, cn, src_depth, dst_depth,
-                       fullW, fullH, margin_left, margin_top, border, p);
-    noteKernel("k_box_generic %dx%d window, depth %d -> %d, %d channel(s)", kw, kh, src_depth, dst_depth, cn);
-    return stg.finish(entry);
 }
 
 } // extern "C"
