@@ -1,5 +1,5 @@
 // imgwarp_common.h -- what resize.hip (cv::resize) and warp.hip (warpAffine / warpPerspective / remap / convertMaps / warpPolar) both use: the depth codes, the
-// reference's rounding and saturation helpers, the per-depth element load / store of the generic kernels, and the two conventions of their dispatchers.
+// reference's rounding and saturation helpers, the per-depth element load / store of the generic kernels, and the frame rule of their dispatchers (NEXT_PATH, their other convention, is rt.h's).
 #pragma once
 #include "rt.h"
 
@@ -34,8 +34,5 @@ __device__ __forceinline__ void copyPix(uchar* d, const uchar* s, int bytes) { f
 inline bool depthOk(int d) { return d == D8U || d == D16U || d == D16S || d == D32F; }
 // the LDS kernels of warp8.h move whole dwords: every frame of a batch starts on a dword (their plans judge pointers and steps; the frames start at multiples of the strides)
 inline bool framesOnDwords(size_t sframe, size_t dframe) { return ((sframe | dframe) & 3) == 0; }
-// runResize / runWarp try their served paths in order; a path answers NEXT_PATH for "not mine, try the next", anything else is the call's return code
-constexpr int NEXT_PATH = -0x7fffffff;
-static_assert(NEXT_PATH != MI355CV_OK && NEXT_PATH != MI355CV_NOT_IMPLEMENTED && NEXT_PATH != MI355CV_ERROR_UNKNOWN, "NEXT_PATH is none of the codes a hook answers");
 
 } // namespace

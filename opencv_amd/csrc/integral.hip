@@ -15,6 +15,9 @@
 // cent of the compulsory 1 B read + 4 (8) B written per pixel, against ~4x that for the row pass + two column passes it replaces.
 // All sums are exact integers (u32 partials, int32 / u64 accumulators); CV_64F outputs are those integers converted once, so they equal the
 // reference's double sums bit for bit.
+//
+// Below the tiled kernels: the general scan (rows + column segments: any channel count, float sources; also the matcher's double sum and squared-sum
+// images, integralSumSq) and the two hooks, mi355cv_integral and mi355cv_integralBatch.  The order-dependent outputs are integral_seq.hip's.
 #include "rt.h"
 #include "integral.h"
 
@@ -373,7 +376,300 @@ bool integralTiledU8(const uchar* src, size_t sstep, size_t sframe, int W, int H
     if (sumIsDouble) { if (sq) ITILES(double, true); else ITILES(double, false); }
     else             { if (sq) ITILES(int, true); else ITILES(int, false); }
 #undef ITILES
+    noteKernel("k_integral_tiles<%s,%s> grid=%u x256, %d frame(s) (after k_integral_tilesums + k_integral_carries)", sumIsDouble ? "double" : "int", sq ? "true" : "false", grid.x, nframes);
     return true;
 }
 
+// ---------------------------------------------------------------------------------- the general scan: any channel count, 8-bit and float sources
+// cv::integral layout (sumpixels.simd.hpp): (H+1) x (W+1) x cn, first row / column zero.  sum in int32 (8-bit sources: exact, the
+// reference's default) or double, squared sum in double.  Three passes, each with enough independent work to fill the chip:
+//   rows    one workgroup per (row, channel): chunked scan of the row -> row-wise prefix sums
+//   colseg  one thread per (column, segment of IS_SEG rows): prefix down the segment in place, segment total to `aux`
+//   coladd  one thread per (column, segment >= 1): adds the totals of the segments above
+// (a single thread walking a whole column would leave all but ~16 CUs idle and serialise 2160 dependent adds).
+namespace {
+
+enum { D8U = MI355CV_8U, D32S = MI355CV_32S, D32F = MI355CV_32F, D64F = MI355CV_64F };
+
+constexpr int IS_SEG = 64;
+
+template <typename TS>
+__global__ __launch_bounds__(256) void k_integral_rows(const uchar* __restrict__ src, size_t sstep, size_t sframe, int W, int H, int cn, int depth,
+                                                       TS* __restrict__ sum, size_t sumStep /*elements*/, size_t sumFrame,
+                                                       double* __restrict__ sq, size_t sqStep, size_t sqFrame)
+{
+    const int y = blockIdx.x, c = blockIdx.y;
+    src += (size_t)blockIdx.z * sframe; sum += (size_t)blockIdx.z * sumFrame; if (sq) sq += (size_t)blockIdx.z * sqFrame;
+    const uchar* row = src + (size_t)y * sstep;
+    const int chunk = (W + 255) / 256;
+    const int x0 = threadIdx.x * chunk, x1 = min(W, x0 + chunk);
+    auto px = [&](int x) -> double { return depth == D8U ? (double)row[x * cn + c] : (double)reinterpret_cast<const float*>(row)[x * cn + c]; };
+    TS s = 0; double q = 0;
+    for (int x = x0; x < x1; x++) { const double v = px(x); s += (TS)v; q += v * v; }
+    __shared__ TS ss[256];
+    __shared__ double qq[256];
+    ss[threadIdx.x] = s; qq[threadIdx.x] = q;
+    __syncthreads();
+    for (int o = 1; o < 256; o <<= 1) {                      // Hillis-Steele inclusive scan over the 256 chunk totals
+        TS a = 0; double b = 0;
+        if ((int)threadIdx.x >= o) { a = ss[threadIdx.x - o]; b = qq[threadIdx.x - o]; }
+        __syncthreads();
+        ss[threadIdx.x] += a; qq[threadIdx.x] += b;
+        __syncthreads();
+    }
+    TS ps = threadIdx.x ? ss[threadIdx.x - 1] : (TS)0; double pq = threadIdx.x ? qq[threadIdx.x - 1] : 0.0;
+    TS* srow = sum + (size_t)(y + 1) * sumStep;
+    double* qrow = sq ? sq + (size_t)(y + 1) * sqStep : nullptr;
+    if (threadIdx.x == 0) { srow[c] = 0; if (qrow) qrow[c] = 0; }
+    for (int x = x0; x < x1; x++) {
+        const double v = px(x);
+        ps += (TS)v; pq += v * v;
+        srow[(x + 1) * cn + c] = ps;
+        if (qrow) qrow[(x + 1) * cn + c] = pq;
+    }
+}
+
+// single-channel 8-bit rows, the common case: a thread owns 16 consecutive pixels (one 16-byte load when the row allows), the
+// 256 thread totals are scanned with wave shuffles + one LDS exchange, and the finished row goes through LDS so that the
+// global stores are lane-consecutive (a thread writing its own 16 results would touch 16 different 64-byte segments).
+template <typename TS>
+__global__ __launch_bounds__(256) void k_integral_rows_u8c1(const uchar* __restrict__ src, size_t sstep, size_t sframe, int W,
+                                                            TS* __restrict__ sum, size_t sumStep, size_t sumFrame,
+                                                            double* __restrict__ sq, size_t sqStep, size_t sqFrame)
+{
+    extern __shared__ __attribute__((aligned(16))) uchar ldsraw[];
+    const int y = blockIdx.x;
+    src += (size_t)blockIdx.z * sframe; sum += (size_t)blockIdx.z * sumFrame; if (sq) sq += (size_t)blockIdx.z * sqFrame;
+    const uchar* row = src + (size_t)y * sstep;
+    const int per = 16 * ((((W + 255) / 256) + 15) / 16);          // pixels per thread, a multiple of 16
+    TS* LS = reinterpret_cast<TS*>(ldsraw);                          // W + 1 sums
+    double* LQ = reinterpret_cast<double*>(ldsraw + (((size_t)(W + 1) * sizeof(TS) + 15) & ~(size_t)15));   // W + 1 squared sums
+    const int x0 = threadIdx.x * per, x1 = min(W, x0 + per);
+    const bool vec = ((((uintptr_t)row) | sstep) & 15) == 0;
+    unsigned s = 0; unsigned long long q = 0;                      // exact: 255 * per and 255^2 * per are far below 2^32 / 2^64
+    for (int x = x0; x < x1; x += 16) {
+        unsigned w[4] = {0, 0, 0, 0};
+        if (vec && x + 16 <= W) { const uint4 v = *reinterpret_cast<const uint4*>(row + x); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
+        else for (int b = 0; b < 16 && x + b < W; b++) w[b >> 2] |= (unsigned)row[x + b] << (8 * (b & 3));
+#pragma unroll
+        for (int b = 0; b < 16; b++) { const unsigned p = (w[b >> 2] >> (8 * (b & 3))) & 255u; s += p; q += p * p; }
+    }
+    // block-wide exclusive scan of (s, q): wave shuffle scan, then the four wave totals through LDS
+    __shared__ unsigned long long ws[4], wq[4];
+    unsigned long long ps = s, pq = q;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    for (int o = 1; o < 64; o <<= 1) {
+        const unsigned long long a = __shfl_up(ps, o), b = __shfl_up(pq, o);
+        if (lane >= o) { ps += a; pq += b; }
+    }
+    if (lane == 63) { ws[wave] = ps; wq[wave] = pq; }
+    __syncthreads();
+    unsigned long long os = ps - s, oq = pq - q;                   // exclusive within the wave
+    for (int k = 0; k < wave; k++) { os += ws[k]; oq += wq[k]; }
+    if (threadIdx.x == 0) { LS[0] = 0; if (sq) LQ[0] = 0; }
+    TS rs = (TS)os; double rq = (double)oq;
+    for (int x = x0; x < x1; x++) {
+        const unsigned p = row[x];
+        rs += (TS)p; rq += (double)(p * p);
+        LS[x + 1] = rs; if (sq) LQ[x + 1] = rq;
+    }
+    __syncthreads();
+    TS* srow = sum + (size_t)(y + 1) * sumStep;
+    for (int x = threadIdx.x; x <= W; x += 256) srow[x] = LS[x];
+    if (sq) { double* qrow = sq + (size_t)(y + 1) * sqStep; for (int x = threadIdx.x; x <= W; x += 256) qrow[x] = LQ[x]; }
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_integral_colseg(T* __restrict__ a, size_t step, size_t frame, int Wc /* (W+1)*cn */, int H, T* __restrict__ aux, size_t auxFrame)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y;
+    if (x >= Wc) return;
+    a += (size_t)blockIdx.z * frame + x; aux += (size_t)blockIdx.z * auxFrame;
+    const int y0 = 1 + seg * IS_SEG, y1 = min(H + 1, y0 + IS_SEG);
+    if (seg == 0) a[0] = 0;
+    T s = 0;
+    int y = y0;
+    for (; y + 8 <= y1; y += 8) {
+        T v[8];
+#pragma unroll
+        for (int u = 0; u < 8; u++) v[u] = a[(size_t)(y + u) * step];
+#pragma unroll
+        for (int u = 0; u < 8; u++) { s += v[u]; a[(size_t)(y + u) * step] = s; }
+    }
+    for (; y < y1; y++) { s += a[(size_t)y * step]; a[(size_t)y * step] = s; }
+    aux[(size_t)seg * Wc + x] = s;
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_integral_coladd(T* __restrict__ a, size_t step, size_t frame, int Wc, int H, const T* __restrict__ aux, size_t auxFrame)
+{
+    const int x = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y + 1;
+    if (x >= Wc) return;
+    a += (size_t)blockIdx.z * frame + x; aux += (size_t)blockIdx.z * auxFrame;
+    T off = 0;
+    for (int s = 0; s < seg; s++) off += aux[(size_t)s * Wc + x];
+    const int y0 = 1 + seg * IS_SEG, y1 = min(H + 1, y0 + IS_SEG);
+#pragma unroll 8
+    for (int y = y0; y < y1; y++) a[(size_t)y * step] += off;
+}
+
+// column passes over one array; aux = nseg x Wc scratch elements per frame
+template <typename T>
+void integralColumns(T* a, size_t step, size_t frame, int Wc, int H, int nframes, T* aux, hipStream_t st)
+{
+    const int nseg = divUp(H, IS_SEG);
+    hipLaunchKernelGGL(k_integral_colseg<T>, dim3(divUp(Wc, 256), nseg, nframes), dim3(256), 0, st, a, step, frame, Wc, H, aux, (size_t)nseg * Wc);
+    if (nseg > 1)
+        hipLaunchKernelGGL(k_integral_coladd<T>, dim3(divUp(Wc, 256), nseg - 1, nframes), dim3(256), 0, st, a, step, frame, Wc, H, aux, (size_t)nseg * Wc);
+}
+
+} // namespace
+
+size_t integralSumSqAuxBytes(int W, int H, int cn, int nframes)
+{
+    return (size_t)divUp(H, IS_SEG) * (W + 1) * cn * nframes * sizeof(double);
+}
+
+void integralSumSq(const uchar* src, size_t sstep, size_t sframe, int W, int H, int cn, int depth, int nframes, double* dsum, double* dsq, double* aux, hipStream_t st)
+{
+    const size_t isteps = (size_t)(W + 1) * cn, iframeD = isteps * (H + 1);
+    hipLaunchKernelGGL(k_integral_rows<double>, dim3(H, cn, nframes), dim3(256), 0, st, src, sstep, sframe, W, H, cn, depth, dsum, isteps, iframeD, dsq, isteps, iframeD);
+    integralColumns<double>(dsum, isteps, iframeD, (int)isteps, H, nframes, aux, st);
+    integralColumns<double>(dsq, isteps, iframeD, (int)isteps, H, nframes, aux, st);
+}
+
+namespace {
+
+// One call of mi355cv_integral past the depth table, under the hook's own argument names (a decline's reason is its condition's text).  Three routes: the ordered
+// kernels of integral_seq.hip for everything whose bits depend on the order of the additions (ordered); for 8-bit sources with CV_32S / CV_64F sums -- exact integers
+// in any order -- exact() stages the call and hands it to the tiled kernels above (one channel), else to the general scan
+struct IntegralCall {
+    int depth, sdepth, sqdepth; const uchar* src_data; size_t src_step; uchar* sum_data; size_t sum_step; uchar* sqsum_data; size_t sqsum_step;
+    uchar* tilted_data; size_t tilted_step; int width, height, cn;
+    const uchar* ds; size_t dss, d1, d2, d3; uchar* s1; uchar* s2; uchar* s3;      // stage(): the source, the sum, the squared and the tilted sum where the kernels find them
+    size_t se() const { return sdepth == D32S ? 4 : 8; }
+
+    // es, e1, e2: bytes per element of the source, of the sum (and the tilted sum), of the squared sum; an output the caller did not give, or that could not be staged, is null
+    void stage(Stager& stg, size_t es, size_t e1, size_t e2)
+    {
+        d2 = d3 = 0;
+        ds = stg.in(src_data, src_step, (size_t)width * cn * es, height, &dss);
+        s1 = stg.out(sum_data, sum_step, (size_t)(width + 1) * cn * e1, height + 1, &d1);
+        s2 = sqsum_data ? stg.out(sqsum_data, sqsum_step, (size_t)(width + 1) * cn * e2, height + 1, &d2) : nullptr;
+        s3 = tilted_data ? stg.out(tilted_data, tilted_step, (size_t)(width + 1) * cn * e1, height + 1, &d3) : nullptr;
+    }
+
+    int ordered()                                                                  // k_iseq_*: float sources, CV_32F sums, CV_32F / CV_32S squared sums, tilted sums
+    {
+        if (depth == D8U && sdepth == D32F && !sqsum_data && !tilted_data && (double)width * height * 255.0 >= 16777216.0)
+            return setError(MI355CV_NOT_IMPLEMENTED, "integral: CV_8U -> CV_32F sums past 2^24 without a squared / tilted sum depend on the CPU's vector width");
+        const size_t e1 = sdepth == D64F ? 8 : 4, e2 = sqdepth == D64F ? 8 : 4, es = depth == D8U ? 1 : depth == D32F ? 4 : depth == D64F ? 8 : 2;
+        if (width <= 0 || height <= 0 || (sum_step % e1) || (sqsum_data && (sqsum_step % e2)) || (tilted_data && (tilted_step % e1)) || (src_step % es))
+            return MI355_DECLINED("width <= 0 || height <= 0 || a step that is not a multiple of its element size");
+        if ((double)(width + 1) * cn * (height + 1) >= 2147483647.0) return MI355_DECLINED("more than 2^31 elements");
+        Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
+        MI355_DECLINE_IF(!ensureDevice());
+        // (HOST_HEAVY: the reference's scalar loops take 10-60 ms per 4K image on one core -- worth two PCIe crossings, unlike the 8-bit vector paths of the tiled kind)
+        MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
+        stage(stg, es, e1, e2);
+        void* aux = tilted_data ? stg.scratch(integralOrderedAuxBytes(width, height, cn, sdepth, true)) : nullptr;
+        if (!ds || !s1 || (sqsum_data && !s2) || (tilted_data && (!s3 || !aux))) return MI355_DECLINED("staging / scratch for the ordered integral");
+        if (!integralOrdered(depth, sdepth, sqdepth, ds, dss, s1, d1, s2, d2, s3, d3, width, height, cn, aux, stream()))
+            return MI355_DECLINED("!integralOrdered(...)");
+        noteKernel("k_iseq_rows + k_iseq_cols%s (ordered sums, depths %d -> %d / %d)", tilted_data ? " + k_iseq_tbuf / tcol0 / tdiag" : "", depth, sdepth, sqdepth);
+        return stg.finish("integral");
+    }
+    int exact()                                                                    // the staging of the two exact routes, then the first of them that takes the call
+    {
+        MI355_DECLINE_IF(width <= 0 || height <= 0 || (sum_step % se()) || (sqsum_data && (sqsum_step % 8)));
+        Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
+        MI355_DECLINE_IF(!ensureDevice());
+        MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels()));
+        stage(stg, 1, se(), 8);
+        MI355_DECLINE_IF(!ds || !s1 || (sqsum_data && !s2));
+        const int rc = tiled(stg);
+        return rc != NEXT_PATH ? rc : scan(stg);
+    }
+    int tiled(Stager& stg)                                                         // k_integral_tiles: one channel, two passes over the pixels + carries instead of a row pass
+    {                                                                              // and two column passes over the sum image
+        static const bool tiledOff = envInt("MI355CV_INTEGRAL_TILED", 1) == 0;
+        if (!(depth == D8U && cn == 1 && !tiledOff)) return NEXT_PATH;
+        void* taux = stg.scratch(integralTiledAuxBytes(width, height, 1, s2 != nullptr));
+        if (taux && integralTiledU8(ds, dss, 0, width, height, 1, s1, d1 / se(), 0, sdepth == D64F, (double*)s2, d2 / 8, 0, taux, stream()))
+            return stg.finish("integral");
+        return NEXT_PATH;
+    }
+    template <typename TS> void scanRows(bool fastRows, size_t ldsFast, hipStream_t st)
+    {
+        if (fastRows) hipLaunchKernelGGL(k_integral_rows_u8c1<TS>, dim3(height, 1, 1), dim3(256), ldsFast, st, ds, dss, 0, width, (TS*)s1, d1 / sizeof(TS), 0, (double*)s2, d2 / 8, 0);
+        else hipLaunchKernelGGL(k_integral_rows<TS>, dim3(height, cn, 1), dim3(256), 0, st, ds, dss, 0, width, height, cn, depth, (TS*)s1, d1 / sizeof(TS), 0, (double*)s2, d2 / 8, 0);
+    }
+    int scan(Stager& stg)                                                          // k_integral_rows / k_integral_rows_u8c1, then the column segments of the sum and the squared sum
+    {
+        const int Wc = (width + 1) * cn, nseg = divUp(height, IS_SEG);
+        hipStream_t st = stream();
+        void* aux = stg.scratch((size_t)nseg * Wc * 8);
+        MI355_DECLINE_IF(!aux);
+        const size_t ldsFast = (((size_t)(width + 1) * se() + 15) & ~(size_t)15) + (s2 ? (size_t)(width + 1) * 8 : 0);
+        const bool fastRows = depth == D8U && cn == 1 && ldsFast <= 60 * 1024;
+        if (sdepth == D32S) { scanRows<int>(fastRows, ldsFast, st); integralColumns<int>((int*)s1, d1 / 4, 0, Wc, height, 1, (int*)aux, st); }
+        else { scanRows<double>(fastRows, ldsFast, st); integralColumns<double>((double*)s1, d1 / 8, 0, Wc, height, 1, (double*)aux, st); }
+        if (s2) integralColumns<double>((double*)s2, d2 / 8, 0, Wc, height, 1, (double*)aux, st);
+        noteKernel("%s<%s> grid=%dx%dx1 x256 + k_integral_colseg / coladd in %d segment(s)", fastRows ? "k_integral_rows_u8c1" : "k_integral_rows", sdepth == D32S ? "int" : "double",
+                   height, fastRows ? 1 : cn, nseg);
+        return stg.finish("integral");
+    }
+};
+
+} // namespace
 } // namespace mi355
+
+using namespace mi355;
+
+extern "C" {
+
+// replaces hal_ni_integral (hal_replacement.hpp:977; caller cv::integral sumpixels.dispatch.cpp:415): every depth triple of the reference's table (:383-406), with or
+// without the squared and the tilted sum.  CV_8U sources with CV_32S / CV_64F sums (squared sum in CV_64F, no tilted sum) take the tiled / scanned kernels above -- exact
+// integers in any order; everything whose value depends on the order of the additions -- float sources, CV_32F sums, CV_32F / CV_32S squared sums, tilted sums -- takes
+// integral_seq.hip, which adds in the reference's order (bit for bit).  One case is left to the CPU: CV_8U -> CV_32F sums without a squared or tilted sum beyond 2^24
+// (the reference's vector body recovers the row prefix in its scalar tail by a subtraction, sumpixels.simd.hpp:528-533, so the bits depend on the CPU's vector width).
+MI355CV_API int mi355cv_integral(int depth, int sdepth, int sqdepth, const uchar* src_data, size_t src_step, uchar* sum_data, size_t sum_step,
+                                 uchar* sqsum_data, size_t sqsum_step, uchar* tilted_data, size_t tilted_step, int width, int height, int cn)
+{
+    mi355::EntryGuard entry_(__func__);
+    MI355_DECLINE_IF(disabled() || !sum_data || !src_data);
+    if (!integralOrderedTriple(depth, sdepth, sqdepth) || cn < 1)
+        return setError(MI355CV_NOT_IMPLEMENTED, "integral: depths %d -> sum %d, sqsum %d%s, %d channels: not a row of the reference's table", depth, sdepth, sqdepth, sqsum_data ? "" : " (no sqsum)", cn);
+    const bool tiledKind = !tilted_data && cn <= 4 && depth == D8U && (sdepth == D32S || sdepth == D64F) && (!sqsum_data || sqdepth == D64F) &&
+                           !(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);          // (sums that wrap: the ordered kernels wrap like the reference)
+    IntegralCall c = {depth, sdepth, sqdepth, src_data, src_step, sum_data, sum_step, sqsum_data, sqsum_step, tilted_data, tilted_step, width, height, cn};
+    return tiledKind ? c.exact() : c.ordered();
+}
+
+// frame-batched form for device-resident CV_8UC1 frames: every frame's (H+1) x (W+1) CV_32S (or CV_64F) sum [+ CV_64F squared sum] from the
+// same three launches that serve one frame (the tile index carries the frame) -- the per-frame launches of a single 4K image are
+// latency-bound (2160 waves), a batch fills the machine.  Strides in bytes.
+MI355CV_API int mi355cv_integralBatch(const uchar* src_data, size_t src_step, size_t src_frame_stride, uchar* sum_data, size_t sum_step, size_t sum_frame_stride,
+                                      uchar* sqsum_data, size_t sqsum_step, size_t sqsum_frame_stride, int nframes, int width, int height, int sdepth)
+{
+    mi355::EntryGuard entry_(__func__);
+    MI355_DECLINE_IF(disabled() || !src_data || !sum_data || nframes < 1 || width <= 0 || height <= 0 || (sdepth != D32S && sdepth != D64F));
+    const size_t se = sdepth == D32S ? 4 : 8;
+    MI355_DECLINE_IF((sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8))));
+    MI355_DECLINE_IF(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);
+    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z; the carries are scratch per call
+        return sliceFrames(nframes, [&](size_t f0, int nf) {
+            return mi355cv_integralBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, sum_data + f0 * sum_frame_stride, sum_step, sum_frame_stride,
+                                         sqsum_data ? sqsum_data + f0 * sqsum_frame_stride : nullptr, sqsum_step, sqsum_frame_stride, nf, width, height, sdepth); });
+    Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
+    if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(sum_data) || (sqsum_data && !isDevicePtr(sqsum_data)))
+        return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: device-resident frames only");
+    if (nframes == 1) { src_frame_stride = 0; sum_frame_stride = 0; sqsum_frame_stride = 0; }
+    void* taux = stg.scratch(integralTiledAuxBytes(width, height, nframes, sqsum_data != nullptr));
+    if (!taux || !integralTiledU8(src_data, src_step, src_frame_stride, width, height, nframes, sum_data, sum_step / se, sum_frame_stride / se, sdepth == D64F,
+                                  (double*)sqsum_data, sqsum_step / 8, sqsum_frame_stride / 8, taux, stream()))
+        return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: frame geometry outside the tiled path");
+    return stg.finish("integralBatch");
+}
+
+} // extern "C"

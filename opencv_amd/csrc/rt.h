@@ -224,6 +224,10 @@ __device__ __forceinline__ unsigned xcdContiguous(unsigned id, unsigned n)
 #define MI355_DECLINED(why)   mi355::declined(__func__, __LINE__, why)
 #define MI355_DECLINE_IF(...) do { if (__VA_ARGS__) return MI355_DECLINED(#__VA_ARGS__); } while (0)
 
+// runResize / runWarp / runMatch try their served paths in order; a path answers NEXT_PATH for "not mine, try the next", anything else is the call's return code
+constexpr int NEXT_PATH = -0x7fffffff;
+static_assert(NEXT_PATH != MI355CV_OK && NEXT_PATH != MI355CV_NOT_IMPLEMENTED && NEXT_PATH != MI355CV_ERROR_UNKNOWN, "NEXT_PATH is none of the codes a hook answers");
+
 #ifdef __HIPCC__
 // (a << n) + b as ONE v_lshl_add_u32, and a + 4 b + 6 c on packed u16 pairs in four of them: written as plain C the optimiser folds the
 // 4 c + 2 c into a 32-bit multiply by 6 (v_mul_lo_u32), which is not a full-rate instruction

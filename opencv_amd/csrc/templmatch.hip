@@ -1,171 +1,42 @@
-// templmatch.hip -- row a13 of SURVEY.md §8: cv::matchTemplate (+ cv::integral).
+// templmatch.hip -- row a13 of SURVEY.md §8: cv::matchTemplate, with and without a mask.
 //
 // Reference: cv::matchTemplate templmatch.cpp:1158-1194 = crossCorr (:566-760, block-wise float FFT correlation)
 // followed by common_matchTemplate (:906-1029, double integral images + per-method normalisation and clamping).
-// Here the correlation is evaluated EXACTLY instead of through FFTs:
-//   * CV_8UC1, template up to 128x128 (BASELINE config 5): a Toeplitz-expanded-template GEMM on the matrix cores,
+// Here the correlation is evaluated directly instead of through FFTs, by the first of five paths that takes the call
+// (struct MatchCall; the matrix-core paths want >= 4096 results):
+//   1. matchRingI8    CV_8UC1, template up to 128x128 (BASELINE config 5): a Toeplitz-expanded-template GEMM on the matrix cores,
 //     v_mfma_i32_32x32x32_i8.  For template row r and a strip of 32 outputs, out[y, x0+n] = sum_k I[y+r, x0+k] *
 //     T[r, k-n]: A = image rows (M = output rows), B[k][n] = T[r][k-n] is generated on chip from the LDS-resident
 //     template (16 KB) by unaligned reads, K = 32-byte steps along the row.  Pixels are biased to signed
 //     (p - 128) so they fit i8; the bias is undone exactly with the window sums the normaliser needs anyway:
 //     sum I*T = acc + 128*sum_window(I) + 128*sum(T) - 128^2*tw*th.  int32 accumulation is exact (|acc| < 2^31).
 //     8-bit inputs on the i8 path run at twice the bf16 MFMA rate named in BASELINE.json and give the integer-exact
-//     correlation (a bf16 GEMM of the same operands differs only by fp32 accumulation rounding).
-//   * everything else (CV_32F, multi-channel, bigger templates): a direct kernel, exact integers for 8U, double for 32F.
-// The post-processing restates common_matchTemplate on window sums from GPU-built integral images (double).
+//     correlation (a bf16 GEMM of the same operands differs only by fp32 accumulation rounding).  k_ccorr_ring_i8, with the
+//     window sums from the kernel itself (template rows >= 66) or from k_wsum_*; k_ccorr_mfma_i8 for images narrower than 4 pixels.
+//   2. matchBlocks8U  CV_8UC1, template of 129..512 per side: up to 4 x 4 blocks of <= 128 x 128, each through path 1, summed as integers.
+//   3. matchPlanes8U  CV_8U with 2-4 channels, template up to 128x128: every channel plane through path 1, summed as integers.
+//   4. matchBf16      CV_32FC1, template up to 512 per side: three or four products of split-bf16 operands (k_ccorr_bf16), window sums in double.
+//   5. matchDirect    everything else: k_ccorr_direct, exact integers for 8U, double for 32F, normalised on window sums from
+//     double integral images (integral.hip).
+// Every path restates common_matchTemplate on its window sums.  matchTemplateMask (runMatchMask) builds on the same correlations.
 #include "rt.h"
 #include "integral.h"
+#include <algorithm>
 #include <cfloat>
+#include <climits>
 #include <cmath>
 #include <cstring>
 #include <cstdio>
 #include <cstdlib>
+#include <type_traits>
 #include <vector>
 
 using namespace mi355;
 
 namespace {
 
-enum { D8U = MI355CV_8U, D32S = MI355CV_32S, D32F = MI355CV_32F, D64F = MI355CV_64F };
+enum { D8U = MI355CV_8U, D32F = MI355CV_32F };
 
-// ---------------------------------------------------------------------------------- integral images
-// cv::integral layout (sumpixels.simd.hpp): (H+1) x (W+1) x cn, first row / column zero.  sum in int32 (8-bit sources: exact, the
-// reference's default) or double, squared sum in double.  Three passes, each with enough independent work to fill the chip:
-//   rows    one workgroup per (row, channel): chunked scan of the row -> row-wise prefix sums
-//   colseg  one thread per (column, segment of IS_SEG rows): prefix down the segment in place, segment total to `aux`
-//   coladd  one thread per (column, segment >= 1): adds the totals of the segments above
-// (a single thread walking a whole column would leave all but ~16 CUs idle and serialise 2160 dependent adds).
-constexpr int IS_SEG = 64;
-
-template <typename TS>
-__global__ __launch_bounds__(256) void k_integral_rows(const uchar* __restrict__ src, size_t sstep, size_t sframe, int W, int H, int cn, int depth,
-                                                       TS* __restrict__ sum, size_t sumStep /*elements*/, size_t sumFrame,
-                                                       double* __restrict__ sq, size_t sqStep, size_t sqFrame)
-{
-    const int y = blockIdx.x, c = blockIdx.y;
-    src += (size_t)blockIdx.z * sframe; sum += (size_t)blockIdx.z * sumFrame; if (sq) sq += (size_t)blockIdx.z * sqFrame;
-    const uchar* row = src + (size_t)y * sstep;
-    const int chunk = (W + 255) / 256;
-    const int x0 = threadIdx.x * chunk, x1 = min(W, x0 + chunk);
-    auto px = [&](int x) -> double { return depth == D8U ? (double)row[x * cn + c] : (double)reinterpret_cast<const float*>(row)[x * cn + c]; };
-    TS s = 0; double q = 0;
-    for (int x = x0; x < x1; x++) { const double v = px(x); s += (TS)v; q += v * v; }
-    __shared__ TS ss[256];
-    __shared__ double qq[256];
-    ss[threadIdx.x] = s; qq[threadIdx.x] = q;
-    __syncthreads();
-    for (int o = 1; o < 256; o <<= 1) {                      // Hillis-Steele inclusive scan over the 256 chunk totals
-        TS a = 0; double b = 0;
-        if ((int)threadIdx.x >= o) { a = ss[threadIdx.x - o]; b = qq[threadIdx.x - o]; }
-        __syncthreads();
-        ss[threadIdx.x] += a; qq[threadIdx.x] += b;
-        __syncthreads();
-    }
-    TS ps = threadIdx.x ? ss[threadIdx.x - 1] : (TS)0; double pq = threadIdx.x ? qq[threadIdx.x - 1] : 0.0;
-    TS* srow = sum + (size_t)(y + 1) * sumStep;
-    double* qrow = sq ? sq + (size_t)(y + 1) * sqStep : nullptr;
-    if (threadIdx.x == 0) { srow[c] = 0; if (qrow) qrow[c] = 0; }
-    for (int x = x0; x < x1; x++) {
-        const double v = px(x);
-        ps += (TS)v; pq += v * v;
-        srow[(x + 1) * cn + c] = ps;
-        if (qrow) qrow[(x + 1) * cn + c] = pq;
-    }
-}
-
-// single-channel 8-bit rows, the common case: a thread owns 16 consecutive pixels (one 16-byte load when the row allows), the
-// 256 thread totals are scanned with wave shuffles + one LDS exchange, and the finished row goes through LDS so that the
-// global stores are lane-consecutive (a thread writing its own 16 results would touch 16 different 64-byte segments).
-template <typename TS>
-__global__ __launch_bounds__(256) void k_integral_rows_u8c1(const uchar* __restrict__ src, size_t sstep, size_t sframe, int W,
-                                                            TS* __restrict__ sum, size_t sumStep, size_t sumFrame,
-                                                            double* __restrict__ sq, size_t sqStep, size_t sqFrame)
-{
-    extern __shared__ __attribute__((aligned(16))) uchar ldsraw[];
-    const int y = blockIdx.x;
-    src += (size_t)blockIdx.z * sframe; sum += (size_t)blockIdx.z * sumFrame; if (sq) sq += (size_t)blockIdx.z * sqFrame;
-    const uchar* row = src + (size_t)y * sstep;
-    const int per = 16 * ((((W + 255) / 256) + 15) / 16);          // pixels per thread, a multiple of 16
-    TS* LS = reinterpret_cast<TS*>(ldsraw);                          // W + 1 sums
-    double* LQ = reinterpret_cast<double*>(ldsraw + (((size_t)(W + 1) * sizeof(TS) + 15) & ~(size_t)15));   // W + 1 squared sums
-    const int x0 = threadIdx.x * per, x1 = min(W, x0 + per);
-    const bool vec = ((((uintptr_t)row) | sstep) & 15) == 0;
-    unsigned s = 0; unsigned long long q = 0;                      // exact: 255 * per and 255^2 * per are far below 2^32 / 2^64
-    for (int x = x0; x < x1; x += 16) {
-        unsigned w[4] = {0, 0, 0, 0};
-        if (vec && x + 16 <= W) { const uint4 v = *reinterpret_cast<const uint4*>(row + x); w[0] = v.x; w[1] = v.y; w[2] = v.z; w[3] = v.w; }
-        else for (int b = 0; b < 16 && x + b < W; b++) w[b >> 2] |= (unsigned)row[x + b] << (8 * (b & 3));
-#pragma unroll
-        for (int b = 0; b < 16; b++) { const unsigned p = (w[b >> 2] >> (8 * (b & 3))) & 255u; s += p; q += p * p; }
-    }
-    // block-wide exclusive scan of (s, q): wave shuffle scan, then the four wave totals through LDS
-    __shared__ unsigned long long ws[4], wq[4];
-    unsigned long long ps = s, pq = q;
-    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    for (int o = 1; o < 64; o <<= 1) {
-        const unsigned long long a = __shfl_up(ps, o), b = __shfl_up(pq, o);
-        if (lane >= o) { ps += a; pq += b; }
-    }
-    if (lane == 63) { ws[wave] = ps; wq[wave] = pq; }
-    __syncthreads();
-    unsigned long long os = ps - s, oq = pq - q;                   // exclusive within the wave
-    for (int k = 0; k < wave; k++) { os += ws[k]; oq += wq[k]; }
-    if (threadIdx.x == 0) { LS[0] = 0; if (sq) LQ[0] = 0; }
-    TS rs = (TS)os; double rq = (double)oq;
-    for (int x = x0; x < x1; x++) {
-        const unsigned p = row[x];
-        rs += (TS)p; rq += (double)(p * p);
-        LS[x + 1] = rs; if (sq) LQ[x + 1] = rq;
-    }
-    __syncthreads();
-    TS* srow = sum + (size_t)(y + 1) * sumStep;
-    for (int x = threadIdx.x; x <= W; x += 256) srow[x] = LS[x];
-    if (sq) { double* qrow = sq + (size_t)(y + 1) * sqStep; for (int x = threadIdx.x; x <= W; x += 256) qrow[x] = LQ[x]; }
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_integral_colseg(T* __restrict__ a, size_t step, size_t frame, int Wc /* (W+1)*cn */, int H, T* __restrict__ aux, size_t auxFrame)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y;
-    if (x >= Wc) return;
-    a += (size_t)blockIdx.z * frame + x; aux += (size_t)blockIdx.z * auxFrame;
-    const int y0 = 1 + seg * IS_SEG, y1 = min(H + 1, y0 + IS_SEG);
-    if (seg == 0) a[0] = 0;
-    T s = 0;
-    int y = y0;
-    for (; y + 8 <= y1; y += 8) {
-        T v[8];
-#pragma unroll
-        for (int u = 0; u < 8; u++) v[u] = a[(size_t)(y + u) * step];
-#pragma unroll
-        for (int u = 0; u < 8; u++) { s += v[u]; a[(size_t)(y + u) * step] = s; }
-    }
-    for (; y < y1; y++) { s += a[(size_t)y * step]; a[(size_t)y * step] = s; }
-    aux[(size_t)seg * Wc + x] = s;
-}
-
-template <typename T>
-__global__ __launch_bounds__(256) void k_integral_coladd(T* __restrict__ a, size_t step, size_t frame, int Wc, int H, const T* __restrict__ aux, size_t auxFrame)
-{
-    const int x = blockIdx.x * 256 + threadIdx.x, seg = blockIdx.y + 1;
-    if (x >= Wc) return;
-    a += (size_t)blockIdx.z * frame + x; aux += (size_t)blockIdx.z * auxFrame;
-    T off = 0;
-    for (int s = 0; s < seg; s++) off += aux[(size_t)s * Wc + x];
-    const int y0 = 1 + seg * IS_SEG, y1 = min(H + 1, y0 + IS_SEG);
-#pragma unroll 8
-    for (int y = y0; y < y1; y++) a[(size_t)y * step] += off;
-}
-
-// column passes over one array; aux = nseg x Wc scratch elements per frame
-template <typename T>
-void integralColumns(T* a, size_t step, size_t frame, int Wc, int H, int nframes, T* aux, hipStream_t st)
-{
-    const int nseg = divUp(H, IS_SEG);
-    hipLaunchKernelGGL(k_integral_colseg<T>, dim3(divUp(Wc, 256), nseg, nframes), dim3(256), 0, st, a, step, frame, Wc, H, aux, (size_t)nseg * Wc);
-    if (nseg > 1)
-        hipLaunchKernelGGL(k_integral_coladd<T>, dim3(divUp(Wc, 256), nseg - 1, nframes), dim3(256), 0, st, a, step, frame, Wc, H, aux, (size_t)nseg * Wc);
-}
 
 // ---------------------------------------------------------------------------------- window sums (8UC1 fast path)
 // For CV_8UC1 the window sums sum(I) and sum(I^2) the post-processing needs are small exact integers (<= 255^2 * tw * th
@@ -1100,12 +971,299 @@ __global__ __launch_bounds__(256) void k_tm_finish_planes(const float* __restric
     *out = (float)num;
 }
 
+// ---------------------------------------------------------------------------------- the call, its switches, its paths
+// The A/B switches of the matcher, all read here.  Once per process: MI355CV_TM_RING=0 (k_ccorr_mfma_i8 instead of the ring kernel), MI355CV_TM_FUSE=0 (window sums by
+// k_wsum_* instead of in the ring kernel), MI355CV_TM_FIN=0 (k_tm_finish instead of the ring kernel's epilogue), MI355CV_TM_BF16=0 (CV_32FC1 on the direct kernel),
+// MI355CV_TM_BLOCKS=0 (no templates beyond 128 per side on the matrix cores), MI355CV_TM_MASK_I8=0 (float planes for every masked call).  On every call:
+// MI355CV_TM_PLANES=0 (multi-channel CV_8U on the direct kernel; the tests flip it inside one process) and MI355CV_TM_SERIAL (set: everything on one stream).
+struct TmSwitches { bool ringOff, fuseOff, finOff, bf16Off, blocksOff, maskI8Off; };
+const TmSwitches& tmSwitches()
+{
+    static const TmSwitches s = {envInt("MI355CV_TM_RING", 1) == 0, envInt("MI355CV_TM_FUSE", 1) == 0, envInt("MI355CV_TM_FIN", 1) == 0,
+                                 envInt("MI355CV_TM_BF16", 1) == 0, envInt("MI355CV_TM_BLOCKS", 1) == 0, envInt("MI355CV_TM_MASK_I8", 1) == 0};
+    return s;
+}
+bool tmPlanesOff() { return envInt("MI355CV_TM_PLANES", 1) == 0; }
+bool tmSerial() { return envInt("MI355CV_TM_SERIAL", INT_MIN) != INT_MIN; }
+
+// raises Kernel's limit of dynamic LDS, once per device
+template <auto Kernel> void raiseDynamicLds(int bytes)
+{
+    static bool set[16] = {};
+    const int dv = activeDevice() & 15;
+    if (!set[dv]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(Kernel), hipFuncAttributeMaxDynamicSharedMemorySize, bytes); set[dv] = true; }
+}
+template <int N> using KSteps = std::integral_constant<int, N>;                 // a `switch (KS)` table hands its case to a generic lambda as a type
+
+// k_ccorr_mfma_i8's LDS, image patch + template; the i8 paths take a template height only if it fits (every th <= 128 does)
+size_t mfmaLdsBytes(int th) { return (size_t)(MT_BM + th - 1) * MT_PPITCH + (size_t)th * MT_TPITCH; }
+bool mfmaLdsFits(int th) { return mfmaLdsBytes(th) <= 160 * 1024; }
+
+// where an i8 correlation left its window sums of I and I^2 (u32, pitch wp, wframe elements per frame)
 struct WOut { unsigned* w1; unsigned* w2; int wp; size_t wframe; };
 
-thread_local bool t_fourProducts = false;      // set by runMatchMask: its TM_CCORR building blocks feed differences of large terms (see BF_LAUNCH)
+// what the correlations inside the paths and inside runMatchMask ask for beyond the public arguments: `wout` comes with the internal method 6 (the raw int32
+// correlation as the result, no normalisation, see k_tm_finish_planes) and receives the window sums; `fourProducts` makes a TM_CCORR on the bf16 path take the mid*mid
+// product (runMatchMask: its results feed differences of large terms)
+int runMatchInner(const char* entry, const uchar* img, size_t istep, size_t iframe, int nframes, int iw, int ih, const uchar* tpl, size_t tstep, int tw, int th, int type,
+                  uchar* res, size_t rstep, size_t rframe, int method, WOut* wout, bool fourProducts);
 
-int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, int nframes, int iw, int ih,
-             const uchar* tpl, size_t tstep, int tw, int th, int type, uchar* res, size_t rstep, size_t rframe, int method, WOut* wout = nullptr)
+// One staged call of matchTemplate / matchTemplateBatch, as runMatchInner hands it to the paths below: images, results and template where the kernels find them.  Every
+// path is named after its kernel and answers NEXT_PATH when the call is not its to serve; they are tried in the order they stand here, matchDirect takes the rest.
+struct MatchCall {
+    const char* entry; Stager& stg; hipStream_t st;
+    const uchar* di; size_t dis, iframe; uchar* dr; size_t drs, rframe; const uchar* dt; size_t dts;          // device pointers, steps and frame strides (bytes)
+    int nframes, iw, ih, tw, th, depth, cn, method, rw, rh;
+    NormArgs na;
+    WOut* wout; bool fourProducts;
+
+    // the template's statistics, computed on the device into a copy of `na` as it stands now (+ the i8 kernels' copy of the template into tx)
+    const NormArgs* uploadStats(uchar* tx)
+    {
+        NormArgs* d = (NormArgs*)stg.param(&na, sizeof na);
+        if (d) hipLaunchKernelGGL(k_tm_tstats, dim3(1), dim3(1024), 0, st, dt, dts, depth, d, tx);
+        return d;
+    }
+
+    int matchRingI8()                                                              // k_ccorr_ring_i8 / k_ccorr_mfma_i8: CV_8UC1, templates up to 128 x 128
+    {
+        if (!(depth == D8U && cn == 1 && tw <= 128 && th <= 128 && (size_t)rw * rh >= 4096 && mfmaLdsFits(th))) return NEXT_PATH;
+        // Per frame: the MFMA kernel, window sums of I and I^2, and the bias removal + normalisation (k_tm_finish).
+        //  * ring kernel with th >= 66 (the default): the window sums come out of the MFMA kernel itself; frames go in chunks of up to
+        //    four per launch (two workgroups of different frames per CU), and the finish of one chunk runs on the auxiliary stream.
+        //  * otherwise two memory-bound kernels (k_wsum_rows / k_wsum_cols) on the auxiliary stream, under the MFMAs.
+        const TmSwitches& sw = tmSwitches();
+        const bool ringK = !sw.ringOff && iw >= 4;
+        const bool fused = ringK && !sw.fuseOff && th >= 66 && (iw & 3) == 0 && ((((uintptr_t)di) | dis | (nframes > 1 ? iframe : 0)) & 3) == 0 &&
+                           (unsigned long long)ih * dis < (1ull << 32);                      // the kernel's fastRow test: 32-bit row offsets
+        const bool fin = fused && !sw.finOff;                                       // bias removal + normalisation in the MFMA kernel's epilogue
+        const int wp = fused ? (rw + 3) & ~3 : rw;
+        const size_t s1frame = (size_t)rw * ih, wframe = (size_t)wp * rh;
+        unsigned* s1 = fused ? nullptr : (unsigned*)stg.scratch(s1frame * nframes * 4);
+        unsigned* q1 = fused ? nullptr : (unsigned*)stg.scratch(s1frame * nframes * 4);
+        unsigned* w1 = (unsigned*)stg.scratch(wframe * nframes * 4);
+        unsigned* w2 = (unsigned*)stg.scratch(wframe * nframes * 4);
+        uchar* dtx = (uchar*)stg.scratch((size_t)th * MT_TPITCH);                // signed, zero-padded copy of the template in the kernels' LDS layout
+        MI355_DECLINE_IF((!fused && (!s1 || !q1)) || !w1 || !w2 || !dtx);
+        na.useW = 1; na.wp = wp;
+        if (wout) { wout->w1 = w1; wout->w2 = w2; wout->wp = wp; wout->wframe = wframe; }
+        const NormArgs* dna = uploadStats(dtx);
+        MI355_DECLINE_IF(!dna);
+        const bool serial = tmSerial();                                             // experiments: everything on one stream
+        hipStream_t aux = serial ? st : auxStream();
+        hipEvent_t evIn = pooledEvent(0), evDone = pooledEvent(1);
+        MI355_DECLINE_IF((!serial && !aux) || !evIn || !evDone);
+        const size_t lds = mfmaLdsBytes(th);
+        const int KS = (tw + 62) / 32;
+        (void)hipEventRecord(evIn, st);                               // inputs (staged copies, template) are ordered on the main stream
+        (void)hipStreamWaitEvent(aux, evIn, 0);
+        for (int f = 0; f < nframes && !fused; f++) {
+            const uchar* dif = di + (size_t)f * iframe;
+            hipLaunchKernelGGL((k_wsum_rows<uchar, unsigned>), dim3(ih, 1, 1), dim3(256), (size_t)(iw + 1) * 4, aux, dif, dis, 0, iw, tw, rw, s1 + f * s1frame, q1 + f * s1frame, s1frame);
+            hipLaunchKernelGGL((k_wsum_cols<unsigned>), dim3(divUp(rw, 256), divUp(rh, WS_CH), 1), dim3(256), 0, aux, s1 + f * s1frame, q1 + f * s1frame, s1frame, th, rw, rh,
+                               w1 + f * wframe, w2 + f * wframe, wframe);
+        }
+        // frames per MFMA launch
+        const int chunk = ringK ? std::max(1, std::min(fin ? 64 : 4, nframes)) : 1;
+        const size_t ldsRing = (((size_t)th * MT_TPITCH + 15) & ~(size_t)15) + (size_t)4 * RG_RING * RG_RP + (size_t)4 * RG_WSCR;
+        for (int f = 0, c = 0; f < nframes; f += chunk, c++) {
+            const int nf = std::min(chunk, nframes - f);
+            const uchar* dif = di + (size_t)f * iframe;
+            int* rf = reinterpret_cast<int*>(dr + (size_t)f * rframe);
+            dim3 grid(divUp(rw, MT_BN), divUp(rh, MT_BM), nf);
+            auto launch = [&](auto ks) {
+                constexpr int KS_ = decltype(ks)::value;
+                if (fused) {
+                    raiseDynamicLds<k_ccorr_ring_i8<KS_, true>>(80 * 1024);
+                    hipLaunchKernelGGL((k_ccorr_ring_i8<KS_, true>), grid, dim3(256), ldsRing, st, dif, dis, iframe, iw, ih, dtx, tw, th, rf, drs, rframe, rw, rh,
+                                       w1 + f * wframe, w2 + f * wframe, wp, wframe, fin ? 1 : 0, dna);
+                } else if (ringK) {
+                    raiseDynamicLds<k_ccorr_ring_i8<KS_, false>>(80 * 1024);
+                    hipLaunchKernelGGL((k_ccorr_ring_i8<KS_, false>), grid, dim3(256), ldsRing, st, dif, dis, iframe, iw, ih, dtx, tw, th, rf, drs, rframe, rw, rh,
+                                       (unsigned*)nullptr, (unsigned*)nullptr, 0, (size_t)0, 0, dna);
+                } else {
+                    raiseDynamicLds<k_ccorr_mfma_i8<KS_>>(160 * 1024);
+                    hipLaunchKernelGGL((k_ccorr_mfma_i8<KS_>), grid, dim3(256), lds, st, dif, dis, 0, iw, ih, dtx, tw, th, rf, drs, 0, rw, rh);
+                }
+            };
+            switch (KS) { case 1: launch(KSteps<1>{}); break; case 2: launch(KSteps<2>{}); break; case 3: launch(KSteps<3>{}); break; case 4: launch(KSteps<4>{}); break; default: launch(KSteps<5>{}); }
+            if (fin) continue;
+            hipEvent_t evM = pooledEvent(2 + c % 62);
+            if (!evM) return MI355CV_ERROR_UNKNOWN;
+            (void)hipEventRecord(evM, st);
+            (void)hipStreamWaitEvent(aux, evM, 0);
+            hipLaunchKernelGGL(k_tm_finish, dim3(divUp(rw, 64), divUp(rh, 16), nf), dim3(256), 0, aux, reinterpret_cast<float*>(rf), drs, rframe,
+                               w1 + f * wframe, w2 + f * wframe, wframe, dna);
+        }
+        if (!fin) {
+            (void)hipEventRecord(evDone, aux);
+            (void)hipStreamWaitEvent(st, evDone, 0);                  // everything after this call on the main stream sees the results
+        }
+        if (ringK) noteKernel("k_ccorr_ring_i8<%d,%s> grid=%dx%dx%d x256 lds=%zu, %d frame(s)%s", std::min(KS, 5), fused ? "true" : "false", divUp(rw, MT_BN), divUp(rh, MT_BM), chunk, ldsRing,
+                              nframes, fin ? "" : fused ? " + k_tm_finish" : " + k_wsum_rows / k_wsum_cols + k_tm_finish");
+        else noteKernel("k_ccorr_mfma_i8<%d> grid=%dx%dx1 x256 lds=%zu, %d frame(s) + k_wsum_rows / k_wsum_cols + k_tm_finish", std::min(KS, 5), divUp(rw, MT_BN), divUp(rh, MT_BM), lds, nframes);
+        return stg.finish(entry);
+    }
+
+    // one CV_8UC1 correlation of matchBlocks8U / matchPlanes8U: the exact int32 plane into `out` (internal method 6), its window sums into slot k of ps
+    bool plane6(PlaneSums& ps, int k, const uchar* img, size_t istep, size_t ifr, int w, int h, const uchar* tpl, size_t tstep, int bw, int bh, float* out, size_t rps, size_t rplane)
+    {
+        WOut wo = {nullptr, nullptr, 0, 0};
+        const int rc = runMatchInner(entry, img, istep, ifr, nframes, w, h, tpl, tstep, bw, bh, MI355CV_MAKETYPE(D8U, 1), (uchar*)out, rps * 4, rplane * 4, 6, &wo, false);
+        ps.w1[k] = wo.w1; ps.w2[k] = wo.w2; ps.wp[k] = wo.wp; ps.wframe[k] = wo.wframe;
+        return rc == MI355CV_OK && wo.w1 && wo.w2;
+    }
+    void finishPlanes(const float* part, size_t rps, size_t rplane, const PlaneSums& ps, const NormArgs* dna)
+    {
+        hipLaunchKernelGGL(k_tm_finish_planes, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, part, rps, rplane, nframes, reinterpret_cast<float*>(dr), drs,
+                           nframes > 1 ? rframe : 0, ps, dna);
+    }
+
+    // CV_8UC1 templates of 129 .. 512 per side: the correlation is linear in the template, so it is the sum of the correlations of up to 4 x 4 blocks of <= 128 x 128 with the
+    // image shifted by the block's offset -- each an exact int32 plane of the matrix-core path (method 6), summed and normalised like the channel planes.  (k_ccorr_direct walks
+    // tw * th taps per output: ~30 ms per 4K frame at 129 x 129, ~120 ms at 256 x 256.)  Never hands the call on.
+    int matchBlocks8U()
+    {
+        if (!(depth == D8U && cn == 1 && (tw > 128 || th > 128) && tw <= 512 && th <= 512 && (size_t)rw * rh >= 4096 && !wout &&
+              !tmSwitches().blocksOff)) return NEXT_PATH;
+        const int nbx = divUp(tw, 128), nby = divUp(th, 128), nb = nbx * nby;                            // blocks start at multiples of 128: aligned sub-images, the last takes the rest
+        const size_t rps = ((size_t)rw + 3) & ~(size_t)3, rplane = rps * rh;                           // floats
+        float* part = (float*)stg.scratch(rplane * 4 * nframes * nb);
+        const NormArgs* dna = uploadStats(nullptr);
+        PlaneSums ps; memset(&ps, 0, sizeof ps);
+        ps.nblocks = nb;
+        for (int b = 0; b < nb; b++) {
+            const int ox = 128 * (b % nbx), oy = 128 * (b / nbx);
+            const int bw = std::min(128, tw - ox), bh = std::min(128, th - oy);
+            if (!part || !dna || !plane6(ps, b, di + (size_t)oy * dis + ox, dis, nframes > 1 ? iframe : 0, rw + bw - 1, rh + bh - 1, dt + (size_t)oy * dts + ox, dts, bw, bh,
+                                         part + (size_t)b * nframes * rplane, rps, rplane))
+                return setError(MI355CV_NOT_IMPLEMENTED, "%s: the block form of a %d x %d template could not be set up", entry, tw, th);
+        }
+        finishPlanes(part, rps, rplane, ps, dna);
+        noteKernel("matchTemplate %dx%d as %d blocks of <= 128 x 128 on the matrix cores + k_tm_finish_planes", tw, th, nb);
+        return stg.finish(entry);
+    }
+
+    // CV_8U with 2-4 channels: per-channel planes through the i8 path (each a TM_CCORR of CV_8UC1, method 6).  Out of scratch, TM_CCORR goes on to k_ccorr_direct
+    int matchPlanes8U()
+    {
+        if (!(depth == D8U && cn > 1 && tw <= 128 && th <= 128 && (size_t)rw * rh >= 4096 && mfmaLdsFits(th) && !tmPlanesOff())) return NEXT_PATH;
+        const size_t pstep = ((size_t)iw + 15) & ~(size_t)15, pplane = pstep * ih;
+        const size_t tps = ((size_t)tw + 15) & ~(size_t)15, tplane = tps * th;
+        const size_t rps = ((size_t)rw + 3) & ~(size_t)3, rplane = rps * rh;                       // floats
+        uchar* pi = (uchar*)stg.scratch(pplane * nframes * cn);
+        uchar* tp = (uchar*)stg.scratch(tplane * cn);
+        float* part = (float*)stg.scratch(rplane * 4 * nframes * cn);
+        const NormArgs* dna = uploadStats(nullptr);                                                 // statistics of the cn-channel template
+        auto served = [&]() -> bool {
+            if (!(pi && tp && part && dna)) return false;
+            hipLaunchKernelGGL(k_tm_split, dim3(divUp(iw, 64), divUp(ih, 4), nframes), dim3(256), 0, st, di, dis, nframes > 1 ? iframe : 0, iw, ih, cn, pi, pstep, pplane, nframes);
+            hipLaunchKernelGGL(k_tm_split, dim3(divUp(tw, 64), divUp(th, 4), 1), dim3(256), 0, st, dt, dts, 0, tw, th, cn, tp, tps, tplane, 1);
+            PlaneSums ps; memset(&ps, 0, sizeof ps);
+            for (int c = 0; c < cn; c++)
+                if (!plane6(ps, c, pi + (size_t)c * nframes * pplane, pstep, pplane, iw, ih, tp + (size_t)c * tplane, tps, tw, th, part + (size_t)c * nframes * rplane, rps, rplane)) return false;
+            finishPlanes(part, rps, rplane, ps, dna);
+            return true;
+        };
+        if (served()) {
+            noteKernel("matchTemplate %dx%d as %d per-channel planes on the matrix cores + k_tm_finish_planes", tw, th, cn);
+            return stg.finish(entry);
+        }
+        if (method != 2) return setError(MI355CV_NOT_IMPLEMENTED, "%s: out of scratch memory for the per-channel planes", entry);
+        return NEXT_PATH;
+    }
+
+    // CV_32FC1: three bf16 products on the matrix cores (k_ccorr_bf16) and window sums by a separable sliding box in double; templates beyond 128 per side as blocks.
+    // MI355CV_TM_BF16=0, or no scratch: k_ccorr_direct + integral images
+    int matchBf16()
+    {
+        const int tmax = tmSwitches().blocksOff ? 128 : 512;                          // beyond 128 per side: blocks of <= 128 x 128, their products accumulated
+        if (!(!tmSwitches().bf16Off && depth == D32F && cn == 1 && tw <= tmax && th <= tmax && (size_t)rw * rh >= 4096 && (drs & 3) == 0 && ((nframes > 1 ? rframe : 0) & 3) == 0 &&
+              (size_t)(iw + 1) * 8 <= 56 * 1024 && (dis & 3) == 0 && ((nframes > 1 ? iframe : 0) & 3) == 0 && ((uintptr_t)di & 3) == 0)) return NEXT_PATH;
+        const int ipitch = (iw + 7) & ~7;
+        const size_t iplane = (size_t)ipitch * ih;
+        unsigned short* ihi = (unsigned short*)stg.scratch(iplane * nframes * 2);
+        unsigned short* imid = (unsigned short*)stg.scratch(iplane * nframes * 2);
+        unsigned short* thi = (unsigned short*)stg.scratch((size_t)th * BF_TE * 2 + 64);
+        unsigned short* tmid = (unsigned short*)stg.scratch((size_t)th * BF_TE * 2 + 64);
+        // window sums of I and I^2 for every method but TM_CCORR: rows by an LDS prefix scan, columns by sliding sums, all in double
+        const size_t s1frame = (size_t)rw * ih, wframe = (size_t)rw * rh;
+        double *s1 = nullptr, *q1 = nullptr, *w1 = nullptr, *w2 = nullptr;
+        if (method != 2) {
+            s1 = (double*)stg.scratch(s1frame * nframes * 8); q1 = (double*)stg.scratch(s1frame * nframes * 8);
+            w1 = (double*)stg.scratch(wframe * nframes * 8); w2 = (double*)stg.scratch(wframe * nframes * 8);
+        }
+        if (!(ihi && imid && thi && tmid && (method == 2 || (s1 && q1 && w1 && w2)))) return NEXT_PATH;
+        hipLaunchKernelGGL(k_tm_split_bf16, dim3(divUp(ipitch, 64), divUp(ih, 4), nframes), dim3(256), 0, st, di, dis, nframes > 1 ? iframe : 0, iw, ih, ihi, imid, ipitch, iplane);
+        const bool four = (method != 2 && method != 3) || fourProducts;
+        const size_t lds = (size_t)(BF_BM + BF_JC - 1) * BF_PP + (size_t)BF_JC * BF_TP;
+        dim3 gb(divUp(rw, BF_BN), divUp(rh, BF_BM), nframes);
+        float* rf = reinterpret_cast<float*>(dr);
+        const size_t rfr = nframes > 1 ? rframe : 0;
+        // one product of an image plane with a template plane (block), written or accumulated into the result
+        auto product = [&](int KS, const unsigned short* ip, int ihb, int icols, const unsigned short* tp, int thb, int acc) {
+            auto one = [&](auto ks) {
+                constexpr int KS_ = decltype(ks)::value;
+                raiseDynamicLds<k_ccorr_bf16<KS_>>(160 * 1024);
+                hipLaunchKernelGGL((k_ccorr_bf16<KS_>), gb, dim3(256), lds, st, ip, ipitch, iplane, ihb, tp, thb, rf, drs, rfr, rw, rh, acc, icols);
+            };
+            switch (KS) { case 1: case 2: one(KSteps<2>{}); break; case 3: case 4: one(KSteps<4>{}); break; case 5: case 6: one(KSteps<6>{}); break; case 7: case 8: one(KSteps<8>{}); break; default: one(KSteps<10>{}); }
+        };
+        // templates beyond 128 per side: blocks of <= 128 x 128 starting at multiples of 128 (the correlation is linear in the template); each block's products are
+        // accumulated onto the result with the image planes shifted by the block's offset
+        const int nbx = divUp(tw, 128), nby = divUp(th, 128);
+        int KS = 0;
+        for (int b = 0; b < nbx * nby; b++) {
+            const int ox = 128 * (b % nbx), oy = 128 * (b / nbx), bw = std::min(128, tw - ox), bh = std::min(128, th - oy);
+            hipLaunchKernelGGL(k_tm_tpl_bf16, dim3(divUp(bh * BF_TE, 256)), dim3(256), 0, st, dt + (size_t)oy * dts + (size_t)ox * 4, dts, bw, bh, thi, tmid);
+            KS = (bw + 31 + 15) / 16;                                                 // K steps of 16 columns covering bw + 31
+            const unsigned short* ih0 = ihi + (size_t)oy * ipitch + ox; const unsigned short* im0 = imid + (size_t)oy * ipitch + ox;
+            product(KS, ih0, ih - oy, ipitch - ox, thi, bh, b > 0);
+            product(KS, ih0, ih - oy, ipitch - ox, tmid, bh, 1);
+            product(KS, im0, ih - oy, ipitch - ox, thi, bh, 1);
+            /* TM_SQDIFF* / TM_CCOEFF*: the result is a difference of large terms (window energy - 2 corr + template energy; corr - mean product), which amplifies the
+               ~2^-17 relative error of the dropped mid * mid term near a perfect match and on images with a large offset: those methods take the fourth product */
+            if (four) product(KS, im0, ih - oy, ipitch - ox, tmid, bh, 1);
+        }
+        if (method != 2) {
+            const NormArgs* dna = uploadStats(nullptr);
+            MI355_DECLINE_IF(!dna);
+            hipLaunchKernelGGL((k_wsum_rows<float, double>), dim3(ih, 1, nframes), dim3(256), (size_t)(iw + 1) * 8, st, di, dis, nframes > 1 ? iframe : 0, iw, tw, rw, s1, q1, s1frame);
+            hipLaunchKernelGGL((k_wsum_cols<double>), dim3(divUp(rw, 256), divUp(rh, WS_CH), nframes), dim3(256), 0, st, s1, q1, s1frame, th, rw, rh, w1, w2, wframe);
+            hipLaunchKernelGGL(k_tm_finish_f, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, rf, drs, rfr, w1, w2, wframe, rw, dna);
+        }
+        noteKernel("k_ccorr_bf16<%d> x%d (hi*hi + hi*mid + mid*hi%s) x %d block(s) grid=%ux%ux%u x256 lds=%zu", KS, four ? 4 : 3, four ? " + mid*mid" : "", nbx * nby, gb.x, gb.y, gb.z, lds);
+        return stg.finish(entry);
+    }
+
+    // k_ccorr_direct: every other call, and what matchPlanes8U / matchBf16 hand on.  Exact integers for CV_8U, double for CV_32F; every method but TM_CCORR normalises on
+    // window sums from double integral images, which this path builds for itself -- k_tm_normalize is never launched without them
+    int matchDirect()
+    {
+        const size_t isteps = (size_t)(iw + 1) * cn, iframeD = isteps * (ih + 1);                 // doubles per integral row / frame
+        double* dsum = nullptr; double* dsq = nullptr;
+        if (method != 2) {
+            dsum = (double*)stg.scratch(iframeD * nframes * sizeof(double));
+            dsq = (double*)stg.scratch(iframeD * nframes * sizeof(double));
+            MI355_DECLINE_IF(!dsum || !dsq);
+            double* aux = (double*)stg.scratch(integralSumSqAuxBytes(iw, ih, cn, nframes));
+            MI355_DECLINE_IF(!aux);
+            integralSumSq(di, dis, iframe, iw, ih, cn, depth, nframes, dsum, dsq, aux, st);
+        }
+        dim3 grid(divUp(rw, 64), divUp(rh, 4), nframes);
+        hipLaunchKernelGGL(k_ccorr_direct, grid, dim3(256), 0, st, di, dis, iframe, dt, dts, tw, th, cn, depth, reinterpret_cast<float*>(dr), drs, rframe, rw, rh);
+        if (method != 2) {
+            const NormArgs* dna = uploadStats(nullptr);
+            MI355_DECLINE_IF(!dna);
+            hipLaunchKernelGGL(k_tm_normalize, grid, dim3(256), 0, st, reinterpret_cast<float*>(dr), drs, rframe, dsum, dsq, isteps, iframeD, dna);
+        }
+        noteKernel("k_ccorr_direct grid=%ux%ux%u x256 depth=%d cn=%d%s", grid.x, grid.y, grid.z, depth, cn, method != 2 ? " + k_tm_normalize on integral images" : "");
+        return stg.finish(entry);
+    }
+};
+
+int runMatchInner(const char* entry, const uchar* img, size_t istep, size_t iframe, int nframes, int iw, int ih, const uchar* tpl, size_t tstep, int tw, int th, int type,
+                  uchar* res, size_t rstep, size_t rframe, int method, WOut* wout, bool fourProducts)
 {
     MI355_DECLINE_IF(disabled());
     const int depth = MI355CV_MAT_DEPTH(type), cn = MI355CV_MAT_CN(type);
@@ -1128,237 +1286,18 @@ int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, i
     NormArgs na; memset(&na, 0, sizeof na);
     na.method = method; na.cn = cn; na.tw = tw; na.th = th; na.rw = rw; na.rh = rh;
     const double area = (double)tw * th; na.invArea = 1. / area;
-    hipStream_t st = stream();
-    auto uploadStats = [&](uchar* tx) -> const NormArgs* {
-        NormArgs* d = (NormArgs*)stg.param(&na, sizeof na);
-        if (d) hipLaunchKernelGGL(k_tm_tstats, dim3(1), dim3(1024), 0, st, dt, dts, depth, d, tx);
-        return d;
-    };
-    // integral images: needed by every method but TM_CCORR, and by the MFMA path's bias correction
-    const bool useMfma = depth == D8U && cn == 1 && tw <= 128 && th <= 128 && (size_t)rw * rh >= 4096 &&
-                         (size_t)(MT_BM + th - 1) * MT_PPITCH + (size_t)th * MT_TPITCH <= 160 * 1024;
-    // CV_8U with 2-4 channels: per-channel planes through the MFMA path (each a TM_CCORR of CV_8UC1, by this same function)
-    const bool planes = depth == D8U && cn > 1 && tw <= 128 && th <= 128 && (size_t)rw * rh >= 4096 &&
-                        (size_t)(MT_BM + th - 1) * MT_PPITCH + (size_t)th * MT_TPITCH <= 160 * 1024 && !(std::getenv("MI355CV_TM_PLANES") && atoi(std::getenv("MI355CV_TM_PLANES")) == 0);
-    // CV_32FC1: three bf16 products on the matrix cores (k_ccorr_bf16) and window sums by a separable sliding box in double; MI355CV_TM_BF16=0 keeps the
-    // direct kernel + integral images
-    static const bool bf16Off = std::getenv("MI355CV_TM_BF16") && atoi(std::getenv("MI355CV_TM_BF16")) == 0;
-    static const bool blocksOff = std::getenv("MI355CV_TM_BLOCKS") && atoi(std::getenv("MI355CV_TM_BLOCKS")) == 0;
-    const int tmax = blocksOff ? 128 : 512;                                       // beyond 128 per side: blocks of <= 128 x 128 (see `blocks` below), their products accumulated
-    const bool bf16Path = !bf16Off && depth == D32F && cn == 1 && tw <= tmax && th <= tmax && (size_t)rw * rh >= 4096 && (drs & 3) == 0 && ((nframes > 1 ? rframe : 0) & 3) == 0 &&
-                          (size_t)(iw + 1) * 8 <= 56 * 1024 && (dis & 3) == 0 && ((nframes > 1 ? iframe : 0) & 3) == 0 && ((uintptr_t)di & 3) == 0;
-    // CV_8UC1 templates of 129 .. 512 per side: the correlation is linear in the template, so it is the sum of the correlations of up to 4 x 4 blocks of <= 128 x 128 with the
-    // image shifted by the block's offset -- each an exact int32 plane of the matrix-core path (method 6), summed and normalised like the channel planes.  (k_ccorr_direct walks
-    // tw * th taps per output: ~30 ms per 4K frame at 129 x 129, ~120 ms at 256 x 256.)
-    const bool blocks = depth == D8U && cn == 1 && (tw > 128 || th > 128) && tw <= 512 && th <= 512 && (size_t)rw * rh >= 4096 && !wout &&
-                        !blocksOff;
-    const bool needInt = method != 2 && !useMfma && !planes && !bf16Path && !blocks;
-    const size_t isteps = (size_t)(iw + 1) * cn;                                   // doubles per integral row
-    const size_t iframeD = isteps * (ih + 1);
-    double* dsum = nullptr; double* dsq = nullptr;
-    if (needInt) {
-        dsum = (double*)stg.scratch(iframeD * nframes * sizeof(double));
-        dsq = (double*)stg.scratch(iframeD * nframes * sizeof(double));
-        MI355_DECLINE_IF(!dsum || !dsq);
-        const int nseg = divUp(ih, IS_SEG);
-        double* aux = (double*)stg.scratch((size_t)nseg * isteps * nframes * sizeof(double));
-        MI355_DECLINE_IF(!aux);
-        hipLaunchKernelGGL(k_integral_rows<double>, dim3(ih, cn, nframes), dim3(256), 0, st, di, dis, iframe, iw, ih, cn, depth, dsum, isteps, iframeD, dsq, isteps, iframeD);
-        integralColumns<double>(dsum, isteps, iframeD, (int)isteps, ih, nframes, aux, st);
-        integralColumns<double>(dsq, isteps, iframeD, (int)isteps, ih, nframes, aux, st);
-    }
-    const size_t s1frame = (size_t)rw * ih;
-    if (useMfma) {
-        // Per frame: the MFMA kernel, window sums of I and I^2, and the bias removal + normalisation (k_tm_finish).
-        //  * ring kernel with th >= 66 (the default): the window sums come out of the MFMA kernel itself; frames go in chunks of up to
-        //    four per launch (two workgroups of different frames per CU), and the finish of one chunk runs on the auxiliary stream.
-        //  * otherwise two memory-bound kernels (k_wsum_rows / k_wsum_cols) on the auxiliary stream, under the MFMAs.
-        static const bool ringOff = std::getenv("MI355CV_TM_RING") && atoi(std::getenv("MI355CV_TM_RING")) == 0;
-        static const bool fuseOff = std::getenv("MI355CV_TM_FUSE") && atoi(std::getenv("MI355CV_TM_FUSE")) == 0;
-        const bool ringK = !ringOff && iw >= 4;
-        const bool fused = ringK && !fuseOff && th >= 66 && (iw & 3) == 0 && ((((uintptr_t)di) | dis | (nframes > 1 ? iframe : 0)) & 3) == 0 &&
-                           (unsigned long long)ih * dis < (1ull << 32);                      // the kernel's fastRow test: 32-bit row offsets
-        static const bool finOff = std::getenv("MI355CV_TM_FIN") && atoi(std::getenv("MI355CV_TM_FIN")) == 0;
-        const bool fin = fused && !finOff;                                          // bias removal + normalisation in the MFMA kernel's epilogue
-        const int wp = fused ? (rw + 3) & ~3 : rw;
-        const size_t wframe = (size_t)wp * rh;
-        unsigned* s1 = fused ? nullptr : (unsigned*)stg.scratch(s1frame * nframes * 4);
-        unsigned* q1 = fused ? nullptr : (unsigned*)stg.scratch(s1frame * nframes * 4);
-        unsigned* w1 = (unsigned*)stg.scratch(wframe * nframes * 4);
-        unsigned* w2 = (unsigned*)stg.scratch(wframe * nframes * 4);
-        uchar* dtx = (uchar*)stg.scratch((size_t)th * MT_TPITCH);                // signed, zero-padded copy of the template in the kernels' LDS layout
-        MI355_DECLINE_IF((!fused && (!s1 || !q1)) || !w1 || !w2 || !dtx);
-        na.useW = 1; na.wp = wp;
-        if (wout) { wout->w1 = w1; wout->w2 = w2; wout->wp = wp; wout->wframe = wframe; }
-        const NormArgs* dna = uploadStats(dtx);
-        MI355_DECLINE_IF(!dna);
-        const bool serial = std::getenv("MI355CV_TM_SERIAL") != nullptr;            // experiments: everything on one stream
-        hipStream_t aux = serial ? st : auxStream();
-        hipEvent_t evIn = pooledEvent(0), evDone = pooledEvent(1);
-        MI355_DECLINE_IF((!serial && !aux) || !evIn || !evDone);
-        const size_t lds = (size_t)(MT_BM + th - 1) * MT_PPITCH + (size_t)th * MT_TPITCH;
-        const int KS = (tw + 62) / 32;
-        (void)hipEventRecord(evIn, st);                               // inputs (staged copies, template) are ordered on the main stream
-        (void)hipStreamWaitEvent(aux, evIn, 0);
-        for (int f = 0; f < nframes && !fused; f++) {
-            const uchar* dif = di + (size_t)f * iframe;
-            hipLaunchKernelGGL((k_wsum_rows<uchar, unsigned>), dim3(ih, 1, 1), dim3(256), (size_t)(iw + 1) * 4, aux, dif, dis, 0, iw, tw, rw, s1 + f * s1frame, q1 + f * s1frame, s1frame);
-            hipLaunchKernelGGL((k_wsum_cols<unsigned>), dim3(divUp(rw, 256), divUp(rh, WS_CH), 1), dim3(256), 0, aux, s1 + f * s1frame, q1 + f * s1frame, s1frame, th, rw, rh,
-                               w1 + f * wframe, w2 + f * wframe, wframe);
-        }
-        // frames per MFMA launch
-        const int chunk = ringK ? std::max(1, std::min(fin ? 64 : 4, nframes)) : 1;
-        const size_t ldsRing = (((size_t)th * MT_TPITCH + 15) & ~(size_t)15) + (size_t)4 * RG_RING * RG_RP + (size_t)4 * RG_WSCR;
-        for (int f = 0, c = 0; f < nframes; f += chunk, c++) {
-            const int nf = std::min(chunk, nframes - f);
-            const uchar* dif = di + (size_t)f * iframe;
-            int* rf = reinterpret_cast<int*>(dr + (size_t)f * rframe);
-            dim3 grid(divUp(rw, MT_BN), divUp(rh, MT_BM), nf);
-#define MFMA_LAUNCH(KS_) do { static bool attrSet[16] = {}; const int dv_ = activeDevice() & 15; \
-            if (!attrSet[dv_]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ccorr_mfma_i8<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ccorr_ring_i8<KS_, false>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); \
-                (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ccorr_ring_i8<KS_, true>), hipFuncAttributeMaxDynamicSharedMemorySize, 80 * 1024); attrSet[dv_] = true; } \
-            if (fused) hipLaunchKernelGGL((k_ccorr_ring_i8<KS_, true>), grid, dim3(256), ldsRing, st, dif, dis, iframe, iw, ih, dtx, tw, th, rf, drs, rframe, rw, rh, \
-                                          w1 + f * wframe, w2 + f * wframe, wp, wframe, fin ? 1 : 0, dna); \
-            else if (ringK) hipLaunchKernelGGL((k_ccorr_ring_i8<KS_, false>), grid, dim3(256), ldsRing, st, dif, dis, iframe, iw, ih, dtx, tw, th, rf, drs, rframe, rw, rh, \
-                                               (unsigned*)nullptr, (unsigned*)nullptr, 0, (size_t)0, 0, dna); \
-            else hipLaunchKernelGGL((k_ccorr_mfma_i8<KS_>), grid, dim3(256), lds, st, dif, dis, 0, iw, ih, dtx, tw, th, rf, drs, 0, rw, rh); } while (0)
-            switch (KS) { case 1: MFMA_LAUNCH(1); break; case 2: MFMA_LAUNCH(2); break; case 3: MFMA_LAUNCH(3); break; case 4: MFMA_LAUNCH(4); break; default: MFMA_LAUNCH(5); }
-#undef MFMA_LAUNCH
-            if (fin) continue;
-            hipEvent_t evM = pooledEvent(2 + c % 62);
-            if (!evM) return MI355CV_ERROR_UNKNOWN;
-            (void)hipEventRecord(evM, st);
-            (void)hipStreamWaitEvent(aux, evM, 0);
-            hipLaunchKernelGGL(k_tm_finish, dim3(divUp(rw, 64), divUp(rh, 16), nf), dim3(256), 0, aux, reinterpret_cast<float*>(rf), drs, rframe,
-                               w1 + f * wframe, w2 + f * wframe, wframe, dna);
-        }
-        if (!fin) {
-            (void)hipEventRecord(evDone, aux);
-            (void)hipStreamWaitEvent(st, evDone, 0);                  // everything after this call on the main stream sees the results
-        }
-    } else {
-        bool done = false;
-        if (blocks) {
-            const int nbx = divUp(tw, 128), nby = divUp(th, 128), nb = nbx * nby;                            // blocks start at multiples of 128: aligned sub-images, the last takes the rest
-            const size_t rps = ((size_t)rw + 3) & ~(size_t)3, rplane = rps * rh;                           // floats
-            float* part = (float*)stg.scratch(rplane * 4 * nframes * nb);
-            const NormArgs* dna = uploadStats(nullptr);
-            if (part && dna) {
-                PlaneSums ps; memset(&ps, 0, sizeof ps);
-                ps.nblocks = nb;
-                done = true;
-                for (int b = 0; b < nb && done; b++) {
-                    const int ox = 128 * (b % nbx), oy = 128 * (b / nbx);
-                    const int bw = std::min(128, tw - ox), bh = std::min(128, th - oy);
-                    WOut wo = {nullptr, nullptr, 0, 0};
-                    done = runMatch(entry, di + (size_t)oy * dis + ox, dis, nframes > 1 ? iframe : 0, nframes, rw + bw - 1, rh + bh - 1, dt + (size_t)oy * dts + ox, dts, bw, bh,
-                                    MI355CV_MAKETYPE(D8U, 1), (uchar*)(part + (size_t)b * nframes * rplane), rps * 4, rplane * 4, 6, &wo) == MI355CV_OK && wo.w1 && wo.w2;
-                    ps.w1[b] = wo.w1; ps.w2[b] = wo.w2; ps.wp[b] = wo.wp; ps.wframe[b] = wo.wframe;
-                }
-                if (done) {
-                    hipLaunchKernelGGL(k_tm_finish_planes, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, part, rps, rplane, nframes, reinterpret_cast<float*>(dr), drs,
-                                       nframes > 1 ? rframe : 0, ps, dna);
-                    noteKernel("matchTemplate %dx%d as %d blocks of <= 128 x 128 on the matrix cores + k_tm_finish_planes", tw, th, nb);
-                    return stg.finish(entry);
-                }
-            }
-            return setError(MI355CV_NOT_IMPLEMENTED, "%s: the block form of a %d x %d template could not be set up", entry, tw, th);
-        }
-        if (planes) {
-            const size_t pstep = ((size_t)iw + 15) & ~(size_t)15, pplane = pstep * ih;
-            const size_t tps = ((size_t)tw + 15) & ~(size_t)15, tplane = tps * th;
-            const size_t rps = ((size_t)rw + 3) & ~(size_t)3, rplane = rps * rh;                       // floats
-            uchar* pi = (uchar*)stg.scratch(pplane * nframes * cn);
-            uchar* tp = (uchar*)stg.scratch(tplane * cn);
-            float* part = (float*)stg.scratch(rplane * 4 * nframes * cn);
-            const NormArgs* dna = uploadStats(nullptr);                                                 // statistics of the cn-channel template
-            if (pi && tp && part && dna) {
-                hipLaunchKernelGGL(k_tm_split, dim3(divUp(iw, 64), divUp(ih, 4), nframes), dim3(256), 0, st, di, dis, nframes > 1 ? iframe : 0, iw, ih, cn, pi, pstep, pplane, nframes);
-                hipLaunchKernelGGL(k_tm_split, dim3(divUp(tw, 64), divUp(th, 4), 1), dim3(256), 0, st, dt, dts, 0, tw, th, cn, tp, tps, tplane, 1);
-                PlaneSums ps; memset(&ps, 0, sizeof ps);
-                done = true;
-                for (int c = 0; c < cn && done; c++) {
-                    WOut wo = {nullptr, nullptr, 0, 0};
-                    done = runMatch(entry, pi + (size_t)c * nframes * pplane, pstep, pplane, nframes, iw, ih, tp + (size_t)c * tplane, tps, tw, th, MI355CV_MAKETYPE(D8U, 1),
-                                    (uchar*)(part + (size_t)c * nframes * rplane), rps * 4, rplane * 4, 6, &wo) == MI355CV_OK && wo.w1 && wo.w2;
-                    ps.w1[c] = wo.w1; ps.w2[c] = wo.w2; ps.wp[c] = wo.wp; ps.wframe[c] = wo.wframe;
-                }
-                if (done)
-                    hipLaunchKernelGGL(k_tm_finish_planes, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, part, rps, rplane, nframes, reinterpret_cast<float*>(dr), drs,
-                                       nframes > 1 ? rframe : 0, ps, dna);
-            }
-            if (done) return stg.finish(entry);
-            if (method != 2) return setError(MI355CV_NOT_IMPLEMENTED, "%s: out of scratch memory for the per-channel planes", entry);   // (no integral images were built)
-        }
-        if (!done && bf16Path) {
-            const int ipitch = (iw + 7) & ~7;
-            const size_t iplane = (size_t)ipitch * ih;
-            unsigned short* ihi = (unsigned short*)stg.scratch(iplane * nframes * 2);
-            unsigned short* imid = (unsigned short*)stg.scratch(iplane * nframes * 2);
-            unsigned short* thi = (unsigned short*)stg.scratch((size_t)th * BF_TE * 2 + 64);
-            unsigned short* tmid = (unsigned short*)stg.scratch((size_t)th * BF_TE * 2 + 64);
-            // window sums of I and I^2 for every method but TM_CCORR: rows by an LDS prefix scan, columns by sliding sums, all in double
-            const size_t s1frame = (size_t)rw * ih, wframe = (size_t)rw * rh;
-            double *s1 = nullptr, *q1 = nullptr, *w1 = nullptr, *w2 = nullptr;
-            if (method != 2) {
-                s1 = (double*)stg.scratch(s1frame * nframes * 8); q1 = (double*)stg.scratch(s1frame * nframes * 8);
-                w1 = (double*)stg.scratch(wframe * nframes * 8); w2 = (double*)stg.scratch(wframe * nframes * 8);
-            }
-            if (ihi && imid && thi && tmid && (method == 2 || (s1 && q1 && w1 && w2))) {
-                hipLaunchKernelGGL(k_tm_split_bf16, dim3(divUp(ipitch, 64), divUp(ih, 4), nframes), dim3(256), 0, st, di, dis, nframes > 1 ? iframe : 0, iw, ih, ihi, imid, ipitch, iplane);
-                const bool four = (method != 2 && method != 3) || t_fourProducts;
-                const size_t lds = (size_t)(BF_BM + BF_JC - 1) * BF_PP + (size_t)BF_JC * BF_TP;
-                dim3 gb(divUp(rw, BF_BN), divUp(rh, BF_BM), nframes);
-                float* rf = reinterpret_cast<float*>(dr);
-                const size_t rfr = nframes > 1 ? rframe : 0;
-                // one product of an image plane with a template plane (block), written or accumulated into the result
-                auto product = [&](int KS, const unsigned short* ip, int ihb, int icols, const unsigned short* tp, int thb, int acc) {
-#define BF_ONE(KS_) do { static bool attrSet[16] = {}; const int dv_ = activeDevice() & 15; \
-                    if (!attrSet[dv_]) { (void)hipFuncSetAttribute(reinterpret_cast<const void*>(k_ccorr_bf16<KS_>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024); attrSet[dv_] = true; } \
-                    hipLaunchKernelGGL((k_ccorr_bf16<KS_>), gb, dim3(256), lds, st, ip, ipitch, iplane, ihb, tp, thb, rf, drs, rfr, rw, rh, acc, icols); } while (0)
-                    switch (KS) { case 1: case 2: BF_ONE(2); break; case 3: case 4: BF_ONE(4); break; case 5: case 6: BF_ONE(6); break; case 7: case 8: BF_ONE(8); break; default: BF_ONE(10); }
-#undef BF_ONE
-                };
-                // templates beyond 128 per side: blocks of <= 128 x 128 starting at multiples of 128 (the correlation is linear in the template); each block's products are
-                // accumulated onto the result with the image planes shifted by the block's offset
-                const int nbx = divUp(tw, 128), nby = divUp(th, 128);
-                int KS = 0;
-                for (int b = 0; b < nbx * nby; b++) {
-                    const int ox = 128 * (b % nbx), oy = 128 * (b / nbx), bw = std::min(128, tw - ox), bh = std::min(128, th - oy);
-                    hipLaunchKernelGGL(k_tm_tpl_bf16, dim3(divUp(bh * BF_TE, 256)), dim3(256), 0, st, dt + (size_t)oy * dts + (size_t)ox * 4, dts, bw, bh, thi, tmid);
-                    KS = (bw + 31 + 15) / 16;                                                 // K steps of 16 columns covering bw + 31
-                    const unsigned short* ih0 = ihi + (size_t)oy * ipitch + ox; const unsigned short* im0 = imid + (size_t)oy * ipitch + ox;
-                    product(KS, ih0, ih - oy, ipitch - ox, thi, bh, b > 0);
-                    product(KS, ih0, ih - oy, ipitch - ox, tmid, bh, 1);
-                    product(KS, im0, ih - oy, ipitch - ox, thi, bh, 1);
-                    /* TM_SQDIFF* / TM_CCOEFF*: the result is a difference of large terms (window energy - 2 corr + template energy; corr - mean product), which amplifies the
-                       ~2^-17 relative error of the dropped mid * mid term near a perfect match and on images with a large offset: those methods take the fourth product */
-                    if (four) product(KS, im0, ih - oy, ipitch - ox, tmid, bh, 1);
-                }
-                if (method != 2) {
-                    const NormArgs* dna = uploadStats(nullptr);
-                    MI355_DECLINE_IF(!dna);
-                    hipLaunchKernelGGL((k_wsum_rows<float, double>), dim3(ih, 1, nframes), dim3(256), (size_t)(iw + 1) * 8, st, di, dis, nframes > 1 ? iframe : 0, iw, tw, rw, s1, q1, s1frame);
-                    hipLaunchKernelGGL((k_wsum_cols<double>), dim3(divUp(rw, 256), divUp(rh, WS_CH), nframes), dim3(256), 0, st, s1, q1, s1frame, th, rw, rh, w1, w2, wframe);
-                    hipLaunchKernelGGL(k_tm_finish_f, dim3(divUp(rw, 64), divUp(rh, 4), nframes), dim3(256), 0, st, rf, drs, rfr, w1, w2, wframe, rw, dna);
-                }
-                noteKernel("k_ccorr_bf16<%d> x%d (hi*hi + hi*mid + mid*hi%s) x %d block(s) grid=%ux%ux%u x256 lds=%zu", KS, four ? 4 : 3, four ? " + mid*mid" : "", nbx * nby, gb.x, gb.y, gb.z, lds);
-                done = true;
-                return stg.finish(entry);
-            }
-        }
-        dim3 grid(divUp(rw, 64), divUp(rh, 4), nframes);
-        if (!done)
-            hipLaunchKernelGGL(k_ccorr_direct, grid, dim3(256), 0, st, di, dis, iframe, dt, dts, tw, th, cn, depth, reinterpret_cast<float*>(dr), drs, rframe, rw, rh);
-        if (method != 2) {
-            const NormArgs* dna = uploadStats(nullptr);
-            MI355_DECLINE_IF(!dna);
-            dim3 g2(divUp(rw, 64), divUp(rh, 4), nframes);
-            hipLaunchKernelGGL(k_tm_normalize, g2, dim3(256), 0, st, reinterpret_cast<float*>(dr), drs, rframe, dsum, dsq, isteps, iframeD, dna);
-        }
-    }
-    return stg.finish(entry);
+    MatchCall c = {entry, stg, stream(), di, dis, iframe, dr, drs, rframe, dt, dts, nframes, iw, ih, tw, th, depth, cn, method, rw, rh, na, wout, fourProducts};
+    // the dispatch rule: the first path that takes the call serves it
+    static int (MatchCall::* const paths[])() = {&MatchCall::matchRingI8, &MatchCall::matchBlocks8U, &MatchCall::matchPlanes8U, &MatchCall::matchBf16};
+    for (auto path : paths) { const int rc = (c.*path)(); if (rc != NEXT_PATH) return rc; }
+    return c.matchDirect();
+}
+
+// what the public entries call: no window sums out, three bf16 products where three do
+int runMatch(const char* entry, const uchar* img, size_t istep, size_t iframe, int nframes, int iw, int ih,
+             const uchar* tpl, size_t tstep, int tw, int th, int type, uchar* res, size_t rstep, size_t rframe, int method)
+{
+    return runMatchInner(entry, img, istep, iframe, nframes, iw, ih, tpl, tstep, tw, th, type, res, rstep, rframe, method, nullptr, false);
 }
 
 // ---------------------------------------------------------------------------------- matchTemplateMask (templmatch.cpp:762-904)
@@ -1431,6 +1370,83 @@ __global__ __launch_bounds__(256) void k_tm_mask_finish(const float* __restrict_
     reinterpret_cast<float*>(reinterpret_cast<uchar*>(res) + (size_t)y * rstep)[x] = r;
 }
 
+// One masked call after runMatchMask's host preparation: the staged image and result, the template-sized operands as the reference's Mat expressions give them
+// (T, M, M^2 and K per channel, nt = tw * th floats each), and the finishing kernel's arguments.  Two routes: byte planes, else float planes.
+struct MaskCall {
+    const char* entry; Stager& stg; hipStream_t st;
+    const uchar* di; size_t dis; uchar* dr; size_t drs;
+    int iw, ih, tw, th, depth, cn, method, rw, rh;
+    bool binary, coeff, needI2;
+    size_t nt; const std::vector<float>& T; const std::vector<float>& M; const std::vector<float>& M2; const std::vector<float>& K;
+    int rpitch; size_t rplane;
+    MaskFin fin;
+
+    void finish(const float* part)
+    {
+        fin.pitch = rpitch; fin.plane = rplane;
+        hipLaunchKernelGGL(k_tm_mask_finish, dim3(divUp(rw, 64), divUp(rh, 4)), dim3(256), 0, st, part, reinterpret_cast<float*>(dr), drs, fin);
+    }
+
+    // CV_8U images under a binary mask, methods without a mean: exact i8 correlations of byte planes (k_tm_mask_planes_u8)
+    int bytePlanes()
+    {
+        if (!(!tmSwitches().maskI8Off && depth == D8U && binary && !coeff)) return NEXT_PATH;        // MI355CV_TM_MASK_I8=0: the float planes for every case (A/B runs)
+        const int p8 = (iw + 15) & ~15; const size_t plane8 = (size_t)p8 * ih;
+        uchar* b8 = (uchar*)stg.scratch(plane8 * cn * (needI2 ? 3 : 1));
+        float* part = (float*)stg.scratch(rplane * 16 * 4);
+        std::vector<uchar> K8(nt * cn), M8(nt * cn);
+        for (size_t i = 0; i < nt * cn; i++) { K8[i] = (uchar)(T[i] * M[i]); M8[i] = (uchar)M[i]; }
+        uchar* dk8 = (uchar*)stg.param(K8.data(), nt * cn);
+        uchar* dm8 = needI2 ? (uchar*)stg.param(M8.data(), nt * cn) : nullptr;
+        if (!b8 || !part || !dk8 || (needI2 && !dm8)) return MI355_DECLINED("out of scratch memory for the byte planes");
+        uchar* pI = b8; uchar* pHi = needI2 ? b8 + plane8 * cn : nullptr; uchar* pLo = needI2 ? b8 + 2 * plane8 * cn : nullptr;
+        hipLaunchKernelGGL(k_tm_mask_planes_u8, dim3(divUp(p8, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, pI, pHi, pLo, p8, plane8);
+        auto cc8 = [&](const uchar* plane, const uchar* kern, int slot, int c) -> int {
+            return runMatch(entry, plane + (size_t)c * plane8, (size_t)p8, 0, 1, iw, ih, kern + (size_t)c * nt, (size_t)tw, tw, th, MI355CV_MAKETYPE(D8U, 1),
+                            reinterpret_cast<uchar*>(part + ((size_t)slot * 4 + c) * rplane), (size_t)rpitch * 4, 0, 2);
+        };
+        for (int c = 0; c < cn; c++) {
+            int rc = cc8(pI, dk8, 0, c);
+            if (rc == MI355CV_OK && needI2) rc = cc8(pHi, dm8, 2, c);                 // (slots 2 and 3 are free for these methods)
+            if (rc == MI355CV_OK && needI2) rc = cc8(pLo, dm8, 3, c);
+            if (rc != MI355CV_OK) return rc;
+            if (needI2) hipLaunchKernelGGL(k_tm_mask_join, dim3((unsigned)((rplane + 255) / 256)), dim3(256), 0, st, part + ((size_t)2 * 4 + c) * rplane,
+                                           part + ((size_t)3 * 4 + c) * rplane, part + ((size_t)1 * 4 + c) * rplane, rplane);
+        }
+        finish(part);
+        noteKernel("matchTemplateMask on byte planes: %d i8 correlation(s) per channel + k_tm_mask_finish", needI2 ? 3 : 1);
+        return stg.finish(entry);
+    }
+
+    // every other masked call: per-channel float planes of I (and I^2, k_tm_mask_planes), each cross-correlation a TM_CCORR of CV_32FC1 with all four bf16 products (or the
+    // direct kernel for sizes the bf16 path does not take), whose note stays the call's
+    int floatPlanes()
+    {
+        const int ipitch = (iw + 3) & ~3; const size_t iplane = (size_t)ipitch * ih;
+        float* f = (float*)stg.scratch(iplane * cn * 4);
+        float* f2 = needI2 ? (float*)stg.scratch(iplane * cn * 4) : nullptr;
+        float* part = (float*)stg.scratch(rplane * 16 * 4);
+        float* dk = (float*)stg.param(K.data(), nt * cn * 4);
+        float* dm = coeff ? (float*)stg.param(M.data(), nt * cn * 4) : nullptr;
+        float* dm2 = (needI2 || (method == 5 && !binary)) ? (float*)stg.param(M2.data(), nt * cn * 4) : nullptr;
+        if (!f || (needI2 && !f2) || !part || !dk || (coeff && !dm) || ((needI2 || (method == 5 && !binary)) && !dm2)) return MI355_DECLINED("out of scratch memory for the float planes");
+        hipLaunchKernelGGL(k_tm_mask_planes, dim3(divUp(ipitch, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, depth, f, f2, ipitch, iplane);
+        auto cc = [&](const float* plane, const float* kern, int kind, int c) -> int {
+            return runMatchInner(entry, reinterpret_cast<const uchar*>(plane + (size_t)c * iplane), (size_t)ipitch * 4, 0, 1, iw, ih, reinterpret_cast<const uchar*>(kern + (size_t)c * nt), (size_t)tw * 4, tw, th,
+                                 MI355CV_MAKETYPE(D32F, 1), reinterpret_cast<uchar*>(part + ((size_t)kind * 4 + c) * rplane), (size_t)rpitch * 4, 0, 2, nullptr, true);
+        };
+        for (int c = 0; c < cn; c++) {
+            int rc = cc(f, dk, 0, c);
+            if (rc == MI355CV_OK && needI2) rc = cc(f2, dm2, 1, c);
+            if (rc == MI355CV_OK && coeff) rc = cc(f, dm, 2, c);
+            if (rc == MI355CV_OK && method == 5 && !binary) rc = cc(f, dm2, 3, c);
+            if (rc != MI355CV_OK) return rc;
+        }
+        finish(part);
+        return stg.finish(entry);
+    }
+};
+
 int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int ih, const uchar* tpl, size_t tstep, int tw, int th, int type,
                  const uchar* mask, size_t mstep, int mtype, uchar* res, size_t rstep, int method)
 {
@@ -1482,66 +1498,16 @@ int runMatchMask(const char* entry, const uchar* img, size_t istep, int iw, int 
         }
         fin.nrm = (float)std::sqrt(nT);
     }
-    // the image: staged like any input, then per-channel float planes of I (and I^2)
+    // the image: staged like any input, then per-channel planes of I (and I^2)
     size_t dis = istep, drs = rstep;
     const uchar* di = stg.in(img, istep, (size_t)iw * cn * e, ih, &dis);
     uchar* dr = stg.out(res, rstep, (size_t)rw * 4, rh, &drs);
     MI355_DECLINE_IF(!di || !dr);
-    const bool needI2 = method != 2 && method != 4;
-    const int ipitch = (iw + 3) & ~3; const size_t iplane = (size_t)ipitch * ih;
-    const int rpitch = (rw + 3) & ~3; const size_t rplane = (size_t)rpitch * rh;
-    static const bool maskI8 = [] { const char* v = getenv("MI355CV_TM_MASK_I8"); return !v || atoi(v) != 0; }();      // 0: the float planes for every case (A/B runs)
-    if (maskI8 && depth == D8U && binary && !coeff) {
-        const int p8 = (iw + 15) & ~15; const size_t plane8 = (size_t)p8 * ih;
-        uchar* b8 = (uchar*)stg.scratch(plane8 * cn * (needI2 ? 3 : 1));
-        float* part = (float*)stg.scratch(rplane * 16 * 4);
-        std::vector<uchar> K8(nt * cn), M8(nt * cn);
-        for (size_t i = 0; i < nt * cn; i++) { K8[i] = (uchar)(T[i] * M[i]); M8[i] = (uchar)M[i]; }
-        uchar* dk8 = (uchar*)stg.param(K8.data(), nt * cn);
-        uchar* dm8 = needI2 ? (uchar*)stg.param(M8.data(), nt * cn) : nullptr;
-        if (!b8 || !part || !dk8 || (needI2 && !dm8)) return MI355_DECLINED("out of scratch memory for the byte planes");
-        uchar* pI = b8; uchar* pHi = needI2 ? b8 + plane8 * cn : nullptr; uchar* pLo = needI2 ? b8 + 2 * plane8 * cn : nullptr;
-        hipLaunchKernelGGL(k_tm_mask_planes_u8, dim3(divUp(p8, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, pI, pHi, pLo, p8, plane8);
-        fin.pitch = rpitch; fin.plane = rplane;
-        auto cc8 = [&](const uchar* plane, const uchar* kern, int slot, int c) -> int {
-            return runMatch(entry, plane + (size_t)c * plane8, (size_t)p8, 0, 1, iw, ih, kern + (size_t)c * nt, (size_t)tw, tw, th, MI355CV_MAKETYPE(D8U, 1),
-                            reinterpret_cast<uchar*>(part + ((size_t)slot * 4 + c) * rplane), (size_t)rpitch * 4, 0, 2);
-        };
-        for (int c = 0; c < cn; c++) {
-            int rc = cc8(pI, dk8, 0, c);
-            if (rc == MI355CV_OK && needI2) rc = cc8(pHi, dm8, 2, c);                 // (slots 2 and 3 are free for these methods)
-            if (rc == MI355CV_OK && needI2) rc = cc8(pLo, dm8, 3, c);
-            if (rc != MI355CV_OK) return rc;
-            if (needI2) hipLaunchKernelGGL(k_tm_mask_join, dim3((unsigned)((rplane + 255) / 256)), dim3(256), 0, st, part + ((size_t)2 * 4 + c) * rplane,
-                                           part + ((size_t)3 * 4 + c) * rplane, part + ((size_t)1 * 4 + c) * rplane, rplane);
-        }
-        hipLaunchKernelGGL(k_tm_mask_finish, dim3(divUp(rw, 64), divUp(rh, 4)), dim3(256), 0, st, part, reinterpret_cast<float*>(dr), drs, fin);
-        noteKernel("matchTemplateMask on byte planes: %d i8 correlation(s) per channel + k_tm_mask_finish", needI2 ? 3 : 1);
-        return stg.finish(entry);
-    }
-    float* f = (float*)stg.scratch(iplane * cn * 4);
-    float* f2 = needI2 ? (float*)stg.scratch(iplane * cn * 4) : nullptr;
-    float* part = (float*)stg.scratch(rplane * 16 * 4);
-    float* dk = (float*)stg.param(K.data(), nt * cn * 4);
-    float* dm = coeff ? (float*)stg.param(M.data(), nt * cn * 4) : nullptr;
-    float* dm2 = (needI2 || (method == 5 && !binary)) ? (float*)stg.param(M2.data(), nt * cn * 4) : nullptr;
-    if (!f || (needI2 && !f2) || !part || !dk || (coeff && !dm) || ((needI2 || (method == 5 && !binary)) && !dm2)) return MI355_DECLINED("out of scratch memory for the float planes");
-    hipLaunchKernelGGL(k_tm_mask_planes, dim3(divUp(ipitch, 64), divUp(ih, 4)), dim3(256), 0, st, di, dis, iw, ih, cn, depth, f, f2, ipitch, iplane);
-    fin.pitch = rpitch; fin.plane = rplane;
-    struct FourProducts { FourProducts() { t_fourProducts = true; } ~FourProducts() { t_fourProducts = false; } } guard;
-    auto cc = [&](const float* plane, const float* kern, int kind, int c) -> int {
-        return runMatch(entry, reinterpret_cast<const uchar*>(plane + (size_t)c * iplane), (size_t)ipitch * 4, 0, 1, iw, ih, reinterpret_cast<const uchar*>(kern + (size_t)c * nt), (size_t)tw * 4, tw, th,
-                        MI355CV_MAKETYPE(D32F, 1), reinterpret_cast<uchar*>(part + ((size_t)kind * 4 + c) * rplane), (size_t)rpitch * 4, 0, 2);
-    };
-    for (int c = 0; c < cn; c++) {
-        int rc = cc(f, dk, 0, c);
-        if (rc == MI355CV_OK && needI2) rc = cc(f2, dm2, 1, c);
-        if (rc == MI355CV_OK && coeff) rc = cc(f, dm, 2, c);
-        if (rc == MI355CV_OK && method == 5 && !binary) rc = cc(f, dm2, 3, c);
-        if (rc != MI355CV_OK) return rc;
-    }
-    hipLaunchKernelGGL(k_tm_mask_finish, dim3(divUp(rw, 64), divUp(rh, 4)), dim3(256), 0, st, part, reinterpret_cast<float*>(dr), drs, fin);
-    return stg.finish(entry);
+    const int rpitch = (rw + 3) & ~3;
+    MaskCall c = {entry, stg, st, di, dis, dr, drs, iw, ih, tw, th, depth, cn, method, rw, rh, binary, coeff, /* needI2 */ method != 2 && method != 4,
+                  nt, T, M, M2, K, rpitch, (size_t)rpitch * rh, fin};
+    const int rc = c.bytePlanes();
+    return rc != NEXT_PATH ? rc : c.floatPlanes();
 }
 
 } // namespace
@@ -1589,105 +1555,6 @@ MI355CV_API int mi355cv_matchTemplateBatch(const uchar* img_data, size_t img_ste
                                               templ_height, type, result_data + f0 * result_frame_stride, result_step, result_frame_stride, method); });
     return runMatch("matchTemplateBatch", img_data, img_step, nframes == 1 ? 0 : img_frame_stride, nframes, img_width, img_height, templ_data, templ_step,
                     templ_width, templ_height, type, result_data, result_step, nframes == 1 ? 0 : result_frame_stride, method);
-}
-
-// replaces hal_ni_integral (hal_replacement.hpp:977; caller cv::integral sumpixels.dispatch.cpp:415): every depth triple of the reference's table (:383-406), with or
-// without the squared and the tilted sum.  CV_8U sources with CV_32S / CV_64F sums (squared sum in CV_64F, no tilted sum) take the tiled / scanned kernels below -- exact
-// integers in any order; everything whose value depends on the order of the additions -- float sources, CV_32F sums, CV_32F / CV_32S squared sums, tilted sums -- takes
-// integral_seq.hip, which adds in the reference's order (bit for bit).  One case is left to the CPU: CV_8U -> CV_32F sums without a squared or tilted sum beyond 2^24
-// (the reference's vector body recovers the row prefix in its scalar tail by a subtraction, sumpixels.simd.hpp:528-533, so the bits depend on the CPU's vector width).
-MI355CV_API int mi355cv_integral(int depth, int sdepth, int sqdepth, const uchar* src_data, size_t src_step, uchar* sum_data, size_t sum_step,
-                                 uchar* sqsum_data, size_t sqsum_step, uchar* tilted_data, size_t tilted_step, int width, int height, int cn)
-{
-    mi355::EntryGuard entry_(__func__);
-    MI355_DECLINE_IF(disabled() || !sum_data || !src_data);
-    if (!integralOrderedTriple(depth, sdepth, sqdepth) || cn < 1)
-        return setError(MI355CV_NOT_IMPLEMENTED, "integral: depths %d -> sum %d, sqsum %d%s, %d channels: not a row of the reference's table", depth, sdepth, sqdepth, sqsum_data ? "" : " (no sqsum)", cn);
-    const bool tiledKind = !tilted_data && cn <= 4 && depth == D8U && (sdepth == D32S || sdepth == D64F) && (!sqsum_data || sqdepth == D64F) &&
-                           !(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);          // (sums that wrap: the ordered kernels wrap like the reference)
-    if (!tiledKind) {
-        if (depth == D8U && sdepth == D32F && !sqsum_data && !tilted_data && (double)width * height * 255.0 >= 16777216.0)
-            return setError(MI355CV_NOT_IMPLEMENTED, "integral: CV_8U -> CV_32F sums past 2^24 without a squared / tilted sum depend on the CPU's vector width");
-        const size_t e1 = sdepth == D64F ? 8 : 4, e2 = sqdepth == D64F ? 8 : 4, es = depth == D8U ? 1 : depth == D32F ? 4 : depth == D64F ? 8 : 2;
-        if (width <= 0 || height <= 0 || (sum_step % e1) || (sqsum_data && (sqsum_step % e2)) || (tilted_data && (tilted_step % e1)) || (src_step % es))
-            return MI355_DECLINED("width <= 0 || height <= 0 || a step that is not a multiple of its element size");
-        if ((double)(width + 1) * cn * (height + 1) >= 2147483647.0) return MI355_DECLINED("more than 2^31 elements");
-        Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-        MI355_DECLINE_IF(!ensureDevice());
-        // (HOST_HEAVY: the reference's scalar loops take 10-60 ms per 4K image on one core -- worth two PCIe crossings, unlike the 8-bit vector paths of the tiled kind)
-        MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels(HOST_HEAVY)));
-        size_t dss, d1, d2 = 0, d3 = 0;
-        const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * es, height, &dss);
-        uchar* s1 = stg.out(sum_data, sum_step, (size_t)(width + 1) * cn * e1, height + 1, &d1);
-        uchar* s2 = sqsum_data ? stg.out(sqsum_data, sqsum_step, (size_t)(width + 1) * cn * e2, height + 1, &d2) : nullptr;
-        uchar* s3 = tilted_data ? stg.out(tilted_data, tilted_step, (size_t)(width + 1) * cn * e1, height + 1, &d3) : nullptr;
-        void* aux = tilted_data ? stg.scratch(integralOrderedAuxBytes(width, height, cn, sdepth, true)) : nullptr;
-        if (!ds || !s1 || (sqsum_data && !s2) || (tilted_data && (!s3 || !aux))) return MI355_DECLINED("staging / scratch for the ordered integral");
-        if (!integralOrdered(depth, sdepth, sqdepth, ds, dss, s1, d1, s2, d2, s3, d3, width, height, cn, aux, stream()))
-            return MI355_DECLINED("!integralOrdered(...)");
-        noteKernel("k_iseq_rows + k_iseq_cols%s (ordered sums, depths %d -> %d / %d)", tilted_data ? " + k_iseq_tbuf / tcol0 / tdiag" : "", depth, sdepth, sqdepth);
-        return stg.finish("integral");
-    }
-    const size_t se = sdepth == D32S ? 4 : 8;
-    MI355_DECLINE_IF(width <= 0 || height <= 0 || (sum_step % se) || (sqsum_data && (sqsum_step % 8)));
-    Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    MI355_DECLINE_IF(!ensureDevice());
-    MI355_DECLINE_IF(hostImageTooSmall(src_data, (size_t)width * height, minPixels()));
-    size_t dss, d1, d2 = 0;
-    const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn * (depth == D8U ? 1 : 4), height, &dss);
-    uchar* s1 = stg.out(sum_data, sum_step, (size_t)(width + 1) * cn * se, height + 1, &d1);
-    uchar* s2 = sqsum_data ? stg.out(sqsum_data, sqsum_step, (size_t)(width + 1) * cn * 8, height + 1, &d2) : nullptr;
-    MI355_DECLINE_IF(!ds || !s1 || (sqsum_data && !s2));
-    const int Wc = (width + 1) * cn, nseg = divUp(height, IS_SEG);
-    hipStream_t st = stream();
-    static const bool tiledOff = getenv("MI355CV_INTEGRAL_TILED") && atoi(getenv("MI355CV_INTEGRAL_TILED")) == 0;
-    if (depth == D8U && cn == 1 && !tiledOff) {
-        // two passes over the pixels + carries (integral.hip) instead of a row pass and two column passes over the sum image
-        void* taux = stg.scratch(integralTiledAuxBytes(width, height, 1, s2 != nullptr));
-        if (taux && integralTiledU8(ds, dss, 0, width, height, 1, s1, d1 / se, 0, sdepth == D64F, (double*)s2, d2 / 8, 0, taux, st))
-            return stg.finish("integral");
-    }
-    void* aux = stg.scratch((size_t)nseg * Wc * 8);
-    MI355_DECLINE_IF(!aux);
-    const size_t ldsFast = (((size_t)(width + 1) * se + 15) & ~(size_t)15) + (s2 ? (size_t)(width + 1) * 8 : 0);
-    const bool fastRows = depth == D8U && cn == 1 && ldsFast <= 60 * 1024;
-    if (sdepth == D32S) {
-        if (fastRows) hipLaunchKernelGGL(k_integral_rows_u8c1<int>, dim3(height, 1, 1), dim3(256), ldsFast, st, ds, dss, 0, width, (int*)s1, d1 / 4, 0, (double*)s2, d2 / 8, 0);
-        else hipLaunchKernelGGL(k_integral_rows<int>, dim3(height, cn, 1), dim3(256), 0, st, ds, dss, 0, width, height, cn, depth, (int*)s1, d1 / 4, 0, (double*)s2, d2 / 8, 0);
-        integralColumns<int>((int*)s1, d1 / 4, 0, Wc, height, 1, (int*)aux, st);
-    } else {
-        if (fastRows) hipLaunchKernelGGL(k_integral_rows_u8c1<double>, dim3(height, 1, 1), dim3(256), ldsFast, st, ds, dss, 0, width, (double*)s1, d1 / 8, 0, (double*)s2, d2 / 8, 0);
-        else hipLaunchKernelGGL(k_integral_rows<double>, dim3(height, cn, 1), dim3(256), 0, st, ds, dss, 0, width, height, cn, depth, (double*)s1, d1 / 8, 0, (double*)s2, d2 / 8, 0);
-        integralColumns<double>((double*)s1, d1 / 8, 0, Wc, height, 1, (double*)aux, st);
-    }
-    if (s2) integralColumns<double>((double*)s2, d2 / 8, 0, Wc, height, 1, (double*)aux, st);
-    return stg.finish("integral");
-}
-
-// frame-batched form for device-resident CV_8UC1 frames: every frame's (H+1) x (W+1) CV_32S (or CV_64F) sum [+ CV_64F squared sum] from the
-// same three launches that serve one frame (integral.hip: the tile index carries the frame) -- the per-frame launches of a single 4K image are
-// latency-bound (2160 waves), a batch fills the machine.  Strides in bytes.
-MI355CV_API int mi355cv_integralBatch(const uchar* src_data, size_t src_step, size_t src_frame_stride, uchar* sum_data, size_t sum_step, size_t sum_frame_stride,
-                                      uchar* sqsum_data, size_t sqsum_step, size_t sqsum_frame_stride, int nframes, int width, int height, int sdepth)
-{
-    mi355::EntryGuard entry_(__func__);
-    MI355_DECLINE_IF(disabled() || !src_data || !sum_data || nframes < 1 || width <= 0 || height <= 0 || (sdepth != D32S && sdepth != D64F));
-    const size_t se = sdepth == D32S ? 4 : 8;
-    MI355_DECLINE_IF((sum_step % se) || (sum_frame_stride % se) || (sqsum_data && ((sqsum_step % 8) || (sqsum_frame_stride % 8))));
-    MI355_DECLINE_IF(sdepth == D32S && (double)width * height * 255.0 > 2147483647.0);
-    if (nframes > MAX_GRID_FRAMES)                                                              // the kernels take the frame from blockIdx.z; the carries are scratch per call
-        return sliceFrames(nframes, [&](size_t f0, int nf) {
-            return mi355cv_integralBatch(src_data + f0 * src_frame_stride, src_step, src_frame_stride, sum_data + f0 * sum_frame_stride, sum_step, sum_frame_stride,
-                                         sqsum_data ? sqsum_data + f0 * sqsum_frame_stride : nullptr, sqsum_step, sqsum_frame_stride, nf, width, height, sdepth); });
-    Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
-    if (!ensureDevice() || !isDevicePtr(src_data) || !isDevicePtr(sum_data) || (sqsum_data && !isDevicePtr(sqsum_data)))
-        return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: device-resident frames only");
-    if (nframes == 1) { src_frame_stride = 0; sum_frame_stride = 0; sqsum_frame_stride = 0; }
-    void* taux = stg.scratch(integralTiledAuxBytes(width, height, nframes, sqsum_data != nullptr));
-    if (!taux || !integralTiledU8(src_data, src_step, src_frame_stride, width, height, nframes, sum_data, sum_step / se, sum_frame_stride / se, sdepth == D64F,
-                                  (double*)sqsum_data, sqsum_step / 8, sqsum_frame_stride / 8, taux, stream()))
-        return setError(MI355CV_NOT_IMPLEMENTED, "integralBatch: frame geometry outside the tiled path");
-    return stg.finish("integralBatch");
 }
 
 } // extern "C"

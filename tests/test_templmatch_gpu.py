@@ -34,11 +34,16 @@ def test_modes_direct_path(cv, orc, dtype, cn, method):
         got = cv.matchTemplate(dev(img), dev(tpl), method).cpu().numpy()
         # CV_32FC1 with >= 4096 results runs as three bf16 products on the matrix cores (test_bf16_split_path_32fc1): the contract's 1e-4 there, 1e-5 on the direct kernel
         from opencv_amd import _lib
-        tol = 1e-4 if "k_ccorr_bf16" in _lib.lib.mi355cv_lastKernel().decode() else 1e-5
+        note = _lib.lib.mi355cv_lastKernel().decode()
+        # every path writes its note, so this is this call's: k_ccorr_direct below 4096 results, above them k_ccorr_bf16 (CV_32FC1) or the i8 kernels (CV_8U, by planes if cn > 1)
+        assert note.startswith("k_ccorr_direct" if (iw - tw + 1) * (ih - th + 1) < 4096 or (dtype == np.float32 and cn > 1) else ("k_ccorr_", "matchTemplate")), note
+        tol = 1e-4 if "k_ccorr_bf16" in note else 1e-5
         assert orc.rel_err(got, want) <= tol, (iw, ih, tw, th)
     img, tpl = rnd((61, 97), dtype, 1), rnd((9, 17), dtype, 2)
     got = cv.matchTemplate(img, tpl, method)                                                                    # host arrays
-    tol = 1e-4 if "k_ccorr_bf16" in _lib.lib.mi355cv_lastKernel().decode() else 1e-5
+    note = _lib.lib.mi355cv_lastKernel().decode()
+    assert note.startswith(("k_ccorr_", "matchTemplate")), note
+    tol = 1e-4 if "k_ccorr_bf16" in note else 1e-5
     assert orc.rel_err(got, orc.orc_matchTemplate(img, tpl, method)) <= tol
 
 
