@@ -915,6 +915,41 @@ MI355CV_API int mi355cv_stereoSGBMSetKernel(int mode);
 /* Lowers the scratch bound to `bytes` (0: back to the limit), so that the chunking of batches can be exercised at small shapes.  Results do not depend on it. */
 MI355CV_API int mi355cv_stereoSGBMSetScratchLimit(size_t bytes);
 
+/* --------------------------------------------------- f3: photo fastNlMeansDenoising (csrc/nlmeans.hip) */
+/* cv::fastNlMeansDenoising (modules/photo, no HAL hook; the definition served is written down in DESIGN 6.20 and tests/nlmeans_restate.py) on a CV_8U image of
+ * cn = 1 .. 4 channels: h[0] is the filter strength (hn = 1), templateWindowSize and searchWindowSize count as the next odd value when even, normType is
+ * cv::NORM_L2 = 4.  The weights are a table of integers built once per call on the host; everything after it is integer arithmetic: the result is determined bit for bit.
+ * Images may live in host memory (staged through HBM, host-cost class HOST_HEAVY) or in this thread's device memory, at any pitch and byte address; device pointers run
+ * on the current stream.  Images narrower or shorter than the border th + sh are served.
+ * Declined (MI355CV_NOT_IMPLEMENTED, dst left untouched, the reason in mi355cv_lastError): NORM_L1 (2) and CV_16U; other depths; cn outside 1 .. 4; hn != 1 (a per-channel
+ * h vector); a window below 1 or, as used, above mi355cv_limit("nlm_max_window") = 181 (T * T <= 2^15; the same bound holds S, far inside the S whose S * S * 255 overflows);
+ * S^2 T^2 cn, the squared differences per pixel of the rule as written, above mi355cv_limit("nlm_max_pixel_work") = 2^24; width or height above
+ * mi355cv_limit("nlm_max_dim") = 16384; a pitch below the row; src and dst that overlap (in host memory as well). */
+MI355CV_API int mi355cv_fastNlMeansDenoising(const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* dst, size_t dst_step, int width, int height, int depth, int cn,
+        const float* h, int hn, int templateWindowSize, int searchWindowSize, int normType);
+/* nframes frames at src + f * src_frame_stride into dst + f * dst_frame_stride; exactly the results of nframes single calls.  Device-resident frames run with the frame in
+ * the grid's z, in launches of at most 65535 frames (mi355cv_fastNlMeansSetChunk lowers that); host-resident batches cross PCIe in chunks through the shared pipeline.
+ * Declined as well: nframes < 1, a frame stride below the frame. */
+MI355CV_API int mi355cv_fastNlMeansDenoisingBatch(const mi355cv_uchar* src, size_t src_step, size_t src_frame_stride, mi355cv_uchar* dst, size_t dst_step,
+        size_t dst_frame_stride, int nframes, int width, int height, int depth, int cn, const float* h, int hn, int templateWindowSize, int searchWindowSize, int normType);
+/* cv::fastNlMeansDenoisingColored on CV_8UC3: mi355cv_cvtBGRtoLab (COLOR_LBGR2Lab), the rule on L with h and on a, b together with hColor (cn = 2) straight out of the Lab
+ * image into a second one, mi355cv_cvtLabtoBGR (COLOR_Lab2LBGR).  Declined as above, and: cn = 4 (CV_8UC4) and every cn but 3. */
+MI355CV_API int mi355cv_fastNlMeansDenoisingColored(const mi355cv_uchar* src, size_t src_step, mi355cv_uchar* dst, size_t dst_step, int width, int height, int depth, int cn,
+        float h, float hColor, int templateWindowSize, int searchWindowSize);
+MI355CV_API int mi355cv_fastNlMeansDenoisingColoredBatch(const mi355cv_uchar* src, size_t src_step, size_t src_frame_stride, mi355cv_uchar* dst, size_t dst_step,
+        size_t dst_frame_stride, int nframes, int width, int height, int depth, int cn, float h, float hColor, int templateWindowSize, int searchWindowSize);
+/* Host only, touches no device: the weight table of the rule.  info[0 .. 3] = its length, the shift of a distance, the weight of distance 0 (mult) and the length of
+ * the non-zero prefix (the table is non-increasing); table, which may be NULL, receives min(length, capacity) entries. */
+MI355CV_API int mi355cv_fastNlMeansWeights(float h, int cn, int templateWindowSize, int searchWindowSize, int* table, int capacity, int* info);
+/* A/B switch (tools/nlmeans_bench.py): -1 the built-in rule, 0 always the plain kernel (a lane per pixel, the rule as written), 1 the tile kernel wherever it applies
+ * (T <= mi355cv_limit("nlm_tile_max_template") = 9, a prefix of at most mi355cv_limit("nlm_lds_table") = 49152 entries, table and tile within
+ * mi355cv_limit("nlm_tile_lds_kib") = 160 KiB of LDS; mi355cv_limit("nlm_tile_cols") = 128 counts the LANES across a workgroup, whose output columns are 2 (64 - (T - 1)); the plain kernel
+ * serves the rest).  Results do not depend on it. */
+MI355CV_API int mi355cv_fastNlMeansSetKernel(int mode);
+/* Lowers the frames per launch of a device-resident batch (0: back to 65535; the Colored entries take 16 at most), so that the cutting of batches can be exercised at
+ * small shapes.  Results do not depend on it. */
+MI355CV_API int mi355cv_fastNlMeansSetChunk(int frames);
+
 #ifdef __cplusplus
 }
 #endif

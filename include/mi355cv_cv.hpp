@@ -972,6 +972,43 @@ inline void filterSpeckles(cv::InputOutputArray _img, double newVal, int maxSpec
 }
 #endif
 
+#ifdef OPENCV_PHOTO_HPP          // cv::fastNlMeansDenoising lives in opencv2/photo.hpp; include it before this header to get the wrappers
+// cv::fastNlMeansDenoising / cv::fastNlMeansDenoisingColored (photo.hpp; denoising.cpp, fast_nlmeans_denoising_invoker.hpp).  The reference has no HAL hook for them.
+// A 2-D CV_8U cv::Mat of 1 .. 4 channels (Colored: CV_8UC3) goes through mi355cv_fastNlMeansDenoising / ...Colored (csrc/nlmeans.hip), source and destination where
+// the Mats live.  The image is the project's restatement of the rule (tests/nlmeans_restate.py): a table of integer weights built on the host, then
+// integer arithmetic, determined bit for bit.  Everything the entries decline (other depths, NORM_L1, a per-channel h, windows or sizes over the limits, dst
+// overlapping src, UMat, no device) goes to the stock function, which finds the destination untouched.  Not compiled here: the reference's headers are absent.
+inline void fastNlMeansDenoising(cv::InputArray _src, cv::OutputArray _dst, float h = 3, int templateWindowSize = 7, int searchWindowSize = 21)
+{
+    if (_src.kind() == cv::_InputArray::MAT && _dst.kind() == cv::_InputArray::MAT) {
+        cv::Mat src = _src.getMat();
+        if (src.dims <= 2 && !src.empty() && src.depth() == CV_8U && src.channels() <= 4) {
+            _dst.create(src.size(), src.type());
+            cv::Mat dst = _dst.getMat();
+            if (mi355cv_fastNlMeansDenoising(src.data, src.step, dst.data, dst.step, src.cols, src.rows, MI355CV_8U, src.channels(), &h, 1, templateWindowSize, searchWindowSize,
+                                             cv::NORM_L2) == MI355CV_OK)
+                return;
+        }
+    }
+    cv::fastNlMeansDenoising(_src, _dst, h, templateWindowSize, searchWindowSize);
+}
+
+inline void fastNlMeansDenoisingColored(cv::InputArray _src, cv::OutputArray _dst, float h = 3, float hColor = 3, int templateWindowSize = 7, int searchWindowSize = 21)
+{
+    if (_src.kind() == cv::_InputArray::MAT && _dst.kind() == cv::_InputArray::MAT) {
+        cv::Mat src = _src.getMat();
+        if (src.dims <= 2 && !src.empty() && src.type() == CV_8UC3) {
+            _dst.create(src.size(), src.type());
+            cv::Mat dst = _dst.getMat();
+            if (mi355cv_fastNlMeansDenoisingColored(src.data, src.step, dst.data, dst.step, src.cols, src.rows, MI355CV_8U, 3, h, hColor, templateWindowSize, searchWindowSize) ==
+                MI355CV_OK)
+                return;
+        }
+    }
+    cv::fastNlMeansDenoisingColored(_src, _dst, h, hColor, templateWindowSize, searchWindowSize);
+}
+#endif
+
 // Batches across the GPUs of one node from C++: forEachShard({0,1,...,7}, nframes, [&](int slot, int device, int first, int count) { ... return 0; })
 // runs the callable once per device on its own host thread bound to that device (mi355cv_runSharded, csrc/shard.hip), frames [first, first + count) being that
 // device's share; inside, call cv:: functions of a HAL-enabled build or mi355cv:: / mi355cv_*Batch entry points on Mats whose storage lives on `device`

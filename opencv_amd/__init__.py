@@ -17,5 +17,6 @@ from .imgproc import *  # noqa: F401,F403
 from .video import *  # noqa: F401,F403
 from .features2d import *  # noqa: F401,F403
 from .calib3d import *  # noqa: F401,F403
+from .photo import *  # noqa: F401,F403
 
 __version__ = "0.1"

@@ -86,6 +86,13 @@ def _load():
         "mi355cv_stereoSGBMBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p]),
         "mi355cv_stereoSGBMSetKernel": (c_int, [c_int]),
         "mi355cv_stereoSGBMSetScratchLimit": (c_int, [c_sz]),
+        "mi355cv_fastNlMeansDenoising": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_int]),
+        "mi355cv_fastNlMeansDenoisingBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_int]),
+        "mi355cv_fastNlMeansDenoisingColored": (c_int, [c_u8p, c_sz, c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_int]),
+        "mi355cv_fastNlMeansDenoisingColoredBatch": (c_int, [c_u8p, c_sz, c_sz, c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_int, c_int, ctypes.c_float, ctypes.c_float, c_int, c_int]),
+        "mi355cv_fastNlMeansWeights": (c_int, [ctypes.c_float, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p]),
+        "mi355cv_fastNlMeansSetKernel": (c_int, [c_int]),
+        "mi355cv_fastNlMeansSetChunk": (c_int, [c_int]),
         "mi355cv_remap": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int,
                                   c_int, c_int, ctypes.c_void_p]),
         "mi355cv_convertMaps": (c_int, [ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz,

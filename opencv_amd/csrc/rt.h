@@ -73,6 +73,14 @@ constexpr int SGBM_TILE_COLS = 64;             // ... geometry, reported for the
 constexpr int SGBM_STRIP_ROWS = 32;            // ... rows a workgroup of the cost kernel walks down
 constexpr int SGBM_CHUNK = 16;                 // ... disparities per lane of the cost kernel
 constexpr int SGBM_PATH_BLOCK = 16;            // ... steps of a path per block of loads in the fast path kernel up to 64 disparities (8 up to 128, 4 above)
+constexpr int NLM_MAX_DIM = 16384;             // mi355cv_fastNlMeans*: width and height (the neighbours' bound; nlmeans_math.h)
+constexpr int NLM_MAX_WINDOW = 181;            // ... templateWindowSize and searchWindowSize as used (odd): 181^2 <= 2^15, the reference's own bound on the patch; S * S * 255 stays far inside an int
+constexpr int NLM_MAX_PIXEL_WORK = 1 << 24;      // ... S^2 T^2 cn, the squared differences per pixel of the rule as written: a lane of the plain kernel does them one after the other (7 / 21 on four channels: 86436)
+constexpr int NLM_TILE_COLS = 128;             // ... geometry, reported for the tests' shapes: LANES across a workgroup of the tile kernel (two waves of 64), not output columns: a wave gives 64 - (T - 1) pixels of a row, a workgroup twice that
+constexpr int NLM_TILE_ROWS = 32;              // ... and its rows, two waves of 16 rows each
+constexpr int NLM_TILE_MAX_TEMPLATE = 9;       // ... the largest T of the tile kernel: the rows of a patch are a lane's registers with compile-time indices
+constexpr int NLM_LDS_TABLE = 49152;           // ... entries of the weight table's non-zero prefix the tile kernel keeps in LDS: 96 KiB as 16-bit words (S >= 13), which holds the 39546 of h = 50 on three channels beside the tile
+constexpr int NLM_TILE_LDS_KIB = 160;          // ... table and tile together: the LDS of a CU
 }
 
 struct ThreadCtx;

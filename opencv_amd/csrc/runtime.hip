@@ -583,7 +583,9 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"stereobm_strip_rows", STEREOBM_STRIP_ROWS}, {"stereobm_generic_tile_cols", STEREOBM_GENERIC_TILE_COLS},
         {"speckle_max_dim", SPECKLE_MAX_DIM}, {"speckle_tile_cols", SPECKLE_TILE_COLS}, {"speckle_tile_rows", SPECKLE_TILE_ROWS},
         {"sgbm_max_dim", SGBM_MAX_DIM}, {"sgbm_max_disparities", SGBM_MAX_DISPARITIES}, {"sgbm_max_cost", SGBM_MAX_COST}, {"sgbm_max_scratch_mib", (int)(SGBM_MAX_SCRATCH_BYTES >> 20)},
-        {"sgbm_tile_cols", SGBM_TILE_COLS}, {"sgbm_strip_rows", SGBM_STRIP_ROWS}, {"sgbm_chunk", SGBM_CHUNK}, {"sgbm_path_block", SGBM_PATH_BLOCK}};
+        {"sgbm_tile_cols", SGBM_TILE_COLS}, {"sgbm_strip_rows", SGBM_STRIP_ROWS}, {"sgbm_chunk", SGBM_CHUNK}, {"sgbm_path_block", SGBM_PATH_BLOCK},
+        {"nlm_max_dim", NLM_MAX_DIM}, {"nlm_max_window", NLM_MAX_WINDOW}, {"nlm_tile_cols", NLM_TILE_COLS}, {"nlm_tile_rows", NLM_TILE_ROWS},
+        {"nlm_tile_max_template", NLM_TILE_MAX_TEMPLATE}, {"nlm_lds_table", NLM_LDS_TABLE}, {"nlm_tile_lds_kib", NLM_TILE_LDS_KIB}, {"nlm_max_pixel_work", NLM_MAX_PIXEL_WORK}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
