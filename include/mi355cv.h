@@ -950,6 +950,51 @@ MI355CV_API int mi355cv_fastNlMeansSetKernel(int mode);
  * small shapes.  Results do not depend on it. */
 MI355CV_API int mi355cv_fastNlMeansSetChunk(int frames);
 
+/* --------------------------------------------------- f3: calib3d rectification (csrc/undistort.hip) */
+/* cv::initUndistortRectifyMap, cv::undistort, the rectifying warp and cv::reprojectImageTo3D (modules/calib3d, no HAL hook).  The definition served is written down in
+ * DESIGN 6.21 and tests/undistort_restate.py: the closed form of the map per destination pixel in separately rounded IEEE doubles.  K: the camera matrix, 9 doubles row
+ * by row; dist: ndist = 0, 4, 5, 8, 12 or 14 coefficients k1 k2 p1 p2 k3 k4 k5 k6 s1 s2 s3 s4 tauX tauY (NULL with ndist = 0); R: any 3 x 3 (a rotation or a
+ * homography), NULL = identity; newK: 3 x 3 (the left 3 x 3 of a 3 x 4 P), NULL = K.  Out of scope: stereoRectify, getOptimalNewCameraMatrix, undistortPoints, the
+ * fisheye model.
+ * m1type: CV_32FC1 (map1 = u, map2 = v as floats), CV_32FC2 (map1 alone) or CV_16SC2 (map1 = the integer coordinates, map2 = CV_16UC1 fractions, the form of
+ * cv::convertMaps; a non-finite coordinate gives entry (0, 0), fraction 0).  The maps may live in host or device memory, at any pitch that keeps their elements aligned.
+ * Declined (MI355CV_NOT_IMPLEMENTED, nothing written, the reason in mi355cv_lastError), each before a device is touched: ndist outside the list; a non-zero tauX / tauY;
+ * newK * R with a determinant that is 0 or not finite; width or height below 1 or above mi355cv_limit("undist_max_dim") = 16384; a pitch below the row; maps that
+ * overlap; another m1type. */
+MI355CV_API int mi355cv_initUndistortRectifyMap(const double* K, const double* dist, int ndist, const double* R, const double* newK, int width, int height, int m1type,
+        void* map1, size_t map1_step, void* map2, size_t map2_step);
+/* The rectifying warp: BY DEFINITION mi355cv_remap of the source with the CV_16SC2 + CV_16UC1 maps of the rule above, for every depth, channel count, interpolation and
+ * border mode mi355cv_remap serves for fixed-point maps -- without the maps ever existing on CV_8U with 1, 3 or 4 channels under INTER_LINEAR (k_undist8_tile evaluates
+ * the rule once per destination tile).  cv::undistort is this with R = NULL, the destination of the source's size, INTER_LINEAR, BORDER_CONSTANT, border value 0.
+ * Declined as above, and: a source beyond mi355cv_limit("undist_max_src_dim") = 32767; src and dst that overlap (in host memory as well). */
+MI355CV_API int mi355cv_undistortRectify(int src_type, const mi355cv_uchar* src, size_t src_step, int src_width, int src_height, mi355cv_uchar* dst, size_t dst_step,
+        int dst_width, int dst_height, const double* K, const double* dist, int ndist, const double* R, const double* newK, int interpolation, int border_type,
+        const double* border_value);
+/* nframes frames of one camera; exactly the results of nframes single calls.  The tile kernel evaluates the rule once per tile and walks
+ * mi355cv_limit("undist_frames_per_group") frames with it; host-resident batches cross PCIe in chunks through the shared pipeline.  Declined as well: nframes < 1, a frame
+ * stride below the frame. */
+MI355CV_API int mi355cv_undistortRectifyBatch(int src_type, const mi355cv_uchar* src, size_t src_step, size_t src_frame_stride, int src_width, int src_height,
+        mi355cv_uchar* dst, size_t dst_step, size_t dst_frame_stride, int dst_width, int dst_height, int nframes, const double* K, const double* dist, int ndist,
+        const double* R, const double* newK, int interpolation, int border_type, const double* border_value);
+/* cv::reprojectImageTo3D: a one-channel disparity of CV_8U, CV_16S, CV_32S or CV_32F -> CV_32FC3 points, Q row by row (16 doubles).  Per pixel in double
+ * h_r = ((Q[r][0] x + Q[r][1] y) + Q[r][2] d) + Q[r][3], the point is (float)(h_r * (1 / h_3)).  handleMissingValues: a pixel with |d - dmin| <= FLT_EPSILON gets
+ * z = 10000, dmin the minimum of ITS frame (mi355cv_minMaxLocBatch, the result stays in HBM: no host synchronisation; a NaN is no candidate).  ddepth: -1 or CV_32F.
+ * Declined: other disparity types; ddepth CV_16S / CV_32S; width or height above mi355cv_limit("reproject_max_dim") = 16384; pitches below the row or off the element
+ * size; overlap; nframes < 1; a frame stride below the frame. */
+MI355CV_API int mi355cv_reprojectImageTo3D(const mi355cv_uchar* disp, size_t disp_step, int disp_type, mi355cv_uchar* dst, size_t dst_step, int width, int height,
+        const double* Q, int handleMissingValues, int ddepth);
+MI355CV_API int mi355cv_reprojectImageTo3DBatch(const mi355cv_uchar* disp, size_t disp_step, size_t disp_frame_stride, int disp_type, mi355cv_uchar* dst, size_t dst_step,
+        size_t dst_frame_stride, int width, int height, int nframes, const double* Q, int handleMissingValues, int ddepth);
+/* A/B switch (tools/undistort_bench.py): -1 the built-in rule, 0 composed (the maps into scratch, then the remap kernels per frame), 1 the tile kernel wherever it
+ * applies.  Results do not depend on it. */
+MI355CV_API int mi355cv_undistortSetKernel(int mode);
+/* The tile kernel's LDS allotment in bytes (0: back to mi355cv_limit("undist_lds_kib") = 24 KiB; at most mi355cv_limit("undist_max_lds_kib") = 48 KiB): a tile whose
+ * source box exceeds it takes the per-pixel sampler, so a small value reaches that arm at small shapes.  Results do not depend on it. */
+MI355CV_API int mi355cv_undistortSetLds(int bytes);
+/* The frames a workgroup of the tile kernel walks with one evaluation of the rule (0: back to mi355cv_limit("undist_frames_per_group"); at most
+ * mi355cv_limit("undist_max_frames_per_group") = 64).  Results do not depend on it. */
+MI355CV_API int mi355cv_undistortSetFramesPerGroup(int frames);
+
 #ifdef __cplusplus
 }
 #endif

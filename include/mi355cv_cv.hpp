@@ -1009,6 +1009,120 @@ inline void fastNlMeansDenoisingColored(cv::InputArray _src, cv::OutputArray _ds
 }
 #endif
 
+#ifdef OPENCV_CALIB3D_HPP        // cv::undistort, cv::initUndistortRectifyMap and cv::reprojectImageTo3D live in opencv2/calib3d.hpp; include it before this header
+// The two ends of the stereo pipeline (csrc/undistort.hip; the reference has no HAL hook for them).  The images are the project's restatement (DESIGN 6.21,
+// tests/undistort_restate.py): the closed form of the map per destination pixel in separately rounded doubles, so a map entry may differ from the stock function's,
+// which accumulates along the row, by one unit of 1/32 px.  Everything the entries decline (tauX / tauY, a singular newCameraMatrix * R, sizes over the limits, dst
+// overlapping src, UMat, no device) goes to the stock function, which finds the destination untouched.  Out of scope: stereoRectify, getOptimalNewCameraMatrix,
+// undistortPoints, the fisheye model.  Not compiled here: the reference's headers are absent.
+namespace detail {
+// K (3 x 3), distCoeffs (a vector of 0, 4, 5, 8, 12 or 14), R (3 x 3 or empty), newK (3 x 3, 3 x 4 or empty) as contiguous doubles; -> false: leave it to the stock function
+struct Camera {
+    double K[9], R[9], nK[9], dist[14]; int ndist = 0; bool hasR = false, hasNK = false;
+    bool set(cv::InputArray _K, cv::InputArray _dist, cv::InputArray _R, cv::InputArray _newK)
+    {
+        cv::Mat k, d, r, n;
+        _K.getMat().convertTo(k, CV_64F);
+        if (k.rows != 3 || k.cols != 3) return false;
+        for (int i = 0; i < 9; i++) K[i] = k.at<double>(i / 3, i % 3);
+        if (!_dist.empty()) {
+            _dist.getMat().convertTo(d, CV_64F);
+            if (d.total() > 14 || (d.rows != 1 && d.cols != 1)) return false;
+            ndist = (int)d.total();
+            d = d.reshape(1, 1);
+            for (int i = 0; i < ndist; i++) dist[i] = d.at<double>(0, i);
+        }
+        if (!_R.empty()) {
+            _R.getMat().convertTo(r, CV_64F);
+            if (r.rows != 3 || r.cols != 3) return false;
+            for (int i = 0; i < 9; i++) R[i] = r.at<double>(i / 3, i % 3);
+            hasR = true;
+        }
+        if (!_newK.empty()) {
+            _newK.getMat().convertTo(n, CV_64F);
+            if (n.rows != 3 || (n.cols != 3 && n.cols != 4)) return false;
+            for (int i = 0; i < 9; i++) nK[i] = n.at<double>(i / 3, i % 3);
+            hasNK = true;
+        }
+        return true;
+    }
+};
+} // namespace detail
+
+inline void initUndistortRectifyMap(cv::InputArray cameraMatrix, cv::InputArray distCoeffs, cv::InputArray R, cv::InputArray newCameraMatrix, cv::Size size, int m1type,
+                                    cv::OutputArray _map1, cv::OutputArray _map2)
+{
+    detail::Camera c;
+    if (m1type <= 0) m1type = CV_16SC2;
+    if (_map1.kind() == cv::_InputArray::MAT && _map2.kind() == cv::_InputArray::MAT && (m1type == CV_16SC2 || m1type == CV_32FC1 || m1type == CV_32FC2) &&
+        c.set(cameraMatrix, distCoeffs, R, newCameraMatrix)) {
+        _map1.create(size, m1type);
+        cv::Mat map1 = _map1.getMat(), map2;
+        if (m1type != CV_32FC2) { _map2.create(size, m1type == CV_16SC2 ? CV_16UC1 : CV_32FC1); map2 = _map2.getMat(); } else _map2.release();
+        if (mi355cv_initUndistortRectifyMap(c.K, c.ndist ? c.dist : nullptr, c.ndist, c.hasR ? c.R : nullptr, c.hasNK ? c.nK : nullptr, size.width, size.height, m1type, map1.data,
+                                            map1.step, map2.data, map2.step) == MI355CV_OK)
+            return;
+    }
+    cv::initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix, size, m1type, _map1, _map2);
+}
+
+// the rectifying warp in one call: cv::remap(src, dst, maps of initUndistortRectifyMap(..., dsize, CV_16SC2), interpolation, borderMode, borderValue) without the maps
+inline void undistortRectify(cv::InputArray _src, cv::OutputArray _dst, cv::InputArray cameraMatrix, cv::InputArray distCoeffs, cv::InputArray R, cv::InputArray newCameraMatrix,
+                             cv::Size dsize, int interpolation = cv::INTER_LINEAR, int borderMode = cv::BORDER_CONSTANT, const cv::Scalar& borderValue = cv::Scalar())
+{
+    detail::Camera c;
+    if (_src.kind() == cv::_InputArray::MAT && _dst.kind() == cv::_InputArray::MAT && c.set(cameraMatrix, distCoeffs, R, newCameraMatrix)) {
+        cv::Mat src = _src.getMat();
+        if (src.dims <= 2 && !src.empty()) {
+            if (dsize.area() == 0) dsize = src.size();
+            _dst.create(dsize, src.type());
+            cv::Mat dst = _dst.getMat();
+            if (dst.data != src.data &&
+                mi355cv_undistortRectify(src.type(), src.data, src.step, src.cols, src.rows, dst.data, dst.step, dst.cols, dst.rows, c.K, c.ndist ? c.dist : nullptr, c.ndist,
+                                         c.hasR ? c.R : nullptr, c.hasNK ? c.nK : nullptr, interpolation, borderMode, borderValue.val) == MI355CV_OK)
+                return;
+        }
+    }
+    cv::Mat map1, map2;
+    cv::initUndistortRectifyMap(cameraMatrix, distCoeffs, R, newCameraMatrix.empty() ? cameraMatrix : newCameraMatrix, dsize.area() ? dsize : _src.size(), CV_16SC2, map1, map2);
+    cv::remap(_src, _dst, map1, map2, interpolation, borderMode, borderValue);
+}
+
+inline void undistort(cv::InputArray src, cv::OutputArray dst, cv::InputArray cameraMatrix, cv::InputArray distCoeffs, cv::InputArray newCameraMatrix = cv::noArray())
+{
+    detail::Camera c;
+    if (src.kind() == cv::_InputArray::MAT && dst.kind() == cv::_InputArray::MAT && c.set(cameraMatrix, distCoeffs, cv::noArray(), newCameraMatrix)) {
+        cv::Mat s = src.getMat();
+        if (s.dims <= 2 && !s.empty()) {
+            dst.create(s.size(), s.type());
+            cv::Mat d = dst.getMat();
+            const double zero[4] = {0, 0, 0, 0};
+            if (d.data != s.data &&
+                mi355cv_undistortRectify(s.type(), s.data, s.step, s.cols, s.rows, d.data, d.step, d.cols, d.rows, c.K, c.ndist ? c.dist : nullptr, c.ndist, nullptr,
+                                         c.hasNK ? c.nK : nullptr, cv::INTER_LINEAR, cv::BORDER_CONSTANT, zero) == MI355CV_OK)
+                return;
+        }
+    }
+    cv::undistort(src, dst, cameraMatrix, distCoeffs, newCameraMatrix);
+}
+
+inline void reprojectImageTo3D(cv::InputArray _disparity, cv::OutputArray _3dImage, cv::InputArray _Q, bool handleMissingValues = false, int ddepth = -1)
+{
+    if (_disparity.kind() == cv::_InputArray::MAT && _3dImage.kind() == cv::_InputArray::MAT && (ddepth == -1 || ddepth == CV_32F)) {
+        cv::Mat disp = _disparity.getMat(), Q;
+        _Q.getMat().convertTo(Q, CV_64F);
+        const int t = disp.type();
+        if (disp.dims <= 2 && !disp.empty() && Q.rows == 4 && Q.cols == 4 && Q.isContinuous() && (t == CV_8UC1 || t == CV_16SC1 || t == CV_32SC1 || t == CV_32FC1)) {
+            _3dImage.create(disp.size(), CV_32FC3);
+            cv::Mat out = _3dImage.getMat();
+            if (mi355cv_reprojectImageTo3D(disp.data, disp.step, t, out.data, out.step, disp.cols, disp.rows, Q.ptr<double>(), handleMissingValues ? 1 : 0, ddepth) == MI355CV_OK)
+                return;
+        }
+    }
+    cv::reprojectImageTo3D(_disparity, _3dImage, _Q, handleMissingValues, ddepth);
+}
+#endif
+
 // Batches across the GPUs of one node from C++: forEachShard({0,1,...,7}, nframes, [&](int slot, int device, int first, int count) { ... return 0; })
 // runs the callable once per device on its own host thread bound to that device (mi355cv_runSharded, csrc/shard.hip), frames [first, first + count) being that
 // device's share; inside, call cv:: functions of a HAL-enabled build or mi355cv:: / mi355cv_*Batch entry points on Mats whose storage lives on `device`

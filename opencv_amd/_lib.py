@@ -93,6 +93,17 @@ def _load():
         "mi355cv_fastNlMeansWeights": (c_int, [ctypes.c_float, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p]),
         "mi355cv_fastNlMeansSetKernel": (c_int, [c_int]),
         "mi355cv_fastNlMeansSetChunk": (c_int, [c_int]),
+        "mi355cv_initUndistortRectifyMap": (c_int, [ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, c_int, c_int, ctypes.c_void_p, c_sz,
+                                                    ctypes.c_void_p, c_sz]),
+        "mi355cv_undistortRectify": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, ctypes.c_void_p,
+                                             ctypes.c_void_p, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_undistortRectifyBatch": (c_int, [c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int,
+                                                  ctypes.c_void_p, ctypes.c_void_p, c_int, c_int, ctypes.c_void_p]),
+        "mi355cv_reprojectImageTo3D": (c_int, [c_u8p, c_sz, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int]),
+        "mi355cv_reprojectImageTo3DBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_u8p, c_sz, c_sz, c_int, c_int, c_int, ctypes.c_void_p, c_int, c_int]),
+        "mi355cv_undistortSetKernel": (c_int, [c_int]),
+        "mi355cv_undistortSetLds": (c_int, [c_int]),
+        "mi355cv_undistortSetFramesPerGroup": (c_int, [c_int]),
         "mi355cv_remap": (c_int, [c_int, c_u8p, c_sz, c_int, c_int, c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int,
                                   c_int, c_int, ctypes.c_void_p]),
         "mi355cv_convertMaps": (c_int, [ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz, c_int, ctypes.c_void_p, c_sz,

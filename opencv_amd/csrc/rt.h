@@ -81,6 +81,15 @@ constexpr int NLM_TILE_ROWS = 32;              // ... and its rows, two waves of
 constexpr int NLM_TILE_MAX_TEMPLATE = 9;       // ... the largest T of the tile kernel: the rows of a patch are a lane's registers with compile-time indices
 constexpr int NLM_LDS_TABLE = 49152;           // ... entries of the weight table's non-zero prefix the tile kernel keeps in LDS: 96 KiB as 16-bit words (S >= 13), which holds the 39546 of h = 50 on three channels beside the tile
 constexpr int NLM_TILE_LDS_KIB = 160;          // ... table and tile together: the LDS of a CU
+constexpr int UNDIST_MAX_DIM = 16384;          // mi355cv_initUndistortRectifyMap / mi355cv_undistortRectify*: width and height of the destination (the neighbours' bound; a column and a row are exact doubles)
+constexpr int UNDIST_MAX_SRC_DIM = 32767;      // ... and of the source: a map entry is 16 bits (mi355cv_remap's own bound)
+constexpr int UNDIST_TILE_COLS = 128;          // ... geometry, reported for the tests' shapes: destination columns of a tile of k_undist8_tile (warp8.h)
+constexpr int UNDIST_TILE_ROWS = 32;           // ... and its rows on one channel (16 on 3 / 4 channels)
+constexpr int UNDIST_LDS_KIB = 24;             // ... the source tile's allotment: six workgroups of four waves a CU
+constexpr int UNDIST_MAX_LDS_KIB = 48;         // ... the most mi355cv_undistortSetLds accepts (with the extremes' 64 bytes below the 64 KiB a launch gets unasked)
+constexpr int UNDIST_FRAMES_PER_GROUP = 8;     // ... frames of a batch a workgroup walks with one evaluation of the rule
+constexpr int UNDIST_MAX_FRAMES_PER_GROUP = 64; // ... the most mi355cv_undistortSetFramesPerGroup accepts
+constexpr int REPROJECT_MAX_DIM = 16384;       // mi355cv_reprojectImageTo3D*: width and height (mi355cv_minMaxLoc's bound, which finds the frame's minimum)
 }
 
 struct ThreadCtx;

@@ -585,7 +585,10 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"sgbm_max_dim", SGBM_MAX_DIM}, {"sgbm_max_disparities", SGBM_MAX_DISPARITIES}, {"sgbm_max_cost", SGBM_MAX_COST}, {"sgbm_max_scratch_mib", (int)(SGBM_MAX_SCRATCH_BYTES >> 20)},
         {"sgbm_tile_cols", SGBM_TILE_COLS}, {"sgbm_strip_rows", SGBM_STRIP_ROWS}, {"sgbm_chunk", SGBM_CHUNK}, {"sgbm_path_block", SGBM_PATH_BLOCK},
         {"nlm_max_dim", NLM_MAX_DIM}, {"nlm_max_window", NLM_MAX_WINDOW}, {"nlm_tile_cols", NLM_TILE_COLS}, {"nlm_tile_rows", NLM_TILE_ROWS},
-        {"nlm_tile_max_template", NLM_TILE_MAX_TEMPLATE}, {"nlm_lds_table", NLM_LDS_TABLE}, {"nlm_tile_lds_kib", NLM_TILE_LDS_KIB}, {"nlm_max_pixel_work", NLM_MAX_PIXEL_WORK}};
+        {"nlm_tile_max_template", NLM_TILE_MAX_TEMPLATE}, {"nlm_lds_table", NLM_LDS_TABLE}, {"nlm_tile_lds_kib", NLM_TILE_LDS_KIB}, {"nlm_max_pixel_work", NLM_MAX_PIXEL_WORK},
+        {"undist_max_dim", UNDIST_MAX_DIM}, {"undist_max_src_dim", UNDIST_MAX_SRC_DIM}, {"undist_tile_cols", UNDIST_TILE_COLS}, {"undist_tile_rows", UNDIST_TILE_ROWS},
+        {"undist_lds_kib", UNDIST_LDS_KIB}, {"undist_max_lds_kib", UNDIST_MAX_LDS_KIB}, {"undist_frames_per_group", UNDIST_FRAMES_PER_GROUP},
+        {"undist_max_frames_per_group", UNDIST_MAX_FRAMES_PER_GROUP}, {"reproject_max_dim", REPROJECT_MAX_DIM}};
     if (!key) return -1;
     for (const auto& e : tab) if (!strcmp(key, e.k)) return e.v;
     return -1;
