@@ -413,7 +413,7 @@ MI355CV_API int mi355cv_connectedComponentsStatsBatch(const mi355cv_uchar* label
  * 16384 (a packed point (y << 16 | x) needs both <= 65535; 16384 is the bound of the neighbouring entries and keeps a frame's point list within 1 GiB and every
  * count below 2^28), an accumulator above mi355cv_limit("hough_max_accum") = 2^26 cells (256 MiB per frame; a cell index is the low word of the sort key), more than 65535 angles, and
  * lines that overlap the source in HBM.  Image and lines both in HBM, or both in host memory (staged under the host policy, cost class HOST_HEAVY; the lines then
- * come back in a second copy after the counts).  cv::HoughLinesP, cv::HoughCircles and cv::HoughLinesPointSet have no entry. */
+ * come back in a second copy after the counts).  cv::HoughCircles: mi355cv_houghCircles below.  cv::HoughLinesP and cv::HoughLinesPointSet have no entry. */
 MI355CV_API int mi355cv_houghLines(const mi355cv_uchar* src_data, size_t src_step, int width, int height, float* lines, int lines_cn, int max_lines,
         double rho, double theta, int threshold, double srn, double stn, double min_theta, double max_theta, int* nlines);
 /* `nframes` frames of one geometry, `src_frame_stride` / `lines_frame_stride` bytes apart (the latter a multiple of 4 and at least max_lines rows); all in HBM,
@@ -427,6 +427,64 @@ MI355CV_API int mi355cv_houghLinesBatch(const mi355cv_uchar* src_data, size_t sr
  * touched and src is only tested for NULL.  The same refusals as mi355cv_houghLines. */
 MI355CV_API int mi355cv_houghLinesAccum(const mi355cv_uchar* src_data, size_t src_step, int width, int height, double rho, double theta, double min_theta,
         double max_theta, int* accum, size_t accum_step, int* numangle, int* numrho);
+/* cv::HoughCircles with method HOUGH_GRADIENT (= 3; HoughCirclesGradient, hough.cpp) has no HAL hook (csrc/houghcircles.hip).  src CV_8UC1.  "float" below is IEEE
+ * binary32 with every operation rounded on its own (no fused multiply-add), sqrtf and / correctly rounded, cvRound round-half-to-even; SHIFT = 10, ONE = 1024.
+ *   arguments  dp = max((float)dp, 1.f), idp = 1.f / dp; canny = cvRound(param1), accT = cvRound(param2); minRadius = max(0, minRadius); centres only when
+ *              maxRadius < 0; maxRadius <= 0 becomes max(width, height), otherwise maxRadius <= minRadius becomes minRadius + 2.
+ *   edges      dx, dy = Sobel 3 x 3 into CV_16S, BORDER_REPLICATE (mi355cv_sobel); edges = the stages of mi355cv_canny on them with low = max(1, canny / 2),
+ *              high = canny, L1 magnitude.  Both stay in HBM.
+ *   accum      acols = ceil(width * idp), arows = ceil(height * idp) (the product in float); (arows + 2) x (acols + 2) CV_32S, row stride astep = acols + 2, zeroed.
+ *   votes      every pixel (x, y) with edges != 0, (vx, vy) != (0, 0) and mag = sqrtf((float)(vx vx + vy vy)) >= 1 is a point.  sx = cvRound((vx * idp) * ONE / mag),
+ *              sy likewise; x0 = cvRound((x * idp) * ONE), y0 likewise.  For both signs of (sx, sy) and r = minRadius .. maxRadius: x2 = (x0 + r sx) >> SHIFT,
+ *              y2 = (y0 + r sy) >> SHIFT; the ray ends at the first r with x2 outside [0, acols) or y2 outside [0, arows), otherwise cell y2 * astep + x2 gains 1.
+ *   centres    cells b = y * astep + x, y in 1 .. arows, x in 1 .. acols, with a[b] > accT, a[b] > a[b - 1], a[b] >= a[b + 1], a[b] > a[b - astep],
+ *              a[b] >= a[b + astep]; ordered by a[b] descending, equal votes by b ascending; cx = (x + 0.5f) * dp, cy = (y + 0.5f) * dp.
+ *   radius     nBins = cvRound((maxRadius - minRadius) / dp * 10).  Every point with (float)minRadius^2 <= r2 <= (float)maxRadius^2, r2 = ex ex + ey ey,
+ *              ex = cx - px, ey = cy - py, adds 1 to bin clamp(cvRound((sqrtf(r2) - minRadius) / dp * 10), 0, nBins - 1).  The scan: maxCount = 0, rBest = 0;
+ *              for (j = nBins - 1; j > 0; j--) if (bins[j]) { upbin = j; cur = 0; for (; j > upbin - 10 && j >= 0; j--) cur += bins[j];
+ *              rCur = (upbin + j) / 2.f / 10 * dp + minRadius; if (cur * rBest >= maxCount * rCur || (rBest < FLT_EPSILON && cur >= maxCount))
+ *              { rBest = rCur; maxCount = cur; } } -- the outer j-- after a window included.  The circle (cx, cy, rBest) with votes = maxCount is kept when
+ *              maxCount > accT.  Centres only: every centre is a circle (cx, cy, 0) with votes = a[b].
+ *   order      votes descending, equal votes by b ascending.
+ *   suppress   the circles are walked in that order; one is kept unless a circle kept before it has ddx ddx + ddy ddy < minDist * minDist (in float); the walk
+ *              stops after max_circles kept circles.
+ * Every count is an integer and every float is computed per element, so the result is a pure function of the input.  The reference was not available to pin these
+ * steps: they are this project's restatement of the rule, held bit for bit against two independent Python restatements (tests/houghcircles_restate.py).
+ * circles: max_circles rows of circles_cn floats, dense: (x, y, radius), or with circles_cn = 4 (x, y, radius, (float)votes).  *ncircles (HOST memory; reading it
+ * back is the call's one host synchronisation of its own -- the hysteresis of the edge stage has its own) receives the number of rows written; a count equal to
+ * max_circles means there may be more.  Rows past the count are never written.
+ * Answered MI355CV_NOT_IMPLEMENTED with every destination and count untouched, before any device is touched: a method other than HOUGH_GRADIENT (HOUGH_GRADIENT_ALT
+ * = 4 among them), dp, minDist, cvRound(param1) or cvRound(param2) not positive or NaN, circles_cn other than 3 or 4, max_circles < 1 or above
+ * mi355cv_limit("houghcircles_max_circles") = 65536, null pointers, width or height <= 0 or above mi355cv_limit("houghcircles_max_dim") = 16384 (a packed point
+ * (y << 16 | x), counts below 2^28), (arows + 2)(acols + 2) above mi355cv_limit("houghcircles_max_accum") = 2^26 cells (a cell index is the low word of the sort
+ * key), a prepared maxRadius above mi355cv_limit("houghcircles_max_radius") = 32768 (x0 + r sx stays inside 31 bits), nBins < 1, steps below a row; and, needing
+ * the device, circles that overlap the source in HBM.  Image and circles both in HBM, or both in host memory (staged under the host policy, cost class HOST_HEAVY;
+ * the circles then come back in a second copy after the counts).  mi355cv_limit("houghcircles_lds_bins") = 40960: radius histograms up to that many bins are kept
+ * in LDS, longer ones in HBM with the same arithmetic. */
+MI355CV_API int mi355cv_houghCircles(const mi355cv_uchar* src_data, size_t src_step, int width, int height, float* circles, int circles_cn, int max_circles, int method,
+        double dp, double minDist, double param1, double param2, int minRadius, int maxRadius, int* ncircles);
+/* `nframes` frames of one geometry, `src_frame_stride` / `circles_frame_stride` bytes apart (the former at least a frame, the latter a multiple of 4 and at least
+ * max_circles rows); all in HBM, or all in host memory.  The hysteresis of the edge stage keeps its own host round-trips per frame; everything after it is one
+ * sequence of launches for all frames, and the counts come back in one copy.  ncircles: `nframes` ints in HOST memory.  A frame without an edge pixel yields 0
+ * circles and does not affect the others.  At most 65535 frames. */
+MI355CV_API int mi355cv_houghCirclesBatch(const mi355cv_uchar* src_data, size_t src_step, size_t src_frame_stride, int width, int height, float* circles, int circles_cn,
+        int max_circles, size_t circles_frame_stride, int nframes, int method, double dp, double minDist, double param1, double param2, int minRadius, int maxRadius,
+        int* ncircles);
+/* The transform from a given edge map (CV_8UC1, non-zero = edge, rows edges_step bytes apart) and its CV_16SC1 gradient planes (rows grad_step bytes apart, an even
+ * number, both planes at even addresses): steps `votes` to `suppress` above; mi355cv_houghCircles is this entry after its edge stage.  An edge pixel whose gradient
+ * is (0, 0) does not vote and is no point.  param1 is checked as above and otherwise unused.  All four buffers in HBM, or all in host memory. */
+MI355CV_API int mi355cv_houghCirclesGradient(const mi355cv_uchar* edges, size_t edges_step, const short* dx, const short* dy, size_t grad_step, int width, int height,
+        float* circles, int circles_cn, int max_circles, int method, double dp, double minDist, double param1, double param2, int minRadius, int maxRadius, int* ncircles);
+/* The geometry, and the accumulator itself: *arows and *acols (HOST memory) always; with accum != NULL the full (arows + 2) x (acols + 2) CV_32S accumulator after
+ * step `votes`, rows accum_step bytes apart (a multiple of 4, at least acols + 2 ints), where the planes live.  With accum == NULL no device is touched and the planes
+ * are only tested for NULL.  The same refusals as mi355cv_houghCirclesGradient, as far as its arguments go. */
+MI355CV_API int mi355cv_houghCirclesAccum(const mi355cv_uchar* edges, size_t edges_step, const short* dx, const short* dy, size_t grad_step, int width, int height,
+        double dp, int minRadius, int maxRadius, int* accum, size_t accum_step, int* arows, int* acols);
+/* A/B switch of the vote: -1 (the default) the library chooses, 0 k_hc_vote (integer atomicAdd into the accumulator in HBM; serves every parameter set),
+ * 1 k_hc_vote_tile (a workgroup owns a tile of mi355cv_limit("houghcircles_tile")^2 cells in LDS and writes it with plain stores).  Both give the identical
+ * accumulator.  The tile kernel was the slower one at every reach measured, so the library always chooses k_hc_vote.  Returns 0, or -1 for another
+ * value. */
+MI355CV_API int mi355cv_houghCirclesSetKernel(int mode);
 /* cv::minMaxLoc (csrc/minmax.hip).  src: one channel of CV_8U, CV_8S, CV_16U, CV_16S, CV_32S, CV_32F or CV_64F (depth 0 .. 6), its base aligned to the element
  * only (a ROI that starts at an odd column is served).  mask: NULL, or CV_8UC1 of the same size with its own pitch; non-zero selects a pixel.
  *   candidates   the selected pixels whose value is not NaN.

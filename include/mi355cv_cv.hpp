@@ -1,6 +1,6 @@
 // mi355cv_cv.hpp -- cv::-identical C++ signatures for the hot-path functions that have NO imgproc HAL hook
 // (SURVEY.md §8b): cornerHarris, cornerMinEigenVal, goodFeaturesToTrack, buildPyramid, pyrUp, demosaicing, distanceTransform, connectedComponents,
-// connectedComponentsWithStats, HoughLines, minMaxLoc, calcHist, calcBackProject, matchTemplate -- and for the map
+// connectedComponentsWithStats, HoughLines, HoughCircles, minMaxLoc, calcHist, calcBackProject, matchTemplate -- and for the map
 // representations of remap the HAL does not cover, convertMaps and warpPolar.  Header-only glue over
 // the C ABI of mi355cv.h: each wrapper calls the fused MI355X entry point and falls back to the stock cv:: function when the
 // library declines (unsupported arguments, no gfx950 device, MI355CV_DISABLE=1), exactly as a HAL hook returning
@@ -294,6 +294,33 @@ inline void HoughLines(cv::InputArray _image, cv::OutputArray _lines, double rho
     }
     if (type == CV_32FC3) cv::HoughLinesWithAccumulator(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
     else cv::HoughLines(image, _lines, rho, theta, threshold, srn, stn, min_theta, max_theta);
+}
+
+// cv::HoughCircles (imgproc.hpp; hough.cpp HoughCirclesGradient): the circle transform of a CV_8UC1 image on the device with method cv::HOUGH_GRADIENT, Vec3f
+// (x, y, radius) or -- when `circles` is a Vec4f array -- Vec4f (x, y, radius, votes), strongest first.  A first call with room for 1024 circles; while the
+// library reports a full list, one more call with twice the capacity.  The steps are this project's restatement of the reference's rule (mi355cv.h), the reference
+// was not available to pin them.  Everything the library declines (cv::HOUGH_GRADIENT_ALT among it) goes to the stock function.  Like mi355cv::pyrUp, this wrapper
+// has not yet been compiled against the reference's headers.
+inline void HoughCircles(cv::InputArray _image, cv::OutputArray _circles, int method, double dp, double minDist, double param1 = 100, double param2 = 100,
+                         int minRadius = 0, int maxRadius = 0)
+{
+    cv::Mat image = _image.getMat();
+    const int type = _circles.fixedType() && _circles.type() == CV_32FC4 ? CV_32FC4 : CV_32FC3, cn = CV_MAT_CN(type);
+    if (image.dims <= 2 && !image.empty() && image.type() == CV_8UC1 && !_circles.isUMat()) {
+        const int top = mi355cv_limit("houghcircles_max_circles");
+        for (int cap = 1024, n = 0; cap <= top; cap *= 2) {
+            std::vector<float> buf((size_t)cap * cn);
+            if (mi355cv_houghCircles(image.data, image.step, image.cols, image.rows, buf.data(), cn, cap, method, dp, minDist, param1, param2, minRadius, maxRadius, &n) !=
+                MI355CV_OK)
+                break;
+            if (n < cap || cap == top) {
+                if (n == 0) { _circles.release(); return; }
+                cv::Mat(1, n, type, buf.data()).copyTo(_circles);
+                return;
+            }
+        }
+    }
+    cv::HoughCircles(image, _circles, method, dp, minDist, param1, param2, minRadius, maxRadius);
 }
 
 // cv::minMaxLoc (core.hpp): one channel of CV_8U .. CV_64F with an optional CV_8UC1 mask; any output may be null.  NaN is never a candidate and an empty

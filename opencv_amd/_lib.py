@@ -217,6 +217,14 @@ def _load():
         "mi355cv_houghLinesBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_sz, c_int, c_dbl, c_dbl, c_int, c_dbl, c_dbl, c_dbl, c_dbl,
                                             ctypes.POINTER(c_int)]),
         "mi355cv_houghLinesAccum": (c_int, [c_u8p, c_sz, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, ctypes.c_void_p, c_sz, ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+        "mi355cv_houghCircles": (c_int, [c_u8p, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_int, ctypes.POINTER(c_int)]),
+        "mi355cv_houghCirclesBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_sz, c_int, c_int, c_dbl, c_dbl, c_dbl, c_dbl, c_int, c_int,
+                                              ctypes.POINTER(c_int)]),
+        "mi355cv_houghCirclesGradient": (c_int, [c_u8p, c_sz, ctypes.c_void_p, ctypes.c_void_p, c_sz, c_int, c_int, ctypes.c_void_p, c_int, c_int, c_int, c_dbl, c_dbl, c_dbl,
+                                                 c_dbl, c_int, c_int, ctypes.POINTER(c_int)]),
+        "mi355cv_houghCirclesAccum": (c_int, [c_u8p, c_sz, ctypes.c_void_p, ctypes.c_void_p, c_sz, c_int, c_int, c_dbl, c_int, c_int, ctypes.c_void_p, c_sz,
+                                              ctypes.POINTER(c_int), ctypes.POINTER(c_int)]),
+        "mi355cv_houghCirclesSetKernel": (c_int, [c_int]),
         "mi355cv_minMaxLoc": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_u8p, c_sz, ctypes.c_void_p, ctypes.c_void_p]),
         "mi355cv_minMaxLocBatch": (c_int, [c_u8p, c_sz, c_sz, c_int, c_int, c_int, c_u8p, c_sz, c_sz, c_int, ctypes.c_void_p, ctypes.c_void_p]),
         "mi355cv_calcHist": (c_int, [c_u8p, c_sz, c_int, c_int, c_int, c_int, ctypes.c_void_p, c_int, ctypes.c_void_p, ctypes.c_void_p, c_int, c_u8p, c_sz, ctypes.c_void_p, c_int,

@@ -10,6 +10,7 @@
 //                                                                                                                  (k_canny_hyst)
 //   5. dst = 255 where map == 2                                                                                    (k_canny_final)
 #include "rt.h"
+#include "canny.h"
 #include <cmath>
 
 using namespace mi355;
@@ -157,6 +158,39 @@ __global__ __launch_bounds__(256) void k_canny_final(const uchar* __restrict__ m
 
 } // namespace
 
+namespace mi355 {
+
+size_t cannyMapPitch(int width) { return ((size_t)width + 63) & ~(size_t)63; }
+size_t cannyMapBytes(int width, int height) { return cannyMapPitch(width) * (((size_t)height + TH - 1) / TH * TH); }
+
+bool cannyFromGradients(const short* dx, const short* dy, size_t gstep, int width, int height, int cn, int L2, int low, int high, uchar* map, int* flag,
+                        uchar* dd, size_t dds, hipStream_t st)
+{
+    const size_t pitch = cannyMapPitch(width);
+    dim3 hgrid(divUp(width, TW), divUp(height, TH));
+    hipLaunchKernelGGL(k_canny_magnms, hgrid, dim3(256), 0, st, dx, dy, gstep / 2, width, height, cn, L2, low, high, map, pitch);
+    // passes are chained through one flag each: a pass that finds the flag of its predecessor clear returns at once, so a burst of
+    // PASSES launches costs little once the map has converged, and the host looks at the last flag only
+    constexpr int PASSES = 8;
+    // every productive pass promotes at least one candidate, so the number of passes is bounded by the number of pixels; a chain that
+    // winds through the tiles (a spiral) really does need one pass per tile crossing
+    const long long maxRounds = ((long long)width * height) / PASSES + 2;
+    for (long long round = 0; round < maxRounds; round++) {
+        if (hipMemsetAsync(flag, 0, PASSES * sizeof(int), st) != hipSuccess) return false;
+        for (int k = 0; k < PASSES; k++)
+            hipLaunchKernelGGL(k_canny_hyst, hgrid, dim3(256), 0, st, map, pitch, width, height, k ? flag + k - 1 : (const int*)nullptr, flag + k);
+        int last = 0;
+        if (hipMemcpyAsync(&last, flag + PASSES - 1, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
+            return false;
+        if (!last) break;
+    }
+    const int dal = ((((uintptr_t)dd | dds) & 3) == 0) ? 1 : 0;
+    hipLaunchKernelGGL(k_canny_final, dim3(divUp(divUp(width, 4), 64), divUp(height, 4)), dim3(256), 0, st, map, pitch, dd, dds, width, height, dal);
+    return true;
+}
+
+} // namespace mi355
+
 extern "C" MI355CV_API int mi355cv_canny(const uchar* src_data, size_t src_step, uchar* dst_data, size_t dst_step, int width, int height, int cn,
                                          double lowThreshold, double highThreshold, int ksize, bool L2gradient)
 {
@@ -177,34 +211,14 @@ extern "C" MI355CV_API int mi355cv_canny(const uchar* src_data, size_t src_step,
     const uchar* ds = stg.in(src_data, src_step, (size_t)width * cn, height, &dss);
     uchar* dd = stg.out(dst_data, dst_step, (size_t)width, height, &dds);
     const size_t gstep = (((size_t)width * cn * 2) + 255) & ~(size_t)255;             // bytes per row of the 16S gradient images
-    const size_t pitch = ((size_t)width + 63) & ~(size_t)63;                          // elements per row of mag / gx / gy / map
     short* dx = (short*)stg.scratch(gstep * height);
     short* dy = (short*)stg.scratch(gstep * height);
-    uchar* map = (uchar*)stg.scratch(pitch * (((size_t)height + TH - 1) / TH * TH));
+    uchar* map = (uchar*)stg.scratch(cannyMapBytes(width, height));
     int* flag = (int*)stg.scratch(256);
     MI355_DECLINE_IF(!ds || !dd || !dx || !dy || !map || !flag);
     int rc = mi355cv_sobel(ds, dss, (uchar*)dx, gstep, width, height, MI355CV_8U, MI355CV_16S, cn, 0, 0, 0, 0, 1, 0, ksize, 1.0, 0.0, B_REPLICATE);
     if (rc == MI355CV_OK) rc = mi355cv_sobel(ds, dss, (uchar*)dy, gstep, width, height, MI355CV_8U, MI355CV_16S, cn, 0, 0, 0, 0, 0, 1, ksize, 1.0, 0.0, B_REPLICATE);
     if (rc != MI355CV_OK) return rc;
-    hipStream_t st = stream();
-    dim3 hgrid(divUp(width, TW), divUp(height, TH));
-    hipLaunchKernelGGL(k_canny_magnms, hgrid, dim3(256), 0, st, dx, dy, gstep / 2, width, height, cn, L2gradient ? 1 : 0, low, high, map, pitch);
-    // passes are chained through one flag each: a pass that finds the flag of its predecessor clear returns at once, so a burst of
-    // PASSES launches costs little once the map has converged, and the host looks at the last flag only
-    constexpr int PASSES = 8;
-    // every productive pass promotes at least one candidate, so the number of passes is bounded by the number of pixels; a chain that
-    // winds through the tiles (a spiral) really does need one pass per tile crossing
-    const long long maxRounds = ((long long)width * height) / PASSES + 2;
-    for (long long round = 0; round < maxRounds; round++) {
-        if (hipMemsetAsync(flag, 0, PASSES * sizeof(int), st) != hipSuccess) return MI355CV_ERROR_UNKNOWN;
-        for (int k = 0; k < PASSES; k++)
-            hipLaunchKernelGGL(k_canny_hyst, hgrid, dim3(256), 0, st, map, pitch, width, height, k ? flag + k - 1 : (const int*)nullptr, flag + k);
-        int last = 0;
-        if (hipMemcpyAsync(&last, flag + PASSES - 1, sizeof(int), hipMemcpyDeviceToHost, st) != hipSuccess || hipStreamSynchronize(st) != hipSuccess)
-            return MI355CV_ERROR_UNKNOWN;
-        if (!last) break;
-    }
-    const int dal = ((((uintptr_t)dd | dds) & 3) == 0) ? 1 : 0;
-    hipLaunchKernelGGL(k_canny_final, dim3(divUp(divUp(width, 4), 64), divUp(height, 4)), dim3(256), 0, st, map, pitch, dd, dds, width, height, dal);
+    if (!cannyFromGradients(dx, dy, gstep, width, height, cn, L2gradient ? 1 : 0, low, high, map, flag, dd, dds, stream())) return MI355CV_ERROR_UNKNOWN;
     return stg.finish("canny");
 }

@@ -19,6 +19,7 @@
 // word of the sort key; 4K at rho = 0.25, theta = pi / 720 (34.6 M cells) is inside it.
 #include "rt.h"
 #include "hough_math.h"
+#include "hough_points.h"
 #include <algorithm>
 #include <vector>
 
@@ -33,15 +34,6 @@ namespace {
 
 using hough::Geom;
 
-// bytes x .. x + 3 of a row w wide as a dword, 0 for the ones past its end
-__device__ __forceinline__ uint32_t loadPix4(const uchar* row, int x, int w)
-{
-    if (x + 4 <= w && ((uintptr_t)(row + x) & 3) == 0) return *reinterpret_cast<const uint32_t*>(row + x);
-    uint32_t v = 0;
-    for (int k = 0; k < 4; k++) if (x + k < w) v |= (uint32_t)row[x + k] << (8 * k);
-    return v;
-}
-
 // ctr: two counters per frame, [2 f] the points, [2 f + 1] the candidates
 __global__ __launch_bounds__(256) void k_hough_points(const uchar* __restrict__ src, size_t sstep, size_t sframe, int w, int h, uint32_t* __restrict__ pts, size_t pframe,
                                                       uint32_t* __restrict__ ctr)
@@ -49,17 +41,14 @@ __global__ __launch_bounds__(256) void k_hough_points(const uchar* __restrict__ 
     const int lane = threadIdx.x & 63, x = blockIdx.x * 256 + 4 * lane, y = blockIdx.y * 4 + (threadIdx.x >> 6);
     if (y >= h) return;                                                      // the whole wave
     const uint32_t v = loadPix4(src + (size_t)blockIdx.z * sframe + (size_t)y * sstep, x, w);
-    const uint64_t b0 = __ballot(v & 0xffu), b1 = __ballot(v & 0xff00u), b2 = __ballot(v & 0xff0000u), b3 = __ballot(v & 0xff000000u);
-    const uint32_t total = __popcll(b0) + __popcll(b1) + __popcll(b2) + __popcll(b3);
+    uint32_t pre;
+    const uint32_t total = ballotPoints4(v, lane, &pre);
     if (!total) return;
-    const uint64_t below = (uint64_t(1) << lane) - 1;
-    const uint32_t pre = __popcll(b0 & below) + __popcll(b1 & below) + __popcll(b2 & below) + __popcll(b3 & below);
     uint32_t base = 0;
     if (lane == 0) base = atomicAdd(ctr + 2 * blockIdx.z, total);
     base = __shfl(base, 0, 64);
     uint32_t* out = pts + (size_t)blockIdx.z * pframe + base + pre;         // base + total <= w * h: every pixel is counted once
-#pragma unroll
-    for (int k = 0; k < 4; k++) if ((v >> (8 * k)) & 0xffu) *out++ = hough::packPoint(x + k, y);
+    storePoints4(v, x, y, out);
 }
 
 // tab: numangle sines, then numangle cosines, both already divided by rho

@@ -37,6 +37,12 @@ constexpr int DISTTRANSFORM_MAX_DIM = 16384; // mi355cv_distanceTransform: width
 constexpr int CCL_MAX_DIM = 16384;         // mi355cv_connectedComponents*: width and height (32-bit pixel indices and areas, coordinate sums below 2^53; ccl_math.h)
 constexpr int HOUGH_MAX_DIM = 16384;       // mi355cv_houghLines*: width and height (packed 16-bit point coordinates, counts below 2^28; hough_math.h)
 constexpr int HOUGH_MAX_ACCUM = 1 << 26;   // ... and the cells of the accumulator, (numangle + 2) x (numrho + 2): a cell index is the low word of the sort key
+constexpr int HOUGHCIRCLES_MAX_DIM = 16384;   // mi355cv_houghCircles*: width and height (packed 16-bit point coordinates, counts below 2^28; houghcircles_math.h)
+constexpr int HOUGHCIRCLES_MAX_ACCUM = 1 << 26; // ... the cells of the centre accumulator, (arows + 2) x (acols + 2): a cell index is the low word of the sort key
+constexpr int HOUGHCIRCLES_MAX_RADIUS = 32768;  // ... the prepared maxRadius: x0 + r * sx of the fixed-point ray stays inside 31 bits
+constexpr int HOUGHCIRCLES_MAX_CIRCLES = 65536; // ... max_circles: the kept list k_hc_suppress tests every candidate against
+constexpr int HOUGHCIRCLES_LDS_BINS = 40960;    // ... geometry, reported for the tests' shapes: radius histograms up to this many bins live in LDS (160 KiB), longer ones in HBM
+constexpr int HOUGHCIRCLES_TILE = 64;           // ... the side of the accumulator tile of k_hc_vote_tile (behind mi355cv_houghCirclesSetKernel(1) only: it won at no reach)
 constexpr int MINMAX_MAX_DIM = 16384;      // mi355cv_minMaxLoc*: width and height (a raster pixel index below 2^28, item counts in 32 bits; minmax_math.h)
 constexpr int DEMOSAIC_MAX_DIM = 16384;    // mi355cv_demosaic*: width and height (the neighbours' bound; a destination row offset of 8 bytes per pixel stays far below 2^31)
 constexpr int CALCHIST_MAX_DIM = 16384;    // mi355cv_calcHist* / mi355cv_calcBackProject*: width and height (the neighbours' bound; a frame has at most 2^28 pixels, so no count of one call passes int32; calchist_math.h)

@@ -571,7 +571,9 @@ MI355CV_API int mi355cv_limit(const char* key)
         {"adaptive_gaussian_max_block", SEP_MAX_TAPS}, {"adaptive_mean_max_block", ADAPTIVE_MEAN_MAX_BLOCK}, {"box_max_ksize", BOX_MAX_KSIZE},
         {"median8u_max_ksize", MEDIAN8U_MAX_KSIZE}, {"bilateral_max_d", 2 * BILATERAL_MAX_RADIUS + 1}, {"orb_max_levels", ORB_MAX_LEVELS}, {"filter2d_dft_taps", FILTER2D_DFT_TAPS},
         {"disttransform_max_dim", DISTTRANSFORM_MAX_DIM}, {"ccl_max_dim", CCL_MAX_DIM},
-        {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"minmax_max_dim", MINMAX_MAX_DIM},
+        {"hough_max_dim", HOUGH_MAX_DIM}, {"hough_max_accum", HOUGH_MAX_ACCUM}, {"houghcircles_max_dim", HOUGHCIRCLES_MAX_DIM}, {"houghcircles_max_accum", HOUGHCIRCLES_MAX_ACCUM},
+        {"houghcircles_max_radius", HOUGHCIRCLES_MAX_RADIUS}, {"houghcircles_max_circles", HOUGHCIRCLES_MAX_CIRCLES}, {"houghcircles_lds_bins", HOUGHCIRCLES_LDS_BINS},
+        {"houghcircles_tile", HOUGHCIRCLES_TILE}, {"minmax_max_dim", MINMAX_MAX_DIM},
         {"demosaic_max_dim", DEMOSAIC_MAX_DIM}, {"calchist_max_dim", CALCHIST_MAX_DIM}, {"calchist_max_bins", CALCHIST_MAX_BINS},
         {"mog2_max_dim", MOG2_MAX_DIM}, {"mog2_max_mixtures", MOG2_MAX_MIXTURES},
         {"farneback_max_dim", FARNEBACK_MAX_DIM}, {"farneback_max_winsize", FARNEBACK_MAX_WINSIZE}, {"farneback_max_poly_n", FARNEBACK_MAX_POLY_N},

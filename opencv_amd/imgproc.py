@@ -37,7 +37,7 @@ __all__ = ["cvtColor", "cvtColorBatch", "COLOR_BGR2YCrCb", "COLOR_RGB2YCrCb", "C
            "DIST_MASK_PRECISE", "connectedComponents", "connectedComponentsWithStats", "connectedComponentsBatch", "connectedComponentsWithStatsBatch",
            "CC_STAT_LEFT", "CC_STAT_TOP", "CC_STAT_WIDTH", "CC_STAT_HEIGHT", "CC_STAT_AREA", "CC_STAT_MAX",
            "CCL_DEFAULT", "CCL_WU", "CCL_GRANA", "CCL_BOLELLI", "CCL_SAUF", "CCL_BBDT", "CCL_SPAGHETTI",
-           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "minMaxLoc", "minMaxLocBatch", "calcHist", "calcHistBatch", "calcBackProject", "calcBackProjectBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
+           "HoughLines", "HoughLinesWithAccumulator", "HoughLinesBatch", "HoughLinesAccumulator", "HoughCircles", "HoughCirclesBatch", "HoughCirclesGradient", "HoughCirclesAccumulator", "HOUGH_GRADIENT", "HOUGH_GRADIENT_ALT", "minMaxLoc", "minMaxLocBatch", "calcHist", "calcHistBatch", "calcBackProject", "calcBackProjectBatch", "buildPyramid", "buildPyramidBatch", "cornerHarris", "cornerMinEigenVal", "cornerHarrisBatch", "goodFeaturesToTrack",
            "resize", "warpAffine", "warpPerspective", "SobelBatch", "boxFilterBatch", "sepFilter2DBatch", "thresholdBatch", "resizeBatch", "warpAffineBatch", "warpPerspectiveBatch", "pyrDownBatch", "remap", "convertMaps", "warpPolar", "WARP_FILL_OUTLIERS", "WARP_POLAR_LINEAR", "WARP_POLAR_LOG", "getRotationMatrix2D", "invertAffineTransform",
            "Canny", "equalizeHist", "createCLAHE", "CLAHE", "cvtColorBGR2NV", "THRESH_OTSU", "adaptiveThreshold", "ADAPTIVE_THRESH_MEAN_C", "ADAPTIVE_THRESH_GAUSSIAN_C", "medianBlur", "bilateralFilter", "moments", "erode", "dilate", "MORPH_ERODE", "MORPH_DILATE", "threshold", "THRESH_BINARY", "THRESH_BINARY_INV", "THRESH_TRUNC", "THRESH_TOZERO", "THRESH_TOZERO_INV",
            "filter2D", "filter2DBatch", "cvtColorFilter2DBatch", "sepFilter2D", "Sobel", "Scharr", "boxFilter", "blur",
@@ -1614,6 +1614,115 @@ def HoughLinesAccumulator(image, rho, theta, min_theta=0, max_theta=math.pi):
         ptr = out.ctypes.data
     bind_stream(s)
     _lib.check(L.mi355cv_houghLinesAccum(*args, _vp(ptr), shape[1] * 4, ctypes.byref(na), ctypes.byref(nr)), "houghLinesAccum")
+    return out
+
+
+# ----------------------------------------------------------------------------- circle transform, HOUGH_GRADIENT (no HAL hook: mi355cv_houghCircles* )
+HOUGH_STANDARD, HOUGH_PROBABILISTIC, HOUGH_MULTI_SCALE, HOUGH_GRADIENT, HOUGH_GRADIENT_ALT = 0, 1, 2, 3, 4       # cv::HoughModes
+_HOUGH_MAX_CIRCLES = 1024                    # the capacity of the first call; a count that reaches the capacity gets another call with twice the capacity
+
+
+def _houghcircles_args(name, method, dp, minDist, param1, param2, maxCircles):
+    if method not in (HOUGH_STANDARD, HOUGH_PROBABILISTIC, HOUGH_MULTI_SCALE, HOUGH_GRADIENT, HOUGH_GRADIENT_ALT):
+        raise ValueError(name + ": unknown method")
+    if not dp > 0 or not minDist > 0 or not param1 > 0 or not param2 > 0:              # CV_Assert(dp > 0 && minDist > 0 && param1 > 0 && param2 > 0)
+        raise ValueError(name + ": dp, minDist, param1 and param2 must be positive")
+    if maxCircles is not None and int(maxCircles) < 1:
+        raise ValueError(name + ": maxCircles must be at least 1")
+
+
+def _houghcircles_8u(name, s):
+    if s.depth != CV_8U or s.cn != 1 or getattr(s.obj, "ndim", 2) != 2:
+        raise ValueError(name + ": the image must be a 2-D CV_8UC1 image")            # CV_Assert(!_image.empty() && _image.type() == CV_8UC1)
+
+
+def _houghcircles_planes(name, edges, dx, dy):
+    e, x, y = Img(edges), Img(dx), Img(dy)
+    _houghcircles_8u(name, e)
+    for g in (x, y):
+        if g.depth != CV_16S or g.cn != 1 or (g.h, g.w) != (e.h, e.w) or g.device != e.device or getattr(g.obj, "ndim", 2) != 2:
+            raise ValueError(name + ": dx and dy must be CV_16SC1 of the edge map's size, where the edge map lives")
+    if x.step != y.step:
+        raise ValueError(name + ": dx and dy must have the same pitch")
+    return e, x, y
+
+
+def _houghcircles_loop(name, ref, cn, maxCircles, call):
+    """call(ptr, cap, n) with growing capacity until the count stays below it (or once, with the caller's own maxCircles)"""
+    cap = int(maxCircles) if maxCircles is not None else _HOUGH_MAX_CIRCLES
+    top = _lib.limit("houghcircles_max_circles")
+    n = ctypes.c_int(0)
+    while True:
+        out = _hough_alloc(ref, (cap, cn))
+        ptr = out.data_ptr() if torch is not None and isinstance(out, torch.Tensor) else out.ctypes.data
+        _lib.check(call(_vp(ptr), cap, ctypes.byref(n)), name)
+        if n.value < cap or maxCircles is not None or cap >= top:
+            break
+        cap = min(2 * cap, top)                                                       # count == capacity: there may be more
+    return out[:n.value]
+
+
+def HoughCircles(image, method, dp, minDist, param1=100, param2=100, minRadius=0, maxRadius=0, maxCircles=None, withVotes=False):
+    """cv::HoughCircles with HOUGH_GRADIENT (hough.cpp HoughCirclesGradient; no HAL hook) -> mi355cv_houghCircles: CV_8UC1 [H,W] -> float32 [N,3] of (x, y, radius), or
+    [N,4] with the votes, strongest first, where the image lives.  maxRadius < 0 returns centres only (radius 0, votes of the centre).  maxCircles caps N; without it
+    the call repeats with a doubled capacity until every circle fits.  Other methods (HOUGH_GRADIENT_ALT) are declined (NotImplementedError)."""
+    s = Img(image)
+    _houghcircles_8u("HoughCircles", s)
+    _houghcircles_args("HoughCircles", method, dp, minDist, param1, param2, maxCircles)
+    cn = 4 if withVotes else 3
+    bind_stream(s)
+    return _houghcircles_loop("houghCircles", image, cn, maxCircles, lambda ptr, cap, n: L.mi355cv_houghCircles(
+        _vp(s.ptr), s.step, s.w, s.h, ptr, cn, cap, int(method), float(dp), float(minDist), float(param1), float(param2), int(minRadius), int(maxRadius), n))
+
+
+def HoughCirclesBatch(frames, method, dp, minDist, param1=100, param2=100, minRadius=0, maxRadius=0, maxCircles=_HOUGH_MAX_CIRCLES, withVotes=False):
+    """cv::HoughCircles over [N,H,W] frames of CV_8UC1 -> (counts: list of N ints, circles float32 [N,maxCircles,cn]); the first counts[f] rows of circles[f] are
+    written (the rest is left as allocated), and counts[f] == maxCircles means frame f may hold more."""
+    n, s0 = _batch_geom(frames)
+    if frames.dim() != 3:
+        raise ValueError("HoughCirclesBatch: frames [N, H, W] of one channel")
+    _houghcircles_8u("HoughCirclesBatch", s0)
+    _houghcircles_args("HoughCirclesBatch", method, dp, minDist, param1, param2, maxCircles)
+    cn, cap = (4 if withVotes else 3), int(maxCircles)
+    out = _batch_alloc(frames, (n, cap, cn), torch.float32)
+    bind_stream(s0)
+    counts = (ctypes.c_int * n)()
+    rc = L.mi355cv_houghCirclesBatch(_vp(s0.ptr), s0.step, int(frames.stride(0)) * s0.esz, s0.w, s0.h, _vp(out.data_ptr()), cn, cap, cap * cn * 4, n, int(method), float(dp),
+                                     float(minDist), float(param1), float(param2), int(minRadius), int(maxRadius), counts)
+    _lib.check(rc, "houghCirclesBatch")
+    return list(counts), out
+
+
+def HoughCirclesGradient(edges, dx, dy, dp, minDist, param2=100, minRadius=0, maxRadius=0, maxCircles=None, withVotes=False):
+    """the circle transform from a given edge map (CV_8UC1, non-zero = edge) and its CV_16SC1 gradient planes -> mi355cv_houghCirclesGradient; HoughCircles is this
+    after its own edge stage (Sobel 3 x 3 and Canny with thresholds max(1, param1 / 2) and param1)."""
+    e, x, y = _houghcircles_planes("HoughCirclesGradient", edges, dx, dy)
+    _houghcircles_args("HoughCirclesGradient", HOUGH_GRADIENT, dp, minDist, 1, param2, maxCircles)
+    cn = 4 if withVotes else 3
+    bind_stream(e, x, y)
+    return _houghcircles_loop("houghCirclesGradient", edges, cn, maxCircles, lambda ptr, cap, n: L.mi355cv_houghCirclesGradient(
+        _vp(e.ptr), e.step, _vp(x.ptr), _vp(y.ptr), x.step, e.w, e.h, ptr, cn, cap, HOUGH_GRADIENT, float(dp), float(minDist), 1.0, float(param2), int(minRadius),
+        int(maxRadius), n))
+
+
+def HoughCirclesAccumulator(edges, dx, dy, dp, minRadius=0, maxRadius=0):
+    """the centre accumulator HoughCircles takes its centres from -> int32 [arows + 2, acols + 2] where the edge map lives (mi355cv_houghCirclesAccum); the cell
+    (y2, x2) of a ray's step is row y2, column x2"""
+    e, x, y = _houghcircles_planes("HoughCirclesAccumulator", edges, dx, dy)
+    if not dp > 0:
+        raise ValueError("HoughCirclesAccumulator: dp must be positive")
+    ar, ac = ctypes.c_int(0), ctypes.c_int(0)
+    args = (_vp(e.ptr), e.step, _vp(x.ptr), _vp(y.ptr), x.step, e.w, e.h, float(dp), int(minRadius), int(maxRadius))
+    _lib.check(L.mi355cv_houghCirclesAccum(*args, None, 0, ctypes.byref(ar), ctypes.byref(ac)), "houghCirclesAccum")
+    shape = (ar.value + 2, ac.value + 2)
+    if torch is not None and isinstance(edges, torch.Tensor):
+        out = torch.empty(shape, dtype=torch.int32, device=edges.device)
+        ptr = out.data_ptr()
+    else:
+        out = np.empty(shape, dtype=np.int32)
+        ptr = out.ctypes.data
+    bind_stream(e, x, y)
+    _lib.check(L.mi355cv_houghCirclesAccum(*args, _vp(ptr), shape[1] * 4, ctypes.byref(ar), ctypes.byref(ac)), "houghCirclesAccum")
     return out
 
 
