@@ -7,15 +7,17 @@
 // For the sigma==0 binomial tables (smooth.dispatch.cpp:89-145) this collapses to
 //   5x5: (sum w_i w_j p + 128) >> 8,  w = 1 4 6 4 1         3x3: (sum w_i w_j p + 8) >> 4,  w = 1 2 1
 //
-// Two kernels:
-//  * k_binomial_roll<KS,CN>: the hot kernel.  HBM-bound (2 B/pixel algorithmic).  One lane owns
-//    16 consecutive bytes of a row (one global_load_dwordx4, one global_store_dwordx4) and walks
-//    DOWN the image keeping the last KS horizontally-filtered rows in registers (packed 2xu16 per
-//    VGPR), so every source byte is fetched once per vertical segment and there is no LDS round
-//    trip.  The +-R*cn neighbour bytes come from the adjacent lanes (ds_bpermute crossbar), from
-//    a 4-byte side load at the wave edges, or from borderInterpolate at the image edges.
-//  * k_sepfixed_generic: any taps / alignment / margins / tiny images.  One thread per output
-//    byte, straight from the formula above.  Correctness path, not a fast path.
+// Every CV_8U entry (mi355cv_gaussianBlurBinomial, mi355cv_gaussianBlur, mi355cv_sepSmoothFixedU8 and the two batch entries) ends in runSmooth: declines and staging,
+// one SmoothCall, then the paths in this order -- the first that takes the call serves it:
+//   binomialRoll     k_binomial_roll2 (here): sigma = 0, 3 / 5 taps, whole 16-byte aligned frames.  k_binomial_roll for gauss_variant <= 1 and BORDER_WRAP
+//   sepmxLong        k_sepmx (sepmx.hip): 7 taps or more on either axis, both passes on the matrix cores, margins included
+//   seprollWhole     k_sep_roll<FixedSmooth> (seproll.hip): any-sigma taps up to 9 on the rolling skeleton, whole frames
+//   seprollWindow    the same kernel on a window with real pixels around it (one frame)
+//   sepmxShort       k_sepmx for the short kernels the skeleton did not take
+//   seplongQ88       k_seplong<3> (seplong.hip): any length and geometry, taps that sum to at most 256 per axis
+//   sepfixedGeneric  k_sepfixed_generic (here): up to 33 taps, one thread per output byte straight from the formula above.  Correctness path, not a fast path
+// MI355CV_SMOOTH_GENERIC=1 switches every path but the first and the last off, MI355CV_SEPMX=0 the two sepmx ones.
+// Also here: the CV_16U sigma = 0 case (runBinom16: k_sep_roll<Binom16> or k_binom16_direct), the tap generators' exports and mi355cv_setParam.
 #include "rt.h"
 #include "gausskernel.h"
 #include "seproll.h"
@@ -569,66 +571,35 @@ __global__ __launch_bounds__(256, WPS) void k_binomial_roll2(
     }
 }
 
-// ---------------------------------------------------------------------------------- copy probe
-// 16 B/lane streaming copy with the same launch geometry as the rolling kernel's traffic (1 read :
-// 1 write): the measured-copy denominator BASELINE.md asks for next to the 8 TB/s spec figure.
-template <bool NT>
-__global__ __launch_bounds__(256) void k_copy16(const uint4* __restrict__ s, uint4* __restrict__ d, size_t n16, int perThread)
-{
-    typedef uint32_t u32x4 __attribute__((ext_vector_type(4)));
-    size_t base = ((size_t)blockIdx.x * perThread) * 256 + threadIdx.x;
-#pragma unroll 4
-    for (int i = 0; i < perThread; i++) {
-        size_t j = base + (size_t)i * 256;
-        if (j < n16) {
-            uint4 v = s[j];
-            u32x4 ov = {v.x, v.y, v.z, v.w};
-            if constexpr (NT) __builtin_nontemporal_store(ov, reinterpret_cast<u32x4*>(d + j));
-            else d[j] = v;
-        }
-    }
-}
-
-// column-walk copy probe: the rolling kernel's work decomposition and access order (wave = 1 KB wide strip
-// walking down `segRows` rows) with the arithmetic removed -- separates access-pattern effects from ALU/wait effects
-template <int UNROLL>
-__global__ __launch_bounds__(256) void k_copy_colwalk(const uchar* __restrict__ src, uchar* __restrict__ dst, size_t step, size_t frame,
-                                                      int H, int nchunks, int nstrips, int segRows, int nseg, int nframes)
-{
-    const int lane = threadIdx.x & 63;
-    const int wid = __builtin_amdgcn_readfirstlane((int)(blockIdx.x * 4 + (threadIdx.x >> 6)));
-    const int strip = wid % nstrips, t0 = wid / nstrips, seg = t0 % nseg, fr = t0 / nseg;
-    if (fr >= nframes) return;
-    const int c = strip * 64 + lane;
-    if (c >= nchunks) return;
-    const int y0 = seg * segRows, y1 = min(H, y0 + segRows);
-    const uchar* s = src + (size_t)fr * frame + 16 * (size_t)c;
-    uchar* d = dst + (size_t)fr * frame + 16 * (size_t)c;
-    for (int y = y0; y < y1; y += UNROLL) {
-        uint4 v[UNROLL];
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) v[u] = *reinterpret_cast<const uint4*>(s + (size_t)min(y + u, y1 - 1) * step);
-#pragma unroll
-        for (int u = 0; u < UNROLL; u++) if (y + u < y1) *reinterpret_cast<uint4*>(d + (size_t)(y + u) * step) = v[u];
-    }
-}
-
 // ---------------------------------------------------------------------------------- host side
 
 bool aligned16(const void* p, size_t step) { return (((uintptr_t)p | step) & 15) == 0; }
 
-int envInt(const char* n, int d) { const char* v = getenv(n); return v ? atoi(v) : d; }
-
 int& tuneSeg() { static int v = envInt("MI355CV_GAUSS_SEG", 0); return v; }
 constexpr int kGaussVariantDefault = 6;
-int& tuneVariant() { static int v = envInt("MI355CV_GAUSS_VARIANT", kGaussVariantDefault); return v; }   // 1: k_binomial_roll, 2: roll2, 3: roll2 + nt stores, 4: 3 with the edge halos as selects instead of branches, 5: 3 at 6 waves / SIMD, 6: 3 with the load ring kept in flight (RING)
+int& tuneVariant() { static int v = envInt("MI355CV_GAUSS_VARIANT", kGaussVariantDefault); return v; }   // 1: k_binomial_roll, 2 .. 6: the rows of launchRoll2
 
 int& tuneAlt() { static int v = envInt("MI355CV_GAUSS_ALT", 1); return v; }   // 1: alternate walking direction of vertical neighbours
 int& tuneLaunchWaves() { static int v = envInt("MI355CV_GAUSS_LAUNCH_WAVES", 393216); return v; }   // work items per launch of a batch (0: one launch)
 
+// A row of launchRoll2's table, one per gauss_variant from 2 on: the instance of k_binomial_roll2 it launches and the template arguments its note reports, both written
+// from the SAME arguments of roll2Row, so that a variant cannot launch one instance and report another
+typedef void (*Roll2Kernel)(const uchar*, size_t, size_t, uchar*, size_t, size_t, int, int, int, int, int, int, int, int, int);
+struct Roll2Variant { Roll2Kernel kernel; bool nt; int wps; bool eb, ring; };
+template <int KS, int CN, bool NT, int WPS, bool EB, bool RING>
+constexpr Roll2Variant roll2Row() { return {k_binomial_roll2<KS, CN, NT, false, WPS, EB, RING>, NT, WPS, EB, RING}; }
+
 template <int KS, int CN>
 void launchRoll2(const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nframes, int W, int H, int border, hipStream_t st, int nt)
 {
+    static const Roll2Variant rows[] = {
+        roll2Row<KS, CN, false, 4, true, false>(),      // 2
+        roll2Row<KS, CN, true, 4, true, false>(),       // 3: nt stores
+        roll2Row<KS, CN, true, 4, false, false>(),      // 4: 3 with the edge halos as selects instead of branches
+        roll2Row<KS, CN, true, 6, true, false>(),       // 5: 3 at 6 waves / SIMD
+        roll2Row<KS, CN, true, 4, true, true>(),        // 6 and beyond: 3 with the load ring kept in flight (RING)
+    };
+    const Roll2Variant& v = rows[nt < 4 ? nt : 4];
     const int nchunks = W * CN / 16;
     const int nstrips = divUp(nchunks, 64);
     int seg = tuneSeg();
@@ -660,18 +631,14 @@ void launchRoll2(const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size
     if (chunk < 1) chunk = 1;
     if (chunk > nframes) chunk = nframes;
     const int nlaunch = (int)((nframes + chunk - 1) / chunk);
-    noteKernel("k_binomial_roll2<%d,%d,%s,false,%d,%s%s> grid=%u x256 seg=%d rows alt=%d, %d launch(es) of <= %lld frames", KS, CN, nt >= 1 ? "true" : "false", nt == 3 ? 6 : 4,
-               nt == 2 ? "false" : "true", nt == 4 ? ",true" : "", (unsigned)((perFrame * chunk + 3) / 4), seg, tuneAlt(), nlaunch, chunk);
+    noteKernel("k_binomial_roll2<%d,%d,%s,false,%d,%s%s> grid=%u x256 seg=%d rows alt=%d, %d launch(es) of <= %lld frames", KS, CN, v.nt ? "true" : "false", v.wps,
+               v.eb ? "true" : "false", v.ring ? ",true" : "", (unsigned)((perFrame * chunk + 3) / 4), seg, tuneAlt(), nlaunch, chunk);
     for (long long f0 = 0; f0 < nframes; f0 += chunk) {
         const int nf = (int)(nframes - f0 < chunk ? nframes - f0 : chunk);
         const uchar* sp = s + (size_t)f0 * sf;
         uchar* dp = d + (size_t)f0 * df;
         dim3 grid((unsigned)((perFrame * nf + 3) / 4));
-        if (nt >= 4)      hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4, true, true>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
-        else if (nt == 3) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 6>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
-        else if (nt == 2) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4, false>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
-        else if (nt == 1) hipLaunchKernelGGL((k_binomial_roll2<KS, CN, true, false, 4>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
-        else              hipLaunchKernelGGL((k_binomial_roll2<KS, CN, false, false, 4>), grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
+        hipLaunchKernelGGL(v.kernel, grid, dim3(256), 0, st, sp, ss, sf, dp, ds, df, W, H, nchunks, nstrips, seg, nseg, nf, border, tuneAlt());
     }
 }
 
@@ -708,16 +675,89 @@ bool rollEligible(const uchar* s, size_t ss, size_t sf, const uchar* d, size_t d
     if (!aligned16(s, ss) || !aligned16(d, ds) || (sf & 15) || (df & 15)) return false;
     if ((W * cn) % 16 != 0) return false;
     if (H < 1) return false;
-    return true;
+    return true;                                 // W * cn is a positive multiple of 16 with cn <= 4, so W >= 4: no image here is narrower than a kernel's radius
 }
 
-// from this many taps on (either axis) the matrix-core kernel goes first: it runs at the same speed for 3 .. 33 taps (3.8 us per 4K CV_8UC1 frame), the register-rolling
-// kernel slows down with every tap (5 / 7 / 9 taps: 3.5 / 4.3 / 5.5 us, three channels 9 taps 24 us against 11; profiles/r06_sepmx.txt)
-static int sepmxMinTaps()
-{
-    static const int v = std::getenv("MI355CV_SEPMX_MIN_TAPS") ? atoi(std::getenv("MI355CV_SEPMX_MIN_TAPS")) : 7;
-    return v;
-}
+// One resolved call of the Q8.8 smoothing of CV_8U images, as runSmooth hands it to the paths below: the frames where the kernels find them, the geometry with the real
+// pixels around it, the taps, the two switches.  Every path is named after its kernel; it answers NEXT_PATH when the call is not its to serve and MI355CV_OK when it
+// has launched.  runSmooth tries them in the order of its list.
+struct SmoothCall {
+    Stager& stg; hipStream_t st;
+    const uchar* dsrc; size_t dss, sframe; uchar* ddst; size_t dds, dframe;        // device pointers, steps and frame strides (0 for one frame)
+    int nframes, W, H, cn, mL, mT, mR, mB;                                          // m*: real pixels around the image
+    const uint16_t* kx; int nx; const uint16_t* ky; int ny; int border; bool binomial;
+    bool generic, sepmxOff;          // MI355CV_SMOOTH_GENERIC is set, MI355CV_SEPMX=0: read once per CALL, not per process (tools/seplong_bench.py flips the former between calls)
+
+    bool noMargins() const { return !(mL | mT | mR | mB); }
+
+    template <int KS, int CN> void roll()
+    {
+        if (tuneVariant() <= 1 || border == B_WRAP) launchRoll<KS, CN>(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, border, st);
+        else launchRoll2<KS, CN>(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, border, st, tuneVariant() - 2);
+    }
+    int binomialRoll()                                                              // k_binomial_roll2; k_binomial_roll for gauss_variant <= 1 and BORDER_WRAP
+    {
+        // sigma = 0, 3 or 5 taps, whole aligned frames.  MI355CV_SMOOTH_GENERIC does not switch this path off.
+        if (!(binomial && noMargins() && rollEligible(dsrc, dss, sframe, ddst, dds, dframe, W, H, cn, nx) && nx == ny)) return NEXT_PATH;
+        static void (SmoothCall::* const byKsizeCn[2][4])() = {
+            {&SmoothCall::roll<3, 1>, &SmoothCall::roll<3, 2>, &SmoothCall::roll<3, 3>, &SmoothCall::roll<3, 4>},
+            {&SmoothCall::roll<5, 1>, &SmoothCall::roll<5, 2>, &SmoothCall::roll<5, 3>, &SmoothCall::roll<5, 4>}};
+        (this->*byKsizeCn[nx == 5][cn - 1])();
+        return MI355CV_OK;
+    }
+    // k_sepmx: both passes on the matrix cores (sepmx.hip), any geometry, margins included -- taps that fit int8 and span at most five 32-byte K steps.  It stands in the
+    // list twice: before the rolling skeleton from sepmxMinTaps taps on (either axis), after it for the short kernels the skeleton did not take (two channels, ...)
+    int sepmx(bool longTaps)
+    {
+        // from this many taps on the matrix-core kernel goes first: it runs at the same speed for 3 .. 33 taps (3.8 us per 4K CV_8UC1 frame), the register-rolling
+        // kernel slows down with every tap (5 / 7 / 9 taps: 3.5 / 4.3 / 5.5 us, three channels 9 taps 24 us against 11; profiles/r06_sepmx.txt)
+        static const int sepmxMinTaps = envInt("MI355CV_SEPMX_MIN_TAPS", 7);
+        if (generic || sepmxOff || (std::max(nx, ny) >= sepmxMinTaps) != longTaps) return NEXT_PATH;
+        return sepmxRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, mL + W + mR, mT + H + mB, mL, mT, border, kx, nx, nx / 2, ky, ny, ny / 2, st) ? MI355CV_OK : NEXT_PATH;
+    }
+    int sepmxLong() { return sepmx(true); }
+    int sepmxShort() { return sepmx(false); }
+    int seprollWhole()                                                              // k_sep_roll<FixedSmooth>: any-sigma Q8.8 taps (<= 9) on the rolling skeleton
+    {
+        if (!(noMargins() && !generic)) return NEXT_PATH;
+        return seprollFixedSmooth(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, kx, nx, ky, ny, border, st) ? MI355CV_OK : NEXT_PATH;
+    }
+    int seprollWindow()                                                             // k_sep_roll<FixedSmooth> on the parent's geometry, storing the window
+    {
+        // a submatrix with real pixels around it (cv_hal_gaussianBlurBinomial's margins)
+        if (!(!noMargins() && nframes == 1 && !generic)) return NEXT_PATH;
+        const Roi roi = {mL + W + mR, mT + H + mB, mL, mT};
+        return seprollFixedSmooth(dsrc, dss, 0, ddst, dds, 0, 1, W, H, cn, kx, nx, ky, ny, border, st, &roi) ? MI355CV_OK : NEXT_PATH;
+    }
+    int seplongQ88()                                                                // k_seplong<3>: the LDS-ring kernel in its Q8.8 mode
+    {
+        // any length, any geometry, margins included -- when no ufixedpoint16 / ufixedpoint32 sum can saturate
+        if (generic) return NEXT_PATH;
+        unsigned sx = 0, sy = 0;
+        for (int i = 0; i < nx; i++) sx += kx[i];
+        for (int i = 0; i < ny; i++) sy += ky[i];
+        if (sx > 256 || sy > 256) return NEXT_PATH;
+        std::vector<int> ix(kx, kx + nx), iy(ky, ky + ny);
+        const SepLongTaps t = {nullptr, nullptr, ix.data(), iy.data(), nx, ny, nx / 2, ny / 2, 3, 0, 0.f, 0};
+        return seplongRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, MI355CV_8U, MI355CV_8U, mL + W + mR, mT + H + mB, mL, mT, border, t, st) ? MI355CV_OK : NEXT_PATH;
+    }
+    int sepfixedGeneric()                                                           // k_sepfixed_generic: takes the rest
+    {
+        // taps that can saturate the reference's fixed-point types (never cv::GaussianBlur's own: they sum to 256), or MI355CV_SMOOTH_GENERIC=1: one thread per byte, <= 33 taps
+        MI355_DECLINE_IF((nx > 33 || ny > 33) && nframes > MAX_GRID_FRAMES);         // sepmxRun and seplongRun take up to 65535 frames, this kernel up to 33 taps
+        if (nx > 33 || ny > 33) return MI355_DECLINED("Q8.8 taps that sum beyond 256 with more than 33 of them");
+        FixedTaps t;
+        t.nx = nx; t.ny = ny;
+        for (int i = 0; i < 33; i++) { t.kx[i] = i < nx ? kx[i] : 0; t.ky[i] = i < ny ? ky[i] : 0; }
+        for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_FRAMES) {                      // the frame is blockIdx.z
+            dim3 grid(divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes - f0));
+            hipLaunchKernelGGL(k_sepfixed_generic, grid, dim3(256), 0, st, dsrc + (size_t)f0 * sframe, dss, sframe, ddst + (size_t)f0 * dframe, dds, dframe,
+                               W, H, cn, mL, mT, mR, mB, border, t);
+        }
+        noteKernel("k_sepfixed_generic grid=%dx%dx%d x256, %d launch(es)", divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes), divUp(nframes, MAX_GRID_FRAMES));
+        return MI355CV_OK;
+    }
+};
 
 int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, uchar* dst, size_t dstep, size_t dframe,
               int nframes, int W, int H, int cn, int mL, int mT, int mR, int mB,
@@ -749,50 +789,15 @@ int runSmooth(const char* entry, const uchar* src, size_t sstep, size_t sframe, 
         if (hostSrc || !isDevicePtr(dst)) return setError(MI355CV_NOT_IMPLEMENTED, "%s: batch entry needs device-resident frames", entry);
         dsrc = src; ddst = dst; dss = sstep; dds = dstep;
     }
-    hipStream_t st = stream();
-    const bool noMargins = !(mL | mT | mR | mB);
-    if (binomial && noMargins && rollEligible(dsrc, dss, sframe, ddst, dds, dframe, W, H, cn, nx) && nx == ny) {
-#define ROLL(KS_, CN_) do { if (tuneVariant() <= 1 || border == B_WRAP || W <= KS_ / 2) launchRoll<KS_, CN_>(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, border, st); \
-                            else launchRoll2<KS_, CN_>(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, border, st, tuneVariant() - 2); } while (0)
-        if (nx == 5) { switch (cn) { case 1: ROLL(5, 1); break; case 2: ROLL(5, 2); break; case 3: ROLL(5, 3); break; default: ROLL(5, 4); } }
-        else         { switch (cn) { case 1: ROLL(3, 1); break; case 2: ROLL(3, 2); break; case 3: ROLL(3, 3); break; default: ROLL(3, 4); } }
-#undef ROLL
-    } else if (std::getenv("MI355CV_SMOOTH_GENERIC") == nullptr && std::max(nx, ny) >= sepmxMinTaps() && !(std::getenv("MI355CV_SEPMX") && std::getenv("MI355CV_SEPMX")[0] == '0') &&
-               sepmxRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, mL + W + mR, mT + H + mB, mL, mT, border, kx, nx, nx / 2, ky, ny, ny / 2, st)) {
-        // 7 taps or more on either axis, any geometry, margins included: both passes on the matrix cores (sepmx.hip) -- taps that fit int8 and span at most five 32-byte K steps
-    } else if (noMargins && std::getenv("MI355CV_SMOOTH_GENERIC") == nullptr &&
-               seprollFixedSmooth(dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, kx, nx, ky, ny, border, st)) {
-        // any-sigma Q8.8 taps (<= 9) on the rolling skeleton
-    } else if (!noMargins && nframes == 1 && std::getenv("MI355CV_SMOOTH_GENERIC") == nullptr && [&] {
-                   // a submatrix with real pixels around it (cv_hal_gaussianBlurBinomial's margins): the rolling kernel on the parent's geometry, storing the window
-                   const Roi roi = {mL + W + mR, mT + H + mB, mL, mT};
-                   return seprollFixedSmooth(dsrc, dss, 0, ddst, dds, 0, 1, W, H, cn, kx, nx, ky, ny, border, st, &roi); }()) {
-    } else if (std::getenv("MI355CV_SMOOTH_GENERIC") == nullptr && std::max(nx, ny) < sepmxMinTaps() && !(std::getenv("MI355CV_SEPMX") && std::getenv("MI355CV_SEPMX")[0] == '0') &&
-               sepmxRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, mL + W + mR, mT + H + mB, mL, mT, border, kx, nx, nx / 2, ky, ny, ny / 2, st)) {
-        // short kernels the rolling skeleton did not take (two channels, ...)
-    } else if (std::getenv("MI355CV_SMOOTH_GENERIC") == nullptr && [&] {
-                   // any length, any geometry, margins included: the LDS-ring kernel in its Q8.8 mode -- when no ufixedpoint16 / ufixedpoint32 sum can saturate
-                   unsigned sx = 0, sy = 0;
-                   for (int i = 0; i < nx; i++) sx += kx[i];
-                   for (int i = 0; i < ny; i++) sy += ky[i];
-                   if (sx > 256 || sy > 256) return false;
-                   std::vector<int> ix(kx, kx + nx), iy(ky, ky + ny);
-                   const SepLongTaps t = {nullptr, nullptr, ix.data(), iy.data(), nx, ny, nx / 2, ny / 2, 3, 0, 0.f, 0};
-                   return seplongRun(stg, dsrc, dss, sframe, ddst, dds, dframe, nframes, W, H, cn, MI355CV_8U, MI355CV_8U, mL + W + mR, mT + H + mB, mL, mT, border, t, st); }()) {
-    } else {
-        // taps that can saturate the reference's fixed-point types (never cv::GaussianBlur's own: they sum to 256), or MI355CV_SMOOTH_GENERIC=1: one thread per byte, <= 33 taps
-        MI355_DECLINE_IF((nx > 33 || ny > 33) && nframes > MAX_GRID_FRAMES);         // sepmxRun and seplongRun take up to 65535 frames, this kernel up to 33 taps
-        if (nx > 33 || ny > 33) return MI355_DECLINED("Q8.8 taps that sum beyond 256 with more than 33 of them");
-        FixedTaps t;
-        t.nx = nx; t.ny = ny;
-        for (int i = 0; i < 33; i++) { t.kx[i] = i < nx ? kx[i] : 0; t.ky[i] = i < ny ? ky[i] : 0; }
-        for (int f0 = 0; f0 < nframes; f0 += MAX_GRID_FRAMES) {                      // the frame is blockIdx.z
-            dim3 grid(divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes - f0));
-            hipLaunchKernelGGL(k_sepfixed_generic, grid, dim3(256), 0, st, dsrc + (size_t)f0 * sframe, dss, sframe, ddst + (size_t)f0 * dframe, dds, dframe,
-                               W, H, cn, mL, mT, mR, mB, border, t);
-        }
-        noteKernel("k_sepfixed_generic grid=%dx%dx%d x256, %d launch(es)", divUp(W * cn, 64), divUp(H, 4), std::min(MAX_GRID_FRAMES, nframes), divUp(nframes, MAX_GRID_FRAMES));
-    }
+    const char* sepmxEnv = std::getenv("MI355CV_SEPMX");
+    SmoothCall c = {stg, stream(), dsrc, dss, nframes > 1 ? sframe : 0, ddst, dds, nframes > 1 ? dframe : 0, nframes, W, H, cn, mL, mT, mR, mB, kx, nx, ky, ny, border, binomial,
+                    std::getenv("MI355CV_SMOOTH_GENERIC") != nullptr, sepmxEnv && sepmxEnv[0] == '0'};
+    // the dispatch rule: the first path that takes the call serves it; sepfixedGeneric takes or declines whatever reaches it
+    static int (SmoothCall::* const paths[])() = {&SmoothCall::binomialRoll, &SmoothCall::sepmxLong, &SmoothCall::seprollWhole, &SmoothCall::seprollWindow,
+                                                  &SmoothCall::sepmxShort, &SmoothCall::seplongQ88, &SmoothCall::sepfixedGeneric};
+    int rc = NEXT_PATH;
+    for (auto path : paths) if ((rc = (c.*path)()) != NEXT_PATH) break;
+    if (rc != MI355CV_OK) return rc;
     return stg.finish(entry);
 }
 
@@ -830,9 +835,11 @@ __global__ __launch_bounds__(256) void k_binom16_direct(const uchar* __restrict_
 
 int runBinom16(const char* entry, const uchar* src, size_t sstep, uchar* dst, size_t dstep, int W, int H, int cn, int mL, int mT, int mR, int mB, int ksize, int border)
 {
-    if (disabled() || W <= 0 || H <= 0 || cn < 1 || cn > 4 || (ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9) || border < 0 || border > B_REFLECT_101 ||
-        mL < 0 || mT < 0 || mR < 0 || mB < 0 || ((sstep | dstep | (uintptr_t)src | (uintptr_t)dst) & 1))
-        return MI355_DECLINED("disabled() || W <= 0 || H <= 0 || cn < 1 || cn > 4 || ksize not in {3, 5, 7, 9} || border outside CONSTANT .. REFLECT_101 || negative margins || odd pointers / steps");
+    MI355_DECLINE_IF(disabled());
+    MI355_DECLINE_IF(W <= 0 || H <= 0 || cn < 1 || cn > 4 || mL < 0 || mT < 0 || mR < 0 || mB < 0);
+    MI355_DECLINE_IF(ksize != 3 && ksize != 5 && ksize != 7 && ksize != 9);
+    MI355_DECLINE_IF(border < 0 || border > B_REFLECT_101);
+    MI355_DECLINE_IF((sstep | dstep | (uintptr_t)src | (uintptr_t)dst) & 1);
     Stager stg;                                  // first: a declined call must also put the host's device back (~Stager)
     MI355_DECLINE_IF(!ensureDevice());
     const bool hostSrc = !isDevicePtr(src);
@@ -871,6 +878,30 @@ const uint16_t* binomTaps(size_t k)
     return nullptr;
 }
 
+// the taps are the sigma = 0 table of 3 or 5 on both axes: what binomialRoll serves
+bool isBinomial(const uint16_t* kx, size_t nx, const uint16_t* ky, size_t ny)
+{
+    if (nx != ny || (nx != 3 && nx != 5)) return false;
+    const uint16_t* b = binomTaps(nx);
+    for (size_t i = 0; i < nx; i++) if (kx[i] != b[i] || ky[i] != b[i]) return false;
+    return true;
+}
+
+// cv::GaussianBlur's Q8.8 taps for CV_8U (getGaussianKernelFixedPoint_ED) from a kernel size and the two sigmas as the hooks get them
+struct GaussTaps { uint16_t kx[lim::GAUSS8U_MAX_KSIZE], ky[lim::GAUSS8U_MAX_KSIZE]; bool binom; };
+int gaussTapsQ88(size_t ksize_width, size_t ksize_height, double sigmaX, double sigmaY, GaussTaps& t)
+{
+    MI355_DECLINE_IF(ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE);
+    if (sigmaY <= 0) sigmaY = sigmaX;
+    std::vector<int64_t> qx, qy;
+    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx));         // (also: a size of 0, an even size)
+    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy));
+    for (size_t i = 0; i < ksize_width; i++) { MI355_DECLINE_IF(qx[i] < 0 || qx[i] > 65535); t.kx[i] = (uint16_t)qx[i]; }
+    for (size_t i = 0; i < ksize_height; i++) { MI355_DECLINE_IF(qy[i] < 0 || qy[i] > 65535); t.ky[i] = (uint16_t)qy[i]; }
+    t.binom = isBinomial(t.kx, ksize_width, t.ky, ksize_height);
+    return MI355CV_OK;
+}
+
 } // namespace
 
 extern "C" {
@@ -900,7 +931,7 @@ static int gaussBatchFromHost(const uchar* src, size_t sstep, size_t sframe, uch
 {
     const HostBatch hb = {src, sstep, sframe, (size_t)W * cn, H, dst, dstep, dframe, (size_t)W * cn, H, nframes};
     return runHostBatch("gaussianBlurBinomialBatch", hb, [&](const uchar* s, size_t ss, size_t sf, uchar* d, size_t ds, size_t df, int nf) {
-        return runSmooth("gaussianBlurBinomialBatch", s, ss, nf > 1 ? sf : 0, d, ds, nf > 1 ? df : 0, nf, W, H, cn, 0, 0, 0, 0, k, ks, k, ks, border, true);
+        return runSmooth("gaussianBlurBinomialBatch", s, ss, sf, d, ds, df, nf, W, H, cn, 0, 0, 0, 0, k, ks, k, ks, border, true);
     });
 }
 
@@ -915,9 +946,6 @@ MI355CV_API int mi355cv_gaussianBlurBinomialBatch(const uchar* src_data, size_t 
     if (nframes > 1 && width > 0 && height > 0 && cn >= 1 && cn <= 4 && hostBatchEligible(src_data, dst_data, nframes))
         return gaussBatchFromHost(src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, cn, k, (int)ksize,
                                   border_type & ~MI355CV_BORDER_ISOLATED);
-    if (nframes == 1)
-        return runSmooth("gaussianBlurBinomialBatch", src_data, src_step, 0, dst_data, dst_step, 0, 1, width, height, cn,
-                         0, 0, 0, 0, k, (int)ksize, k, (int)ksize, border_type & ~MI355CV_BORDER_ISOLATED, true);
     return runSmooth("gaussianBlurBinomialBatch", src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride,
                      nframes, width, height, cn, 0, 0, 0, 0, k, (int)ksize, k, (int)ksize,
                      border_type & ~MI355CV_BORDER_ISOLATED, true);
@@ -957,22 +985,12 @@ MI355CV_API int mi355cv_gaussianBlur(const uchar* src_data, size_t src_step, uch
     // sepFilter2D itself, whose hook (mi355cv_sepFilter, ROI offsets included) reproduces that arithmetic.
     if (margin_left | margin_top | margin_right | margin_bottom)
         return mi355::setError(MI355CV_NOT_IMPLEMENTED, "gaussianBlur: submatrix with real margins is the reference's sepFilter2D case");
-    MI355_DECLINE_IF(ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE);
-    if (sigmaY <= 0) sigmaY = sigmaX;
-    std::vector<int64_t> qx, qy;
-    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx));
-    MI355_DECLINE_IF(!gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy));
-    uint16_t kx[lim::GAUSS8U_MAX_KSIZE], ky[lim::GAUSS8U_MAX_KSIZE];
-    for (size_t i = 0; i < ksize_width; i++) { MI355_DECLINE_IF(qx[i] < 0 || qx[i] > 65535); kx[i] = (uint16_t)qx[i]; }
-    for (size_t i = 0; i < ksize_height; i++) { MI355_DECLINE_IF(qy[i] < 0 || qy[i] > 65535); ky[i] = (uint16_t)qy[i]; }
-    bool binom = ksize_width == ksize_height && (ksize_width == 3 || ksize_width == 5);
-    if (binom) {
-        const uint16_t* b = binomTaps(ksize_width);
-        for (size_t i = 0; i < ksize_width; i++) if (kx[i] != b[i] || ky[i] != b[i]) binom = false;
-    }
+    GaussTaps t;
+    const int rc = gaussTapsQ88(ksize_width, ksize_height, sigmaX, sigmaY, t);
+    if (rc != MI355CV_OK) return rc;
     return runSmooth("gaussianBlur", src_data, src_step, 0, dst_data, dst_step, 0, 1, width, height, cn,
                      (int)margin_left, (int)margin_top, (int)margin_right, (int)margin_bottom,
-                     kx, (int)ksize_width, ky, (int)ksize_height, border_type & ~MI355CV_BORDER_ISOLATED, binom);
+                     t.kx, (int)ksize_width, t.ky, (int)ksize_height, border_type & ~MI355CV_BORDER_ISOLATED, t.binom);
 }
 
 // cv::GaussianBlur on CV_8U with any sigma over a batch of device-resident whole frames (no reference counterpart: SURVEY section 8e, frames are independent units): the
@@ -982,22 +1000,11 @@ MI355CV_API int mi355cv_gaussianBlurBatch(const uchar* src_data, size_t src_step
 {
     mi355::EntryGuard entry_(__func__);
     MI355_DECLINE_IF(depth != MI355CV_8U);
-    if (nframes < 1 || !(ksize_width & 1) || !(ksize_height & 1) || ksize_width > (size_t)lim::GAUSS8U_MAX_KSIZE || ksize_height > (size_t)lim::GAUSS8U_MAX_KSIZE)
-        return MI355_DECLINED("nframes < 1 || even kernel size || ksize > lim::GAUSS8U_MAX_KSIZE");
-    if (sigmaY <= 0) sigmaY = sigmaX;
-    std::vector<int64_t> qx, qy;
-    if (!gaussianKernelFixedQ((int)ksize_width, sigmaX > 0 ? sigmaX : 0, 8, qx) || !gaussianKernelFixedQ((int)ksize_height, sigmaY > 0 ? sigmaY : 0, 8, qy))
-        return MI355_DECLINED("!gaussianKernelFixedQ");
-    uint16_t kx[lim::GAUSS8U_MAX_KSIZE], ky[lim::GAUSS8U_MAX_KSIZE];
-    for (size_t i = 0; i < ksize_width; i++) { MI355_DECLINE_IF(qx[i] < 0 || qx[i] > 65535); kx[i] = (uint16_t)qx[i]; }
-    for (size_t i = 0; i < ksize_height; i++) { MI355_DECLINE_IF(qy[i] < 0 || qy[i] > 65535); ky[i] = (uint16_t)qy[i]; }
-    bool binom = ksize_width == ksize_height && (ksize_width == 3 || ksize_width == 5);
-    if (binom) {
-        const uint16_t* b = binomTaps(ksize_width);
-        for (size_t i = 0; i < ksize_width; i++) if (kx[i] != b[i] || ky[i] != b[i]) binom = false;
-    }
-    return runSmooth("gaussianBlurBatch", src_data, src_step, nframes > 1 ? src_frame_stride : 0, dst_data, dst_step, nframes > 1 ? dst_frame_stride : 0, nframes, width, height, cn,
-                     0, 0, 0, 0, kx, (int)ksize_width, ky, (int)ksize_height, border_type & ~MI355CV_BORDER_ISOLATED, binom);
+    GaussTaps t;
+    const int rc = gaussTapsQ88(ksize_width, ksize_height, sigmaX, sigmaY, t);
+    if (rc != MI355CV_OK) return rc;
+    return runSmooth("gaussianBlurBatch", src_data, src_step, src_frame_stride, dst_data, dst_step, dst_frame_stride, nframes, width, height, cn,
+                     0, 0, 0, 0, t.kx, (int)ksize_width, t.ky, (int)ksize_height, border_type & ~MI355CV_BORDER_ISOLATED, t.binom);
 }
 
 // tuning knobs for experiments (tools/tune_gauss.py): "gauss_seg" rows per work item (0 = heuristic),
@@ -1011,37 +1018,6 @@ MI355CV_API int mi355cv_setParam(const char* key, int value)
     if (!strcmp(key, "gauss_alt")) { tuneAlt() = value; return 0; }
     if (!strcmp(key, "gauss_launch_waves")) { tuneLaunchWaves() = value; return 0; }
     return -1;
-}
-
-// streaming-copy probe: copies `bytes` (multiple of 16) device->device with 16 B/lane accesses
-MI355CV_API int mi355cv_copyProbe(const void* src, void* dst, size_t bytes, int perThread, int nt)
-{
-    mi355::EntryGuard entry_(__func__);
-    MI355_DECLINE_IF(!ensureDevice() || (bytes & 15) || perThread < 1);
-    size_t n16 = bytes / 16;
-    size_t blocks = (n16 + (size_t)256 * perThread - 1) / ((size_t)256 * perThread);
-    if (nt) hipLaunchKernelGGL((k_copy16<true>), dim3((unsigned)blocks), dim3(256), 0, stream(), (const uint4*)src, (uint4*)dst, n16, perThread);
-    else    hipLaunchKernelGGL((k_copy16<false>), dim3((unsigned)blocks), dim3(256), 0, stream(), (const uint4*)src, (uint4*)dst, n16, perThread);
-    if (hipGetLastError() != hipSuccess) return MI355CV_ERROR_UNKNOWN;
-    if (!asyncMode()) (void)hipStreamSynchronize(stream());
-    return MI355CV_OK;
-}
-
-MI355CV_API int mi355cv_copyProbeColwalk(const void* src, void* dst, int W, int H, int nframes, int segRows, int unroll)
-{
-    mi355::EntryGuard entry_(__func__);
-    MI355_DECLINE_IF(!ensureDevice() || (W & 15));
-    const int nchunks = W / 16, nstrips = divUp(nchunks, 64), nseg = divUp(H, segRows);
-    const long long items = (long long)nstrips * nseg * nframes;
-    dim3 grid((unsigned)((items + 3) / 4));
-    const uchar* s = (const uchar*)src; uchar* d = (uchar*)dst;
-    if (unroll == 1) hipLaunchKernelGGL((k_copy_colwalk<1>), grid, dim3(256), 0, stream(), s, d, (size_t)W, (size_t)W * H, H, nchunks, nstrips, segRows, nseg, nframes);
-    else if (unroll == 2) hipLaunchKernelGGL((k_copy_colwalk<2>), grid, dim3(256), 0, stream(), s, d, (size_t)W, (size_t)W * H, H, nchunks, nstrips, segRows, nseg, nframes);
-    else if (unroll == 5) hipLaunchKernelGGL((k_copy_colwalk<5>), grid, dim3(256), 0, stream(), s, d, (size_t)W, (size_t)W * H, H, nchunks, nstrips, segRows, nseg, nframes);
-    else hipLaunchKernelGGL((k_copy_colwalk<10>), grid, dim3(256), 0, stream(), s, d, (size_t)W, (size_t)W * H, H, nchunks, nstrips, segRows, nseg, nframes);
-    if (hipGetLastError() != hipSuccess) return MI355CV_ERROR_UNKNOWN;
-    if (!asyncMode()) (void)hipStreamSynchronize(stream());
-    return MI355CV_OK;
 }
 
 // host-side tap generator, exported so bindings can show / test the exact Q8.8 kernel in use
@@ -1069,14 +1045,9 @@ MI355CV_API int mi355cv_sepSmoothFixedU8(const uchar* src_data, size_t src_step,
 {
     mi355::EntryGuard entry_(__func__);
     MI355_DECLINE_IF(!kx || !ky);
-    bool binom = kxlen == kylen && (kxlen == 3 || kxlen == 5);
-    if (binom) {
-        const uint16_t* b = binomTaps(kxlen);
-        for (int i = 0; i < kxlen; i++) if (kx[i] != b[i] || ky[i] != b[i]) binom = false;
-    }
     return runSmooth("sepSmoothFixedU8", src_data, src_step, 0, dst_data, dst_step, 0, 1, width, height, cn,
                      (int)margin_left, (int)margin_top, (int)margin_right, (int)margin_bottom,
-                     kx, kxlen, ky, kylen, border_type & ~MI355CV_BORDER_ISOLATED, binom);
+                     kx, kxlen, ky, kylen, border_type & ~MI355CV_BORDER_ISOLATED, isBinomial(kx, kxlen, ky, kylen));
 }
 
 } // extern "C"
